@@ -14,12 +14,16 @@ tests/test_rasterize_meshes.py:563-571).  Inputs are resident in HBM before the 
                                                                              of 64 (generator seeds 0..7), rank r runs sub-batches
                                                                              r, r+G, ...; one pass = K "steps" (K = 8/G per rank)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                                               also every leg listed below under --full
+    python bench.py ... --dump-outputs DIR                                   also the last timed step's outputs as DIR/*.npy
 
 The only collective is the final gather of the depth images to rank 0 (RCCL over xGMI), inside the timed region; its
 time is also reported separately (`gather_ms`).  Rank 0 prints ONE JSON line.
 
-Beside the headline number the line carries (rank 0, N = 1 only, all outside the timed region):
+Beside the headline number the line carries, from the timed steps themselves:
   roofline       dominant kernel: algorithmic bytes per launch / average launch duration (HIP events on the launch stream)
+With --full only (all outside the timed region; rank 0 and N = 1 only, except without_prewarm):
+  without_prewarm  the same W + K steps timed on every rank ahead of the prewarm, on a process that had run nothing before
   cpu_baseline   the reference's own CPU kernels (oracle/_ref) on a seeded 8-mesh subset of the batch at full resolution,
                  and the reference's pure-Python `rasterize_meshes_python` on BASELINE configs[0], both on this box's cores
   other_configs  BASELINE configs[1] (the reference's cow, 256^2, K=8, coarse+fine forward) and configs[3] (1M points,
@@ -92,6 +96,14 @@ def parse():
                     help="wall-clock bound for the CPU baseline legs (the Python reference takes ~31 s of it; the C++ kernels then "
                          "run as many meshes of the seeded 8-mesh subset as fit, smallest / largest / middle first, at least "
                          "two: ~10-30 s of CPU work each, the backward single-threaded)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the run without prewarm, and (rank 0, N = 1) the other BASELINE configs, the lighter "
+                         "batch, the drop-in timings, the reference's device kernels, the CPU baselines.  Off: set up, warm up, time the "
+                         "steps, print the line.  The --no-* options above select among these legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (rank 0): "
+                         "pix_to_face (float64), zbuf, bary_coords, dists on a fixed seeded sample of pixels (all K slots), and the "
+                         "gradient of the packed vertices (float32); at most 56 MB in all")
     return ap.parse_args()
 
 
@@ -566,6 +578,46 @@ def config4_cpu_baseline(budget_s=40.0):
     return out
 
 
+DUMP_FRAGMENT_BYTES = 40_000_000  # --dump-outputs: pix_to_face + zbuf + bary_coords + dists of the sampled pixels
+DUMP_VERTS_BYTES = 16_000_000     # --dump-outputs: the gradient of the packed vertices
+
+
+def _dump_rows(n_rows, row_bytes, budget, seed):
+    """Row indices to write: None (all of them) when they fit in `budget` bytes, else a fixed seeded sample, ascending."""
+    take = budget // row_bytes
+    if take >= n_rows:
+        return None
+    return torch.randperm(n_rows, generator=torch.Generator().manual_seed(seed))[:take].sort().values
+
+
+def dump_outputs(out, out_dir):
+    """--dump-outputs: what the last timed step returned to its caller, as out_dir/<name>.npy.  The fragments (N, H, W, K[, 3]) are
+    written per pixel, every K slot of a pixel together: all pixels when they fit in DUMP_FRAGMENT_BYTES, else a fixed seeded sample
+    of them (the same one in every run with the same arguments).  pix_to_face as float64 (exact), the rest float32.  The gradient of
+    the packed vertices (V, 3) likewise within DUMP_VERTS_BYTES.  -> {name: shape written}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    frag = {n: out[n].detach() for n in ("pix_to_face", "zbuf", "bary_coords", "dists")}
+    dtype = {n: torch.float64 if n == "pix_to_face" else torch.float32 for n in frag}
+    n_px = math.prod(frag["pix_to_face"].shape[:3])
+    px_bytes = sum(math.prod(x.shape[3:]) * dtype[n].itemsize for n, x in frag.items())
+    parts = [(frag, _dump_rows(n_px, px_bytes, DUMP_FRAGMENT_BYTES, seed=0), 3)]
+    gv = out["verts_packed_grad"].detach()
+    parts.append(({"verts_packed_grad": gv}, _dump_rows(gv.shape[0], 3 * 4, DUMP_VERTS_BYTES, seed=1), 1))
+    dtype["verts_packed_grad"] = torch.float32
+    written = {}
+    for arrays, rows, lead in parts:
+        for n, x in arrays.items():
+            x = x.reshape((-1,) + tuple(x.shape[lead:]))
+            if rows is not None:
+                x = x[rows.to(x.device)]
+            a = x.to(dtype[n]).cpu().numpy()
+            np.save(os.path.join(out_dir, n + ".npy"), a)
+            written[n] = list(a.shape)
+    return written
+
+
 def dry_run(world, rank, local_rank):
     """`--dry-run`: the launch plumbing of an N-GPU run without RCCL and without a kernel -- what a first contact with an 8-GPU node
     should not have to debug.  Every rank reports (RANK, LOCAL_RANK, the device it would bind, visible devices, pid) over gloo;
@@ -574,7 +626,8 @@ def dry_run(world, rank, local_rank):
     `--gpus 8 --dry-run` lists seven devices that do not exist)."""
     import torch.distributed as dist
 
-    visible = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    counted = os.environ.get("P3D_BENCH_DEVICES_VISIBLE")  # set by spawn_ranks: the ranks then never open a device at all
+    visible = int(counted) if counted is not None else (torch.cuda.device_count() if torch.cuda.is_available() else 0)
     mine = {"rank": rank, "local_rank": local_rank, "device": f"cuda:{local_rank}", "devices_visible": visible, "pid": os.getpid(),
             "master": f"{os.environ.get('MASTER_ADDR', '?')}:{os.environ.get('MASTER_PORT', '?')}",
             "ipc_mode_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")}
@@ -620,6 +673,8 @@ def spawn_ranks(args):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC: RCCL across processes needs it on this driver
+    if args.dry_run:  # counted once, here: N ranks that opened the devices only to count them would hold N device handles at once
+        env["P3D_BENCH_DEVICES_VISIBLE"] = str(have)
     env.setdefault("OMP_NUM_THREADS", str(max(1, usable_cores() // n)))
     return subprocess.call(cmd, env=env)
 
@@ -799,13 +854,15 @@ def main():
     g_b = torch.randn((B, H, W, K, 3), generator=gen).to(device)
     g_d = torch.randn((B, H, W, K), generator=gen).to(device)
 
-    def step(i):
+    def step(i, keep=None):
         meshes, vp, _, _, _ = batches[i % len(batches)]
         vp.grad = None
         m = meshes.update_verts_packed(vp)
         p2f, zbuf, bary, dists = p3d.rasterize_meshes(m, image_size=(H, W), blur_radius=blur, faces_per_pixel=K,
                                                       perspective_correct=True, clip_barycentric_coords=True)
         torch.autograd.backward([zbuf, bary, dists], [g_z, g_b, g_d])
+        if keep is not None:  # the last timed step under --dump-outputs: what its caller receives
+            keep.update(pix_to_face=p2f, zbuf=zbuf, bary_coords=bary, dists=dists, verts_packed_grad=vp.grad)
         return p2f, zbuf
 
     own = [B] * world if not jobs_mode else [B * len(sub_batches_of_rank(args.jobs, B, r, world)) for r in range(world)]
@@ -826,9 +883,9 @@ def main():
                 return None
 
     # The driver's protocol to the letter first (W warm-up steps, K timed, nothing ahead of them): reported beside the headline as
-    # `without_prewarm`, so that the two protocols never have to be compared across runs.
+    # `without_prewarm`, so that the two protocols never have to be compared across runs.  --full only.
     cold = None
-    if args.prewarm_s > 0 and not jobs_mode:
+    if args.full and args.prewarm_s > 0 and not jobs_mode:
         for i in range(args.warmup):
             step(i)
         torch.cuda.synchronize()
@@ -861,11 +918,12 @@ def main():
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
+    last = {} if args.dump_outputs else None
     t0 = time.perf_counter()
     kept = []
     ev[0].record()
     for i in range(steps):
-        p2f, zbuf = step(i)
+        p2f, zbuf = step(i, last if i == steps - 1 else None)
         ev[i + 1].record()
         if jobs_mode:
             kept.append(zbuf)
@@ -900,6 +958,11 @@ def main():
         gather_ms = max(p["gather_ms"] for p in per_rank)
     else:
         elapsed, gather_ms = float(mine[0]), float(mine[1])
+    dumped = None
+    if last is not None:
+        if rank == 0:
+            dumped = dump_outputs(last, args.dump_outputs)
+        del last
     per_step = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(steps))
     median_ms = per_step[len(per_step) // 2]
     valid = p2f >= 0
@@ -1027,56 +1090,59 @@ def main():
                 "total_faces_per_rank": total_faces, "pixel_slot_fill": hit_frac, "covered_pixel_fraction": covered / px,
                 "parallelism": f"batch-sharded x{world}, final gather to rank 0 only",
                 "path": "pytorch3d_amd.rasterize_meshes -- this package's L2 mirror of renderer/mesh/rasterize_meshes.py (autograd Function over "
-                        "the C ABI); the unmodified reference MeshRasterizer over pytorch3d._C on the same batch is timed beside it: dropin_ms_per_step",
+                        "the C ABI); with --full the unmodified reference MeshRasterizer over pytorch3d._C on the same batch is timed beside it: dropin_ms_per_step",
             },
             "roofline": roofline,
             "kernels_ms": {k: round(v["avg_ms"], 4) for k, v in sorted(kernels.items())},
         }
-        if world == 1 and not args.no_other_configs:
-            try:
-                out["other_configs"] = other_configs(lib, _lib, device)
-            except Exception as e:
-                out["other_configs"] = {"error": repr(e)}
-        if world == 1 and not jobs_mode and not args.no_other_configs:
-            try:
-                out["workload_torus_div_1.5"] = light_workload_sensitivity(device, B, H, W, K, blur)
-            except Exception as e:
-                out["workload_torus_div_1.5"] = {"error": repr(e)}
-        if world == 1 and not jobs_mode and not args.no_dropin:
-            out["dropin"] = dropin_timing(B, H)
-            out["dropin"]["mirror_ms_per_step"] = elapsed / steps * 1e3
-            # what `from pytorch3d.renderer import MeshRasterizer` gets on the same batch, next to the headline's own path
-            out["config"]["dropin_ms_per_step"] = {k: round(v["ms_per_step"], 4) for k, v in out["dropin"].items()
-                                                   if isinstance(v, dict) and v.get("ms_per_step")}
-            if B == 64 and H == 512 and isinstance(out.get("other_configs"), dict):
-                out["other_configs"]["config4_points_renderer_dropin"] = dropin_points_timing()
-        if world == 1 and not jobs_mode and not args.no_other_configs and B == 64 and H == 512 and isinstance(out.get("other_configs"), dict):
-            try:  # the N = 1 anchor of BASELINE configs[4]'s scaling curve, timed on this build in this run
-                out["other_configs"]["config5_jobs512_1gpu"] = config5_one_gpu(args, device, H, W, K, blur, value)
-            except Exception as e:
-                out["other_configs"]["config5_jobs512_1gpu"] = {"error": repr(e)}
-        if world == 1 and not jobs_mode and not args.no_reference_device:
-            try:  # the same-GPU baseline: the reference's own device kernels on the bench batch
-                _, _, _, verts_cpu, faces_cpu = batches[0]
-                rd = reference_device_leg(device, verts_cpu, faces_cpu, H, W, K, blur, elapsed / steps * 1e3)
-                out["vs_reference_device"] = rd
-                if rd.get("value"):
-                    out["vs_baseline"] = value / rd["value"]
-                    out["vs_baseline_note"] = ("BASELINE.md publishes no number for this metric; the ratio is against the reference's own device kernels "
-                                               "compiled for this GPU and timed in this run (vs_reference_device)")
-            except Exception as e:
-                out["vs_reference_device"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            try:
-                _, _, _, verts_cpu, faces_cpu = batches[0]
-                out["cpu_baseline"] = cpu_baseline(verts_cpu, faces_cpu, H, W, K, blur, args.cpu_budget_s)
-            except Exception as e:  # the baseline must never sink the GPU measurement
-                out["cpu_baseline"] = {"value": None, "error": repr(e)}
-            if isinstance(out.get("other_configs"), dict) and isinstance(out["other_configs"].get("config4_points_1m_512_k10_fwd_bwd"), dict):
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
+        if args.full:  # everything beyond the headline: the --no-* options select among these legs
+            if world == 1 and not args.no_other_configs:
                 try:
-                    out["other_configs"]["config4_points_1m_512_k10_fwd_bwd"]["cpu_baseline"] = config4_cpu_baseline()
+                    out["other_configs"] = other_configs(lib, _lib, device)
                 except Exception as e:
-                    out["other_configs"]["config4_points_1m_512_k10_fwd_bwd"]["cpu_baseline"] = {"value": None, "error": repr(e)}
+                    out["other_configs"] = {"error": repr(e)}
+            if world == 1 and not jobs_mode and not args.no_other_configs:
+                try:
+                    out["workload_torus_div_1.5"] = light_workload_sensitivity(device, B, H, W, K, blur)
+                except Exception as e:
+                    out["workload_torus_div_1.5"] = {"error": repr(e)}
+            if world == 1 and not jobs_mode and not args.no_dropin:
+                out["dropin"] = dropin_timing(B, H)
+                out["dropin"]["mirror_ms_per_step"] = elapsed / steps * 1e3
+                # what `from pytorch3d.renderer import MeshRasterizer` gets on the same batch, next to the headline's own path
+                out["config"]["dropin_ms_per_step"] = {k: round(v["ms_per_step"], 4) for k, v in out["dropin"].items()
+                                                       if isinstance(v, dict) and v.get("ms_per_step")}
+                if B == 64 and H == 512 and isinstance(out.get("other_configs"), dict):
+                    out["other_configs"]["config4_points_renderer_dropin"] = dropin_points_timing()
+            if world == 1 and not jobs_mode and not args.no_other_configs and B == 64 and H == 512 and isinstance(out.get("other_configs"), dict):
+                try:  # the N = 1 anchor of BASELINE configs[4]'s scaling curve, timed on this build in this run
+                    out["other_configs"]["config5_jobs512_1gpu"] = config5_one_gpu(args, device, H, W, K, blur, value)
+                except Exception as e:
+                    out["other_configs"]["config5_jobs512_1gpu"] = {"error": repr(e)}
+            if world == 1 and not jobs_mode and not args.no_reference_device:
+                try:  # the same-GPU baseline: the reference's own device kernels on the bench batch
+                    _, _, _, verts_cpu, faces_cpu = batches[0]
+                    rd = reference_device_leg(device, verts_cpu, faces_cpu, H, W, K, blur, elapsed / steps * 1e3)
+                    out["vs_reference_device"] = rd
+                    if rd.get("value"):
+                        out["vs_baseline"] = value / rd["value"]
+                        out["vs_baseline_note"] = ("BASELINE.md publishes no number for this metric; the ratio is against the reference's own device kernels "
+                                                   "compiled for this GPU and timed in this run (vs_reference_device)")
+                except Exception as e:
+                    out["vs_reference_device"] = {"value": None, "error": repr(e)}
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    _, _, _, verts_cpu, faces_cpu = batches[0]
+                    out["cpu_baseline"] = cpu_baseline(verts_cpu, faces_cpu, H, W, K, blur, args.cpu_budget_s)
+                except Exception as e:  # the baseline must never sink the GPU measurement
+                    out["cpu_baseline"] = {"value": None, "error": repr(e)}
+                if isinstance(out.get("other_configs"), dict) and isinstance(out["other_configs"].get("config4_points_1m_512_k10_fwd_bwd"), dict):
+                    try:
+                        out["other_configs"]["config4_points_1m_512_k10_fwd_bwd"]["cpu_baseline"] = config4_cpu_baseline()
+                    except Exception as e:
+                        out["other_configs"]["config4_points_1m_512_k10_fwd_bwd"]["cpu_baseline"] = {"value": None, "error": repr(e)}
         print(json.dumps(out), flush=True)
     if dist_on:
         dist.destroy_process_group()

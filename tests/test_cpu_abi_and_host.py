@@ -491,6 +491,43 @@ def test_bench_jobs_mode_deals_every_sub_batch_to_exactly_one_rank():
         bench.sub_batches_of_rank(500, 64, 0, 2)
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample_within_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (bench.py: dump_outputs) on CPU tensors shaped like the step's outputs: outputs that fit are written
+    whole; past the byte budget a fixed seeded sample of pixels (every K slot of each, the same pixels in every array, ascending) and
+    of vertex rows; float64 pix_to_face, float32 for the rest; the same files from two calls."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(U.ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    N, H, W, K, V = 2, 16, 16, 4, 100
+    pix = torch.arange(N * H * W * K, dtype=torch.int64).view(N, H, W, K)  # entry = pixel * K + slot
+    out = {"pix_to_face": pix, "zbuf": pix.float(), "dists": -pix.float(), "bary_coords": pix.float()[..., None].expand(-1, -1, -1, -1, 3),
+           "verts_packed_grad": torch.arange(V * 3, dtype=torch.float32).view(V, 3)}
+    whole = bench.dump_outputs(out, str(tmp_path / "whole"))
+    assert whole == {"pix_to_face": [N * H * W, K], "zbuf": [N * H * W, K], "bary_coords": [N * H * W, K, 3], "dists": [N * H * W, K],
+                     "verts_packed_grad": [V, 3]}
+    assert np.array_equal(np.load(tmp_path / "whole" / "pix_to_face.npy"), pix.view(-1, K).double().numpy())
+
+    monkeypatch.setattr(bench, "DUMP_FRAGMENT_BYTES", 10_000)  # K * (8 + 4 + 12 + 4) = 112 bytes per pixel -> 89 of 512 pixels
+    monkeypatch.setattr(bench, "DUMP_VERTS_BYTES", 600)        # 12 bytes per vertex -> 50 of 100 rows
+    runs = [bench.dump_outputs(out, str(tmp_path / r)) for r in ("a", "b")]
+    assert runs[0] == runs[1] and runs[0]["pix_to_face"] == [89, K] and runs[0]["verts_packed_grad"] == [50, 3]
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in runs[0]}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in runs[0]}
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert a["pix_to_face"].dtype == np.float64 and all(a[n].dtype == np.float32 for n in a if n != "pix_to_face")
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in a) <= 10_000 + 600 + 5 * 128  # + the .npy headers
+    px = a["pix_to_face"][:, 0] / K
+    assert np.all(np.diff(px) > 0) and np.array_equal(a["pix_to_face"], px[:, None] * K + np.arange(K))  # whole pixels, ascending
+    assert np.array_equal(a["zbuf"], a["pix_to_face"]) and np.array_equal(a["dists"], -a["pix_to_face"])
+    assert np.array_equal(a["bary_coords"], np.repeat(a["pix_to_face"][..., None], 3, -1))
+    rows = a["verts_packed_grad"][:, 0] / 3
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a["verts_packed_grad"], rows[:, None] * 3 + np.arange(3))
+
+
 def test_pybind_flavour_builds_and_exports_the_operator_set():
     """pytorch3d_amd/csrc/bind.cpp (INTEGRATION.md section B compiled): the torch extension builds against include/p3d_amd.h, links
     libp3d_amd.so and exports every hot-path operator of `pytorch3d._C` under the reference's names (no compute call without a GPU)."""

@@ -1,4 +1,4 @@
-"""CPU suite, part 4: the N>1 path on 2 gloo ranks.
+"""CPU suite, part 4: the N>1 path on 2 and 8 gloo ranks.
 
 The batch of independent (mesh, camera) jobs is partitioned by cost, every rank rasterizes its own
 slice (here with the oracle as the stand-in compute function -- the driver is agnostic to it), local
@@ -63,11 +63,9 @@ def _worker(rank, world, port, out_dir):
         dist.destroy_process_group()
 
 
-@pytest.mark.timeout(300)
-def test_two_rank_sharded_render_equals_unsharded(tmp_path):
+def _sharded_equals_unsharded(world, tmp_path):
     from oracle import oracle as orc
 
-    world = 2
     port = _free_port()
     mp.spawn(_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     fv, first, cnt = _problem()
@@ -79,6 +77,20 @@ def test_two_rank_sharded_render_equals_unsharded(tmp_path):
         assert torch.equal(got["z"], ref[1])
         parts = got["parts"]
         assert parts[0][0] == 0 and parts[-1][1] == 5 and all(a[1] == b[0] for a, b in zip(parts, parts[1:]))
+    return parts
+
+
+@pytest.mark.timeout(300)
+def test_two_rank_sharded_render_equals_unsharded(tmp_path):
+    _sharded_equals_unsharded(2, tmp_path)
+
+
+@pytest.mark.timeout(300)
+def test_eight_rank_sharded_render_equals_unsharded(tmp_path):
+    """The N = 8 rendezvous and gather of bench.py's collective (sharding.gather_batch, all_gather and gather to rank 0): 5 jobs over
+    8 ranks, so that at least three ranks own empty shards, assemble the un-sharded batch bit for bit on every rank."""
+    parts = _sharded_equals_unsharded(8, tmp_path)
+    assert sum(b == a for a, b in parts) >= 3
 
 
 def test_partition_properties():

@@ -39,7 +39,7 @@ def _check_common(j, n_gpus, steps):
 
 def test_single_rank_line_small():
     j = _run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--batch", "4", "--image-size", "128",
-              "--no-cpu-baseline"])
+              "--no-cpu-baseline", "--full"])
     _check_common(j, 1, 3)
     assert j["scaling"] == "weak" and "other_configs" in j
     assert j["without_prewarm"]["value"] > 0 and j["without_prewarm"]["steps"] == 3  # the driver's protocol to the letter, beside the headline
@@ -118,28 +118,95 @@ def _torchrun(n, port, extra, timeout=200):
     return _run(cmd, {"P3D_BENCH_TEST_BACKEND": "gloo", "OMP_NUM_THREADS": "1"}, timeout=timeout)
 
 
-def test_eight_ranks_and_an_uneven_deal_gather_what_one_rank_renders():
-    """The N > 1 path as far as one GPU allows: EIGHT ranks over gloo sharing cuda:0, weak mode (rank r
-    renders generator seed r) and `--jobs` (8 sub-batches dealt to 8 ranks, and to THREE: 3 + 3 + 2), against ONE rank running the
-    same 8 sub-batches: the depth images gathered on rank 0 are the same bytes, in job order, in all four runs; every rank's clock
-    and kernel time ride in the line."""
+def test_three_ranks_and_an_uneven_deal_gather_what_one_rank_renders():
+    """The N > 1 path as far as one GPU allows: THREE ranks over gloo sharing cuda:0, so that at most five
+    processes hold the device at once (the ranks, the launcher -- torch.distributed.run asks torch.cuda.is_available(), which opens
+    it -- and this process), in weak mode (rank r renders generator seed r), in `--jobs` mode with one sub-batch per rank, and in
+    `--jobs` mode with 8 sub-batches dealt 3 + 3 + 2, each against ONE rank running the same sub-batches: the depth images gathered
+    on rank 0 are the same bytes, in job order; every rank's clock and kernel time ride in the line.  The eight-rank rendezvous and
+    gather: tests/test_cpu_sharding_gloo.py."""
     import time
 
     t0 = time.time()
-    single = _run([sys.executable, "bench.py", "--gpus", "1", "--warmup", "1", "--batch", "2", "--image-size", "64", "--jobs", "16",
-                   "--prewarm-s", "0", "--gather-checksum", "--no-other-configs", "--no-cpu-baseline", "--no-dropin", "--no-reference-device"])
-    ref = single["gather"]["gathered"]
-    assert ref["shape"] == [16, 64, 64] and single["config"]["global_batch"] == 16 and single["steps"] == 8
-    runs = {"weak x8": _torchrun(8, 29581, ["--steps", "2"]), "jobs x8": _torchrun(8, 29582, ["--jobs", "16"]),
-            "jobs x3 (3 + 3 + 2)": _torchrun(3, 29583, ["--jobs", "16"])}
-    for name, j in runs.items():
+
+    def single(jobs):
+        return _run([sys.executable, "bench.py", "--gpus", "1", "--warmup", "1", "--batch", "2", "--image-size", "64", "--jobs", str(jobs),
+                     "--prewarm-s", "0", "--gather-checksum", "--no-other-configs", "--no-cpu-baseline", "--no-dropin", "--no-reference-device"])
+
+    ref = {}
+    for jobs in (6, 16):
+        j = single(jobs)
+        ref[jobs] = j["gather"]["gathered"]
+        assert ref[jobs]["shape"] == [jobs, 64, 64] and j["config"]["global_batch"] == jobs and j["steps"] == jobs // 2
+    runs = {"weak x3": (6, _torchrun(3, 29581, ["--steps", "2"])), "jobs x3 (1 + 1 + 1)": (6, _torchrun(3, 29582, ["--jobs", "6"])),
+            "jobs x3 (3 + 3 + 2)": (16, _torchrun(3, 29583, ["--jobs", "16"]))}
+    for name, (jobs, j) in runs.items():
         n = j["n_gpus"]
         got = j["gather"]["gathered"]
-        assert j["gather"]["ok"] and (got["sha256"], got["shape"]) == (ref["sha256"], ref["shape"]), (name, j["gather"], ref)
+        assert n == 3 and j["gather"]["ok"] and (got["sha256"], got["shape"]) == (ref[jobs]["sha256"], ref[jobs]["shape"]), (name, j["gather"], ref)
         assert len(j["per_rank"]) == n and all(p["mesh_fine_ms"] > 0 and p["mesh_backward_ms"] > 0 and p["seconds"] > 0 for p in j["per_rank"]), name
-        assert j["config"]["global_batch"] == 16 and j["value"] > 0
-    assert runs["jobs x3 (3 + 3 + 2)"]["steps"] == 3 and runs["jobs x8"]["steps"] == 1 and runs["weak x8"]["scaling"] == "weak"
+        assert j["config"]["global_batch"] == jobs and j["value"] > 0
+    assert runs["jobs x3 (3 + 3 + 2)"][1]["steps"] == 3 and runs["jobs x3 (1 + 1 + 1)"][1]["steps"] == 1
+    assert runs["weak x3"][1]["scaling"] == "weak"
     assert time.time() - t0 < 240, "the multi-rank plumbing test is meant to stay short"
+
+
+def test_plain_line_is_lean_and_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: K timed steps, the headline keys, no leg of --full.  With
+    `--dump-outputs DIR` it writes what the last timed step returned (float32 / float64, at most 64 MB; every pixel at this size):
+    the same fragments as the step recomputed here on the same inputs, and the same in two runs with the same arguments (the vertex
+    gradient sums with atomics: to rounding)."""
+    import importlib.util
+    import math
+
+    import numpy as np
+    import torch
+
+    import pytorch3d_amd as p3d
+
+    names = ("pix_to_face", "zbuf", "bary_coords", "dists", "verts_packed_grad")
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        j = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4", "--image-size", "128",
+                  "--dump-outputs", str(d)])
+        _check_common(j, 1, 3)
+        full_only = ("without_prewarm", "other_configs", "workload_torus_div_1.5", "dropin", "vs_reference_device", "cpu_baseline")
+        assert all(j.get(k) is None for k in full_only), {k: j[k] for k in full_only if j.get(k) is not None}
+        assert j["vs_baseline"] is None and j["prewarm_steps"] > 0
+        assert sorted(os.listdir(d)) == sorted(n + ".npy" for n in names)
+        assert sum(os.path.getsize(d / (n + ".npy")) for n in names) <= 64e6
+        arrs = {n: np.load(d / (n + ".npy")) for n in names}
+        assert arrs["pix_to_face"].dtype == np.float64 and all(arrs[n].dtype == np.float32 for n in names[1:])
+        assert {n: list(a.shape) for n, a in arrs.items()} == j["dump_outputs"]["shapes"]
+        dumps.append(arrs)
+    a, b = dumps
+    px = 4 * 128 * 128
+    assert a["pix_to_face"].shape == (px, 8) and a["bary_coords"].shape == (px, 8, 3) and a["verts_packed_grad"].shape[1] == 3
+    hit = a["pix_to_face"] >= 0
+    assert 0 < hit.mean() < 1 and np.all(a["zbuf"][hit] > 0) and np.all(a["pix_to_face"] == np.round(a["pix_to_face"]))
+    for n in names[:4]:
+        assert np.array_equal(a[n], b[n]), n
+    g = a["verts_packed_grad"]
+    assert np.isfinite(g).all() and np.abs(g).max() > 0
+    np.testing.assert_allclose(b["verts_packed_grad"], g, rtol=1e-4, atol=1e-5 * float(np.abs(g).max()))
+
+    # bench.py's step on its own inputs (build_batch seed 0, upstream gradients from generator seed 231, SoftRas blur), here
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev, B, H, K = torch.device("cuda:0"), 4, 128, 8
+    meshes, _, _, _ = bench.build_batch(B, seed=0, device=dev)
+    vp = meshes.verts_packed().clone().requires_grad_(True)
+    gen = torch.Generator().manual_seed(231)
+    ups = [torch.randn(sh, generator=gen).to(dev) for sh in ((B, H, H, K), (B, H, H, K, 3), (B, H, H, K))]
+    p2f, zbuf, bary, dists = p3d.rasterize_meshes(meshes.update_verts_packed(vp), image_size=(H, H), blur_radius=math.log(1.0 / 1e-4 - 1.0) * 1e-4,
+                                                  faces_per_pixel=K, perspective_correct=True, clip_barycentric_coords=True)
+    torch.autograd.backward([zbuf, bary, dists], ups)
+    want = {"pix_to_face": p2f.double(), "zbuf": zbuf, "bary_coords": bary, "dists": dists}
+    for n, w in want.items():
+        assert np.array_equal(a[n], w.detach().reshape((px,) + tuple(w.shape[3:])).cpu().numpy()), n
+    np.testing.assert_allclose(g, vp.grad.cpu().numpy(), rtol=1e-4, atol=1e-5 * float(np.abs(g).max()))
 
 
 def test_dry_run_of_an_eight_gpu_launch_maps_ranks_to_devices():
