@@ -559,6 +559,25 @@ int p3d_hard_rgb_blend_forward(const float* colors, const int64_t* pix_to_face, 
 int p3d_hard_rgb_blend_backward(const float* grad_out, const int64_t* pix_to_face, int64_t npix, int K, float* grad_colors,
                                 p3d_stream_t stream);
 
+/* ---- SplatterPhongShader's blend ------------------------------------------------------------------------------------
+ *
+ * replaces SplatterBlender.forward (pytorch3d/renderer/splatter_blend.py) after its camera call: masking, the 9-direction
+ * occlusion layers, the splat weights, the three-buffer accumulation, normalisation and back-to-front compositing in one
+ * launch, nothing of size 9 x K per pixel in memory.  colors (N,H,W,K,3), screen_coords (N,H,W,K,3) =
+ * cameras.transform_points_screen(..., with_xyflip=False), both contiguous f32; background_mask (N,H,W,K) one byte per
+ * entry, nonzero where pix_to_face < 0 (a torch.bool tensor); sigma > 0; any K >= 1, any H, W.
+ *   forward: out (N,H,W,4) RGBA, 16-byte aligned, fully written.
+ *   backward: grad_out (N,H,W,4) -> grad_colors, grad_screen_coords (N,H,W,K,3) fully written (zero at background
+ *   entries, zero z).  Gather form without atomics: bit-identical from run to run.  The workspace (16-byte aligned)
+ *   holds one 96-byte record per pixel: p3d_splatter_blend_backward_workspace_bytes(). */
+size_t p3d_splatter_blend_backward_workspace_bytes(int N, int H, int W);
+int p3d_splatter_blend_forward(const float* colors, const float* screen_coords, const uint8_t* background_mask, float sigma,
+                               const float background[3], int N, int H, int W, int K, float* out, p3d_stream_t stream);
+int p3d_splatter_blend_backward(const float* grad_out, const float* colors, const float* screen_coords,
+                                const uint8_t* background_mask, float sigma, const float background[3], int N, int H, int W,
+                                int K, float* grad_colors, float* grad_screen_coords, void* workspace, size_t workspace_bytes,
+                                p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

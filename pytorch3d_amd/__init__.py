@@ -7,6 +7,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     interpolate_face_attributes      host-side mirrors of the reference's L2 functions
     clip_faces, softmax_rgb_blend, sigmoid_alpha_blend, hard_rgb_blend, phong_shading, sample_textures_uv,
     sample_textures_atlas            the neighbouring steps, fused
+    splatter_blend, SplatterBlender  SplatterPhongShader's blend, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -20,6 +21,7 @@ from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401
 from .shading import (flat_shading, gouraud_shading, phong_shading, phong_shading_vertex_colors,  # noqa: F401
                       soft_phong_shading)
+from .splatter import SplatterBlender, phong_shading_with_pixels, splatter_blend  # noqa: F401
 from .structures import PackedMeshes, PackedPointclouds  # noqa: F401
 from .textures import sample_textures_atlas, sample_textures_uv  # noqa: F401
 

@@ -294,6 +294,7 @@ def patch_reference_python():
     _patch_mesh_rasterizer(our_rm)
     _patch_points_rasterizer(our_rm)
     _patch_soft_phong_shader(our_shade)
+    _patch_splatter_phong_shader(importlib.import_module(__package__ + ".splatter"))
     _patch_meshes_offset_verts()
     _patch_hard_and_silhouette_shaders()
 
@@ -644,6 +645,48 @@ def _patch_soft_phong_shader(our_shade):
     forward.__wrapped__ = orig
     shader.SoftPhongShader.forward = forward
     _PATCHED.append((shader.SoftPhongShader, "forward", orig, forward))
+
+
+def _patch_splatter_phong_shader(our_splat):
+    """SplatterPhongShader.forward (shader.py:309-374): texels = meshes.sample_textures(fragments); _phong_shading_with_pixels on
+    the detached fragments; SplatterBlender -> pytorch3d_amd.splatter (fused Phong + interpolation kernels, the reference's
+    camera call for the screen transform, one blend kernel; no (N,H,W,K,9,5) tensors).  The sigma warning of
+    check_blend_params is kept.  Falls back to the reference's forward for CPU tensors, colour widths other than 3, a
+    background colour that requires grad and whatever _shading_ok rejects."""
+    import importlib
+
+    shader = importlib.import_module("pytorch3d.renderer.mesh.shader")
+    cls = getattr(shader, "SplatterPhongShader", None)
+    if cls is None:
+        return
+    orig = cls.forward
+
+    def forward(self, fragments, meshes, **kwargs):
+        try:
+            cameras = self._get_cameras(**kwargs)
+            lights = kwargs.get("lights", self.lights)
+            materials = kwargs.get("materials", self.materials)
+            blend_params = kwargs.get("blend_params", self.blend_params)
+            ok = (_shading_ok(meshes, fragments, lights, cameras, materials) and hasattr(cameras, "transform_points_screen")
+                  and float(blend_params.sigma) > 0.0 and not getattr(blend_params.background_color, "requires_grad", False))
+        except Exception:
+            ok = False
+        texels = None
+        if ok:
+            texels = meshes.sample_textures(fragments)
+            ok = _is_hip_f32(texels) and texels.dim() == 5 and texels.shape[-1] == 3
+        _count("SplatterPhongShader.forward", ok)
+        if not ok:
+            return orig(self, fragments, meshes, **kwargs)
+        colors, pixel_coords_cameras = our_splat.phong_shading_with_pixels(meshes, fragments.detach(), lights, cameras, materials,
+                                                                           texels)
+        self.check_blend_params(blend_params)
+        return our_splat.SplatterBlender(tuple(colors.shape[:4]), colors.device)(colors, pixel_coords_cameras, cameras,
+                                                                                fragments.pix_to_face < 0, blend_params)
+
+    forward.__wrapped__ = orig
+    cls.forward = forward
+    _PATCHED.append((cls, "forward", orig, forward))
 
 
 def _patch_hard_and_silhouette_shaders():
