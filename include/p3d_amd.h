@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define P3D_ABI_VERSION 1
+#define P3D_ABI_VERSION 2
 
 #define P3D_OK 0
 #define P3D_ERR_INVALID_ARG (-1)   /* null pointer / negative size / bad mode                    */
@@ -57,7 +57,7 @@ const char* p3d_error_string(int code);
  * state between them. */
 size_t p3d_rasterize_meshes_workspace_bytes(int64_t F, int N, int H, int W, int bin_size, int max_faces_per_bin);
 
-/* Short workspaces (p3d_rasterize_meshes and p3d_rasterize_meshes_with_cover only; the reference has no counterpart: its
+/* Short workspaces (p3d_rasterize_meshes and p3d_rasterize_meshes_ex only; the reference has no counterpart: its
  * coarse stage allocates the padded (N, BH, BW, max_faces_per_bin) tensor, rasterize_coarse.cu:353-354).
  * Those two calls accept ANY workspace of at least p3d_rasterize_meshes_short_workspace_bytes(..., list_entries = 0) bytes:
  * the bin lists get whatever room is left after the fixed arrays.  Whether the lists fit is decided on the device, after
@@ -111,23 +111,18 @@ int p3d_rasterize_meshes_fine(const float* face_verts, const int32_t* bin_faces,
                               float* bary, float* dists, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
 /* replaces RasterizeMeshesBackward, rasterize_meshes.h:211-252 (_C.rasterize_meshes_backward).
- * grad_face_verts (F,3,3) f32 is zeroed and accumulated here. */
+ * grad_face_verts (F,3,3) f32 is zeroed and accumulated here.  = p3d_rasterize_meshes_backward_ex(no faces, no records, no
+ * cover, flags 0). */
 int p3d_rasterize_meshes_backward(const float* face_verts, const int64_t* pix_to_face, const float* grad_zbuf,
                                   const float* grad_bary, const float* grad_dists, int64_t F, int N, int H, int W, int K,
                                   int perspective_correct, int clip_barycentric_coords, float* grad_face_verts,
                                   p3d_stream_t stream);
-/* The same backward with the gradient of `face_verts = verts_packed[faces_packed]` (rasterize_meshes.py:146, torch
- * indexing + its index_put backward) fused in: the per-face partials are flushed straight to grad_verts (V,3) through
- * faces (F,3) -- no (F,3,3) intermediate, no separate scatter.  grad_verts zeroed and accumulated. */
-int p3d_rasterize_meshes_backward_verts(const float* face_verts, const int64_t* faces, const int64_t* pix_to_face,
-                                        const float* grad_zbuf, const float* grad_bary, const float* grad_dists, int64_t F,
-                                        int64_t V, int N, int H, int W, int K, int perspective_correct,
-                                        int clip_barycentric_coords, float* grad_verts, p3d_stream_t stream);
 
-/* ---- row cover: what the forward knows about empty image regions, handed to the backward (round 3) ----
- * The reference's autograd node saves pix_to_face for the backward (renderer/mesh/rasterize_meshes.py:291-296) and the
- * backward kernel reads all N*H*W*K entries of it to find the samples that hold a face (rasterize_meshes.cu:593-603).  At
- * the bench workload 68 % of those reads find nothing.  The forward can say so for free: `cover` is (N, ceil(H/16),
+/* ---- the forward with what it can tell the backward, and the backward that uses it ------------------------------------
+ *
+ * Row cover (round 3).  The reference's autograd node saves pix_to_face for the backward (renderer/mesh/rasterize_meshes.py:
+ * 291-296) and the backward kernel reads all N*H*W*K entries of it to find the samples that hold a face (rasterize_meshes.cu:
+ * 593-603).  At the bench workload 68 % of those reads find nothing.  The forward can say so for free: `cover` is (N, ceil(H/16),
  * ceil(W/16)) int32; bit r of word (n, cy, cx) is set iff some pixel of output row 16*cy + r, columns 16*cx .. 16*cx+15 of
  * image n holds a face (pix_to_face[n, y, x, 0] >= 0).  The autograd nodes of pytorch3d_amd/rasterize_meshes.py save it
  * next to pix_to_face; a backward without cover (the `_C.rasterize_meshes_backward` drop-in) reads everything, as before.
@@ -142,97 +137,76 @@ size_t p3d_rasterize_meshes_cover_bytes(int N, int H, int W);
 int p3d_rasterize_meshes_cover_check(const int64_t* pix_to_face, const int32_t* cover, int N, int H, int W, int K, int32_t* stale,
                                      p3d_stream_t stream);
 
-/* p3d_rasterize_meshes + the row cover of its output (cover may be null: then identical to p3d_rasterize_meshes). */
-int p3d_rasterize_meshes_with_cover(const float* face_verts, const int64_t* mesh_to_face_first_idx,
-                                    const int64_t* num_faces_per_mesh, const int64_t* clipped_faces_neighbor_idx, int64_t F,
-                                    int N, int H, int W, float blur_radius, int faces_per_pixel, int bin_size,
-                                    int max_faces_per_bin, int perspective_correct, int clip_barycentric_coords,
-                                    int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary, float* dists,
-                                    int32_t* cover, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
-
-/* The cover AND the list of its non-empty words (round 6): `cover_and_list` is one buffer of p3d_rasterize_meshes_cover_list_bytes --
- * the (N, ceil(H/16), ceil(W/16)) words of the cover as above, an int32 counter (+ 15 spare), then room for one int32 per word.
- * The wave that sets the first bit of a word appends the word's index to the list (one atomic per 16 x 16 pixel block that holds a
- * face), so the backward finds its work without a pass over the cover: p3d_rasterize_meshes_backward[_verts]_with_cover_list take
- * the same buffer and no workspace, and launch two kernels fewer than the _with_cover forms (the list builder and the memset of
- * its counter; 0.02 ms of the 2.3 ms bench step).  The words in front are a plain cover: the buffer may be handed to every
- * function that takes `cover`.  The list's order is the order in which the forward's tiles finished. */
+/* Cover list (round 6): a buffer of p3d_rasterize_meshes_cover_list_bytes holds the (N, ceil(H/16), ceil(W/16)) words of the
+ * cover as above, an int32 counter (+ 15 spare), then room for one int32 per word.  The wave that sets the first bit of a word
+ * appends the word's index to the list (one atomic per 16 x 16 pixel block that holds a face), so the backward finds its work
+ * without a pass over the cover and without a workspace: two kernels fewer than with a plain cover (the list builder
+ * mesh_backward_areas and the memset of its counter; 0.02 ms of the 2.3 ms bench step).  The words in front are a plain cover:
+ * the buffer may be handed to every function that takes `cover`.  The list's order is the order in which the forward's tiles
+ * finished. */
 size_t p3d_rasterize_meshes_cover_list_bytes(int N, int H, int W);
-int p3d_rasterize_meshes_with_cover_list(const float* face_verts, const int64_t* mesh_to_face_first_idx,
-                                         const int64_t* num_faces_per_mesh, const int64_t* clipped_faces_neighbor_idx, int64_t F,
-                                         int N, int H, int W, float blur_radius, int faces_per_pixel, int bin_size,
-                                         int max_faces_per_bin, int perspective_correct, int clip_barycentric_coords,
-                                         int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary, float* dists,
-                                         int32_t* cover_and_list, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
-int p3d_rasterize_meshes_backward_with_cover_list(const float* face_verts, const int64_t* pix_to_face, const float* grad_zbuf,
-                                                  const float* grad_bary, const float* grad_dists, const int32_t* cover_and_list,
-                                                  int64_t F, int N, int H, int W, int K, int perspective_correct,
-                                                  int clip_barycentric_coords, float* grad_face_verts, p3d_stream_t stream);
-int p3d_rasterize_meshes_backward_verts_with_cover_list(const float* face_verts, const int64_t* faces, const int64_t* pix_to_face,
-                                                        const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
-                                                        const int32_t* cover_and_list, int64_t F, int64_t V, int N, int H, int W,
-                                                        int K, int perspective_correct, int clip_barycentric_coords,
-                                                        float* grad_verts, p3d_stream_t stream);
 
-/* Per-face reciprocals for the backward (round 6; the reference has no counterpart: its backward re-derives them per sample,
- * geometry_utils.cuh:101-161, 365-385).  p3d_gather_face_verts_pre is p3d_gather_face_verts with a thread per face that also writes
- * face_pre (F, 4) f32, 16-byte aligned: 1 / (barycentric area), 1 / |v1 - v0|^2, 1 / |v2 - v0|^2, 1 / |v2 - v1|^2 (-1 where the squared
- * length is <= 1e-8: the degenerate-edge rule).  p3d_rasterize_meshes_backward_verts_pre is
- * p3d_rasterize_meshes_backward_verts_with_cover_list (cover_and_list may be null: then every row is read) reading those instead of
- * forming them per sample; face_pre null: identical to the _with_cover_list form.  face_pre must belong to THESE face_verts. */
+/* flags of p3d_rasterize_meshes_ex */
+#define P3D_RASTER_COVER_LIST 1u     /* `cover` is a cover-list buffer: the forward also writes the list behind the words       */
+#define P3D_RASTER_CUDA_TIE_ORDER 2u /* the replay of the reference's CUDA tie procedure (below)                                 */
+
+/* CUDA tie order (round 4).  The kernels of this library keep the K nearest faces under the total order (depth, face index), as
+ * the reference's CPU and Python implementations do (rasterize_meshes_cpu.cpp:263-288, rasterize_meshes.py); its CUDA kernels keep
+ * an unsorted array and replace "the" farthest entry only by a strictly nearer candidate (RasterizeMeshesFineCudaKernel /
+ * CheckPixelInsideFace, rasterize_meshes.cu:112-237): the same depths, but among faces of exactly the K-th depth possibly other
+ * survivors, depending on array positions, i.e. on the pixel's whole history (2 in 10^4 entries of the bench launch; zbuf is
+ * bit-equal either way).  With P3D_RASTER_CUDA_TIE_ORDER the fine kernel marks the pixels in which the two procedures can differ
+ * (an entry dropped at the depth of the last survivor while a nearer survivor has a larger face index; or the clipped-face
+ * neighbour rule in play: 2 in 10^3 pixels of the bench launch) and a replay re-runs the reference's procedure, faces in
+ * ascending index, for those: pix_to_face (and the rows that go with it) become what the reference's CUDA kernels return.  1.2 x
+ * the time of p3d_rasterize_meshes on the bench batch (round 4: ~10 x).  The marks take the LAST N * ceil(H/8) * ceil(W/8) * 8
+ * bytes (rounded up to 256) of the workspace when it is at least that much larger than the binning needs
+ * (p3d_rasterize_meshes_workspace_bytes counts them in; a caller of the short-workspace size adds them); without that room the
+ * replay finds the marks in the output itself (one pix_to_face entry of every pixel is read).  Diagnostic: with
+ * P3D_TIE_SKIP_REPLAY set in the environment the replay is skipped and the marks (-2) stay in pix_to_face
+ * (profiles/tie_order_timing.py --count-marks). */
+
+/* p3d_rasterize_meshes + the row cover of its output.  cover: p3d_rasterize_meshes_cover_bytes, or with P3D_RASTER_COVER_LIST a
+ * p3d_rasterize_meshes_cover_list_bytes buffer; null: no cover (flags may then not hold P3D_RASTER_COVER_LIST).  Unknown bits,
+ * or P3D_RASTER_CUDA_TIE_ORDER together with P3D_RASTER_COVER_LIST (a combination no caller reaches): P3D_ERR_INVALID_ARG.
+ * Short workspaces are accepted (above). */
+int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh_to_face_first_idx, const int64_t* num_faces_per_mesh,
+                            const int64_t* clipped_faces_neighbor_idx, int64_t F, int N, int H, int W, float blur_radius,
+                            int faces_per_pixel, int bin_size, int max_faces_per_bin, int perspective_correct,
+                            int clip_barycentric_coords, int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary,
+                            float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
+                            p3d_stream_t stream);
+
+/* Per-face records (round 6; the reference has no counterpart: its backward re-derives them per sample, geometry_utils.cuh:
+ * 101-161, 365-385): face_pre (F, 4) f32, 16-byte aligned: 1 / (barycentric area), 1 / |v1 - v0|^2, 1 / |v2 - v0|^2,
+ * 1 / |v2 - v1|^2 (-1 where the squared length is <= 1e-8: the degenerate-edge rule).  p3d_gather_face_verts_pre is
+ * p3d_gather_face_verts with a thread per face that also writes them.  They belong to THOSE face_verts. */
 int p3d_gather_face_verts_pre(const float* verts, const int64_t* faces, int64_t V, int64_t F, float* face_verts, float* face_pre,
                               p3d_stream_t stream);
-int p3d_rasterize_meshes_backward_verts_pre(const float* face_verts, const float* face_pre, const int64_t* faces,
-                                            const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary,
-                                            const float* grad_dists, const int32_t* cover_and_list, int64_t F, int64_t V, int N, int H,
-                                            int W, int K, int perspective_correct, int clip_barycentric_coords, float* grad_verts,
-                                            p3d_stream_t stream);
 
-/* The same for callers that arrive with face_verts already made (the reference's own signature, `_C.rasterize_meshes_backward`):
- * p3d_rasterize_meshes_backward_with_cover / _with_cover_list (cover null: every row is read; cover_has_list != 0: the list behind the
- * cover is taken and the workspace ignored) that first writes the per-face reciprocals into face_pre_scratch (F x 4 f32, 16-byte aligned;
- * null: the per-sample form) with one small launch. */
-int p3d_rasterize_meshes_backward_pre(const float* face_verts, const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary,
-                                      const float* grad_dists, const int32_t* cover, int cover_has_list, int64_t F, int N, int H, int W,
-                                      int K, int perspective_correct, int clip_barycentric_coords, float* grad_face_verts,
-                                      float* face_pre_scratch, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
-
-/* CUDA tie order -- p3d_rasterize_meshes_with_cover, then a replay that makes pix_to_face (and the rows that go with it) what
- * the reference's CUDA kernels return where faces tie EXACTLY in depth at a pixel's K-th place.  The kernels of this library keep
- * the K nearest under the total order (depth, face index), as the reference's CPU and Python implementations do
- * (rasterize_meshes_cpu.cpp:263-288, rasterize_meshes.py); its CUDA kernels keep an unsorted array and replace "the" farthest entry
- * only by a strictly nearer candidate (RasterizeMeshesFineCudaKernel / CheckPixelInsideFace, rasterize_meshes.cu:112-237): the
- * same depths, but among faces of exactly the K-th depth possibly other survivors, depending on array positions, i.e. on the
- * pixel's whole history (2 in 10^4 entries of the bench launch; zbuf is bit-equal either way).  The fine kernel marks the
- * pixels in which the two procedures can differ (an entry dropped at the depth of the last survivor while a nearer survivor has
- * a larger face index; or the clipped-face neighbour rule in play: 2 in 10^3 pixels of the bench launch) and the replay re-runs
- * the reference's procedure, faces in ascending index, for those: 1.2 x the time of p3d_rasterize_meshes on the bench batch
- * (round 4: ~10 x).  The marks take the LAST N * ceil(H/8) * ceil(W/8) * 8 bytes (rounded up to 256) of the workspace when it
- * is at least that much larger than the binning needs (p3d_rasterize_meshes_workspace_bytes counts them in; a caller of the
- * short-workspace size adds them); without that room the replay finds the marks in the output itself (one pix_to_face entry of
- * every pixel is read).  Diagnostic: with P3D_TIE_SKIP_REPLAY set in the environment the replay is skipped and the marks (-2)
- * stay in pix_to_face (profiles/tie_order_timing.py --count-marks). */
-int p3d_rasterize_meshes_cuda_order(const float* face_verts, const int64_t* mesh_to_face_first_idx,
-                                    const int64_t* num_faces_per_mesh, const int64_t* clipped_faces_neighbor_idx, int64_t F,
-                                    int N, int H, int W, float blur_radius, int faces_per_pixel, int bin_size,
-                                    int max_faces_per_bin, int perspective_correct, int clip_barycentric_coords,
-                                    int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary, float* dists,
-                                    int32_t* cover, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
-
-/* the two backward entry points with the cover of THAT pix_to_face (null: all rows are read).  workspace (optional, may be
- * null; p3d_rasterize_meshes_backward_workspace_bytes): room for the list of covered 16 x 16 areas, so that the launch holds
- * only workgroups with work -- workgroups reach the CUs round robin, and a mix of empty and full ones leaves CUs idle. */
+/* Scratch of a backward with a plain cover: room for the list of covered 16 x 16 areas (built by mesh_backward_areas), so
+ * that the launch holds only workgroups with work -- workgroups reach the CUs round robin, and a mix of empty and full ones
+ * leaves CUs idle.  Without it (workspace null or smaller) the launch spans every area. */
 size_t p3d_rasterize_meshes_backward_workspace_bytes(int N, int H, int W);
-int p3d_rasterize_meshes_backward_with_cover(const float* face_verts, const int64_t* pix_to_face, const float* grad_zbuf,
-                                             const float* grad_bary, const float* grad_dists, const int32_t* cover, int64_t F,
-                                             int N, int H, int W, int K, int perspective_correct,
-                                             int clip_barycentric_coords, float* grad_face_verts, void* workspace,
-                                             size_t workspace_bytes, p3d_stream_t stream);
-int p3d_rasterize_meshes_backward_verts_with_cover(const float* face_verts, const int64_t* faces, const int64_t* pix_to_face,
-                                                   const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
-                                                   const int32_t* cover, int64_t F, int64_t V, int N, int H, int W, int K,
-                                                   int perspective_correct, int clip_barycentric_coords, float* grad_verts,
-                                                   void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+
+/* flags of p3d_rasterize_meshes_backward_ex */
+#define P3D_BWD_COVER_HAS_LIST 1u /* `cover` is the front of a cover-list buffer: take the list, ignore the workspace            */
+#define P3D_BWD_MAKE_FACE_PRE 2u  /* face_pre is scratch (F x 4 f32) that this call fills first with one small launch            */
+
+/* The backward of p3d_rasterize_meshes[_ex].  faces null: grad_out is grad_face_verts (F,3,3).  faces (F,3) i64: grad_out is the
+ * gradient of `face_verts = verts_packed[faces_packed]` (rasterize_meshes.py:146, torch indexing + its index_put backward)
+ * fused in, grad_verts (V,3): the per-face partials are flushed straight to the vertices -- no (F,3,3) intermediate, no
+ * separate scatter.  grad_out is zeroed and accumulated here.
+ * cover: the cover of THAT pix_to_face, or null (every row is read).
+ * face_pre: per-face records (above), or null (formed per sample).  Without P3D_BWD_MAKE_FACE_PRE they are read as
+ * p3d_gather_face_verts_pre wrote them.  Records are used by the launches with perspective_correct && clip_barycentric_coords
+ * && K in {4, 8} only (P3D_BWD_MAKE_FACE_PRE launches nothing otherwise).
+ * Unknown flag bits or a face_pre that is not 16-byte aligned: P3D_ERR_INVALID_ARG. */
+int p3d_rasterize_meshes_backward_ex(const float* face_verts, const int64_t* faces, float* face_pre,
+                                     const int64_t* pix_to_face, const float* grad_zbuf, const float* grad_bary,
+                                     const float* grad_dists, const int32_t* cover, int64_t F, int64_t V, int N, int H, int W,
+                                     int K, int perspective_correct, int clip_barycentric_coords, unsigned flags,
+                                     float* grad_out, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
 /* ---- packed vertices <-> per-face vertices (optional fast path of the L2 function) ------ */
 
@@ -259,7 +233,7 @@ int p3d_transform_gather_face_verts(const float* verts_world, const int64_t* fac
 int p3d_transform_verts_forward(const float* verts_world, const int64_t* mesh_to_vert_first_idx, const float* matrices,
                                 int64_t V, int N, int num_matrices, float* verts_ndc, p3d_stream_t stream);
 /* ... and its backward: grad_verts_world (V,3) = J^T grad_verts_ndc (V,3), i.e. what torch autograd computes through the
- * two transform_points calls; applied to the output of p3d_rasterize_meshes_backward_verts it gives the gradient of the
+ * two transform_points calls; applied to the grad_verts of p3d_rasterize_meshes_backward_ex it gives the gradient of the
  * rasterization wrt world-space vertices. */
 int p3d_transform_verts_backward(const float* verts_world, const int64_t* mesh_to_vert_first_idx, const float* matrices,
                                  const float* grad_verts_ndc, int64_t V, int N, int num_matrices, float* grad_verts_world,
@@ -283,7 +257,7 @@ int p3d_rasterize_points(const float* points, const int64_t* cloud_to_packed_fir
                          int points_per_pixel, int bin_size, int max_points_per_bin, int32_t* idxs, float* zbuf,
                          float* dists, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
-/* p3d_rasterize_points, then the CUDA tie order (see p3d_rasterize_meshes_cuda_order): the reference's point kernels keep the same
+/* p3d_rasterize_points, then the CUDA tie order (see P3D_RASTER_CUDA_TIE_ORDER): the reference's point kernels keep the same
  * unsorted array (rasterize_points.cu:38-84) and sort it by depth ALONE (rasterize_points.cu:26-28, stable): where points tie
  * exactly in depth, the survivors at the K-th place and the order of the tied entries follow the array positions.  The replay
  * re-runs that procedure, points in ascending index, for every pixel whose K slots are full. */

@@ -4,7 +4,7 @@
     python profiles/exp_measure.py [--iters 40] [--batch 64] name=path/to/libp3d_<name>.so ...
 
 Every variant library is opened with ctypes next to the product library and driven through the C ABI directly
-(p3d_rasterize_meshes, p3d_rasterize_meshes_backward_verts) on the same device buffers; per variant:
+(p3d_rasterize_meshes_ex, p3d_rasterize_meshes_backward_ex) on the same device buffers; per variant:
   * per-kernel milliseconds from the library's own HIP-event profiler (p3d_profile_*: events on the launch stream);
   * forward parity against the PRODUCT library's outputs: pix_to_face equal, zbuf / bary / dists bit-equal (the product
     library is what the whole GPU test-suite pins to the oracle and the reference's device code);
@@ -29,7 +29,7 @@ def open_lib(path):
     from pytorch3d_amd import _lib
 
     lib = ctypes.CDLL(path)
-    for name in ("p3d_rasterize_meshes_workspace_bytes", "p3d_rasterize_meshes_with_cover", "p3d_rasterize_meshes_backward_verts_with_cover",
+    for name in ("p3d_rasterize_meshes_workspace_bytes", "p3d_rasterize_meshes_ex", "p3d_rasterize_meshes_backward_ex",
                  "p3d_rasterize_meshes_backward_workspace_bytes",
                  "p3d_profile_enable", "p3d_profile_collect", "p3d_profile_num_entries", "p3d_profile_entry", "p3d_profile_reset"):
         res, args = _lib._SIGNATURES[name]
@@ -97,13 +97,13 @@ def main():
 
     def run(lib, out, gv, ws):
         # what the L2 mirror (and bench.py) runs: the forward writes the row cover, the backward walks it
-        rc = lib.p3d_rasterize_meshes_with_cover(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K,
+        rc = lib.p3d_rasterize_meshes_ex(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K,
                                                  bin_size, M, 1, 1, 0, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
-                                                 out[3].data_ptr(), cover.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+                                                 out[3].data_ptr(), cover.data_ptr(), 0, ws.data_ptr(), ws.numel(), stream)
         assert rc == 0, rc
-        rc = lib.p3d_rasterize_meshes_backward_verts_with_cover(fv.data_ptr(), fp.data_ptr(), out[0].data_ptr(), gz.data_ptr(),
-                                                                gb.data_ptr(), gd.data_ptr(), cover.data_ptr(), F, V, B, H, H, K, 1, 1,
-                                                                gv.data_ptr(), bws.data_ptr(), bws.numel(), stream)
+        rc = lib.p3d_rasterize_meshes_backward_ex(fv.data_ptr(), fp.data_ptr(), None, out[0].data_ptr(), gz.data_ptr(), gb.data_ptr(),
+                                                  gd.data_ptr(), cover.data_ptr(), F, V, B, H, H, K, 1, 1, 0, gv.data_ptr(), bws.data_ptr(),
+                                                  bws.numel(), stream)
         assert rc == 0, rc
 
     product = _lib.load()

@@ -79,8 +79,8 @@ def main():
     }
 
     def run(ptrs):
-        rc = lib.p3d_rasterize_meshes_with_cover(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K, bin_size,
-                                                 M, 1, 1, 0, ptrs[0], ptrs[1], ptrs[2], ptrs[3], cover.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        rc = lib.p3d_rasterize_meshes_ex(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K, bin_size,
+                                                 M, 1, 1, 0, ptrs[0], ptrs[1], ptrs[2], ptrs[3], cover.data_ptr(), 0, ws.data_ptr(), ws.numel(), stream)
         assert rc == 0, rc
 
     for _ in range(60):  # clocks
@@ -124,8 +124,8 @@ def main():
                 ptrs.append(o.data_ptr() + off)
                 off += sz
             def go():
-                rc = lib.p3d_rasterize_meshes_with_cover(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K,
-                                                         bin_size, M, 1, 1, 0, ptrs[0], ptrs[1], ptrs[2], ptrs[3], c.data_ptr(), w.data_ptr(),
+                rc = lib.p3d_rasterize_meshes_ex(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K,
+                                                         bin_size, M, 1, 1, 0, ptrs[0], ptrs[1], ptrs[2], ptrs[3], c.data_ptr(), 0, w.data_ptr(),
                                                          w.numel(), stream)
                 assert rc == 0, rc
             for _ in range(3):
@@ -145,8 +145,8 @@ def main():
             ptrs.append(o.data_ptr() + off)
             off += sz
         def go():
-            rc = lib.p3d_rasterize_meshes_with_cover(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K,
-                                                     bin_size, M, 1, 1, 0, ptrs[0], ptrs[1], ptrs[2], ptrs[3], c.data_ptr(), w.data_ptr(),
+            rc = lib.p3d_rasterize_meshes_ex(fv.data_ptr(), first.data_ptr(), count.data_ptr(), nbr.data_ptr(), F, B, H, H, blur, K,
+                                                     bin_size, M, 1, 1, 0, ptrs[0], ptrs[1], ptrs[2], ptrs[3], c.data_ptr(), 0, w.data_ptr(),
                                                      w.numel(), stream)
             assert rc == 0, rc
         for _ in range(3):

@@ -198,7 +198,7 @@ def _mesh_workspace(lib, F, N, H, W, bin_size, M, dev, what="meshes", extra=0):
 # ----------------------------------------------------------------------------------------------
 # meshes
 # ----------------------------------------------------------------------------------------------
-# CUDA tie order (include/p3d_amd.h: p3d_rasterize_meshes_cuda_order).  False: the K nearest faces of a pixel under the total
+# CUDA tie order (include/p3d_amd.h: P3D_RASTER_CUDA_TIE_ORDER).  False: the K nearest faces of a pixel under the total
 # order (depth, face index), as the reference's CPU and Python implementations return them.  True: where faces tie EXACTLY in
 # depth at the K-th place, the survivors the reference's CUDA kernels keep (bit-identical pix_to_face to a CUDA render; the fine
 # kernel marks the pixels concerned and a replay kernel rewrites those: profiles/tie_order_timing.py).  rasterize_points obeys it too (there the reference's CUDA kernels also ORDER tied
@@ -224,7 +224,7 @@ def rasterize_meshes(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, cli
                      clip_barycentric_coords, cull_backfaces):
     """RasterizeMeshes, rasterize_meshes.h:513-562.  Returns (pix_to_face, zbuf, bary, dists).
 
-    The row cover of the output (include/p3d_amd.h: p3d_rasterize_meshes_with_cover) is written as well and remembered for the
+    The row cover of the output (include/p3d_amd.h: p3d_rasterize_meshes_ex) is written as well and remembered for the
     pix_to_face tensor returned here (_remember_cover): the reference's autograd node hands that very tensor to
     `rasterize_meshes_backward` (renderer/mesh/rasterize_meshes.py:312-357), which then walks only the rows that hold a face --
     the operator signatures stay the reference's."""
@@ -251,10 +251,12 @@ def rasterize_meshes(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, cli
 # `forget_cover(pix_to_face)` after such a write; RECALL_COVERS = False (P3D_RECALL_COVERS=0) switches the recall off (+0.5 ms on
 # the bench batch).  Pinned by tests/test_gpu_cover.py.
 RECALL_COVERS = os.environ.get("P3D_RECALL_COVERS", "1") not in ("", "0")
-# the forward appends the non-empty words of its cover to a list behind it (p3d_rasterize_meshes_with_cover_list); 0: the plain cover,
-# the backward builds the list itself (mesh_backward_areas)
+# the forward appends the non-empty words of its cover to a list behind it (include/p3d_amd.h: P3D_RASTER_COVER_LIST); 0: the plain
+# cover, the backward builds the list itself (mesh_backward_areas)
 COVER_LIST = os.environ.get("P3D_COVER_LIST", "1") not in ("", "0")
-# the backward of perspective + clip launches with K = 4 / 8 reads per-face reciprocals (include/p3d_amd.h: p3d_rasterize_meshes_backward_pre)
+# the backward of perspective + clip launches with K = 4 / 8 reads per-face records (include/p3d_amd.h: p3d_gather_face_verts_pre):
+# written by the fused vertex node's gather (pytorch3d_amd/rasterize_meshes.py), made in the call for rasterize_meshes_backward.
+# 0: formed per sample.  Read at call time, by both.
 FACE_PRE = os.environ.get("P3D_FACE_PRE", "1") not in ("", "0")
 CHECK_COVERS = os.environ.get("P3D_CHECK", "0") not in ("", "0")
 COVER_RECALLS = [0, 0]  # backward calls without an explicit cover: [found the forward's, found none] (read by tests / profiles)
@@ -319,7 +321,7 @@ def _recall_cover(p2f):
 def _rasterize_meshes_covered(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size,
                               blur_radius, faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct,
                               clip_barycentric_coords, cull_backfaces, want_cover=True):
-    """rasterize_meshes + the row cover of its output (include/p3d_amd.h: p3d_rasterize_meshes_with_cover) for the autograd
+    """rasterize_meshes + the row cover of its output (include/p3d_amd.h: p3d_rasterize_meshes_ex) for the autograd
     nodes of this package: ((pix_to_face, zbuf, bary, dists), cover or None)."""
     dev = _same_device(("face_verts", face_verts), ("mesh_to_face_first_idx", mesh_to_face_first_idx),
                        ("num_faces_per_mesh", num_faces_per_mesh),
@@ -349,23 +351,21 @@ def _rasterize_meshes_covered(face_verts, mesh_to_face_first_idx, num_faces_per_
         # without it the replay finds its pixels by reading a pix_to_face entry of every pixel)
         marks = N * ((H + 7) // 8) * ((W + 7) // 8) * 8 + 1024 if CUDA_TIE_ORDER else 0
         ws, need, need_at, entries = _mesh_workspace(lib, F, N, H, W, bin_size, M, dev, extra=marks) if binned else (_workspace(marks, dev), None, 0, None)
-        cover = None
+        cover, flags = None, _lib.RASTER_CUDA_TIE_ORDER if CUDA_TIE_ORDER else 0
         if want_cover and not CUDA_TIE_ORDER and COVER_LIST:
-            # the cover with the list of its non-empty words behind it (include/p3d_amd.h: p3d_rasterize_meshes_with_cover_list): what is
-            # handed on is the (N, CY, CX) view of the buffer's first words -- a plain cover to everybody; the backward wrappers of this
-            # package see the room behind it (cover_has_list) and take the list
+            # the cover with the list of its non-empty words behind it (include/p3d_amd.h: P3D_RASTER_COVER_LIST): what is handed on
+            # is the (N, CY, CX) view of the buffer's first words -- a plain cover to everybody; the backward of this package sees
+            # the room behind it (cover_has_list) and takes the list
             words = N * ((H + 15) // 16) * ((W + 15) // 16)
             buf = torch.empty((lib.p3d_rasterize_meshes_cover_list_bytes(N, H, W) // 4,), dtype=torch.int32, device=dev)
             cover = buf[:words].view(N, (H + 15) // 16, (W + 15) // 16)
+            flags |= _lib.RASTER_COVER_LIST
         elif want_cover:
             cover = torch.empty((N, (H + 15) // 16, (W + 15) // 16), dtype=torch.int32, device=dev)
-        entry = lib.p3d_rasterize_meshes_cuda_order if CUDA_TIE_ORDER else (lib.p3d_rasterize_meshes_with_cover_list if (want_cover and COVER_LIST)
-                                                                            else lib.p3d_rasterize_meshes_with_cover)
-        rc = entry(
+        rc = lib.p3d_rasterize_meshes_ex(
             _ptr(fv), _ptr(first), _ptr(count), _ptr(nb), F, N, H, W, float(blur_radius), K, bin_size if binned else 0,
             M if binned else 0, int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), int(bool(cull_backfaces)),
-            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(cover) if want_cover else None, _ptr(ws), ws.numel(),
-            _stream(dev))
+            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(cover), flags, _ptr(ws), ws.numel(), _stream(dev))
         _lib.check(rc, "rasterize_meshes")
         if need is not None:
             need.report_later(ws, need_at, entries)
@@ -461,46 +461,74 @@ def backward_workspace(cover, N, H, W, dev):
     return _workspace(n, dev)
 
 
+def _refuse_when_deterministic():
+    """The backward scatters with float atomics, like the reference's (rasterize_meshes.cu:587 alertNotDeterministic)."""
+    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
+        raise RuntimeError("RasterizeMeshesBackwardCuda does not have a deterministic implementation")
+
+
+# The one call into p3d_rasterize_meshes_backward_ex, for rasterize_meshes_backward below and the autograd nodes of
+# pytorch3d_amd/rasterize_meshes.py.  Which kernels a backward launches depends on the caller and the switches as follows:
+#
+#   caller                               face_pre                                          cover
+#   rasterize_meshes_backward,           made in the call (BWD_MAKE_FACE_PRE) iff          the list if cover_has_list; else the
+#   _RasterizeFaceVerts (faces None)     FACE_PRE and persp and clip and K in (4, 8)       workspace + mesh_backward_areas if a
+#                                                                                          cover; else every row
+#   _RasterizeMeshVerts                  the gather's records iff they exist and (the      the same
+#                                        cover has a list or there is no cover)
+#   _RasterizeMeshWorld                  never                                             the same
+#
+# QUIRK, kept on purpose: _RasterizeMeshVerts with a cover WITHOUT a list (COVER_LIST off, or CUDA_TIE_ORDER) forms the
+# reciprocals per sample although it has the records -- the entry point that took the records had no workspace argument.
+# Dropping the clause changes results on degenerate edges (ADVICE round 6 item 1): a fix of its own.
+def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad_dists, perspective_correct, clip_barycentric_coords,
+                   cover, face_pre=None):
+    """grad_face_verts (F,3,3) when faces is None, else grad_verts (V,3) through faces (F,3).  Missing grads count as zeros;
+    cover: the row cover of THIS pix_to_face or None; face_pre: the records of p3d_gather_face_verts_pre (faces given) or None."""
+    _refuse_when_deterministic()
+    dev = pix_to_face.device
+    zeros = lambda *tail: torch.zeros(tuple(pix_to_face.shape) + tail, dtype=torch.float32, device=dev)
+    gz = _c(grad_zbuf, torch.float32) if grad_zbuf is not None else zeros()
+    gb = _c(grad_bary, torch.float32) if grad_bary is not None else zeros(3)
+    gd = _c(grad_dists, torch.float32) if grad_dists is not None else zeros()
+    fv, p2f = _c(face_verts, torch.float32), _c(pix_to_face, torch.int64)
+    N, H, W, K = p2f.shape
+    F = fv.size(0)
+    persp, clip = int(bool(perspective_correct)), int(bool(clip_barycentric_coords))
+    has_list = cover_has_list(cover, N, H, W)
+    flags = _lib.BWD_COVER_HAS_LIST if has_list else 0
+    with torch.cuda.device(dev):
+        if faces is None:
+            out = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+            if FACE_PRE and persp and clip and K in (4, 8):
+                face_pre = torch.empty((F, 4), dtype=torch.float32, device=dev)  # scratch the call fills first (one small launch)
+                flags |= _lib.BWD_MAKE_FACE_PRE
+        else:
+            faces = _c(faces, torch.int64)
+            # (zeros: with F == 0 nothing is called -- a null faces pointer would ask for the per-face form)
+            out = (torch.empty if F else torch.zeros)((V, 3), dtype=torch.float32, device=dev)
+            if not (has_list or cover is None):
+                face_pre = None  # the QUIRK above
+        if F == 0:
+            return out
+        ws = backward_workspace(cover, N, H, W, dev)
+        rc = _lib.load().p3d_rasterize_meshes_backward_ex(
+            _ptr(fv), _ptr(faces), _ptr(face_pre), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), cover_ptr(cover, N, H, W), F, V, N, H, W,
+            K, persp, clip, flags, _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+        _lib.check(rc, "rasterize_meshes_backward")
+    return out
+
+
 def rasterize_meshes_backward(face_verts, pix_to_face, grad_zbuf, grad_bary, grad_dists, perspective_correct,
                               clip_barycentric_coords, _cover=None):
     """RasterizeMeshesBackward, rasterize_meshes.h:211-252.  Returns grad_face_verts (F,3,3).
     _cover (not part of the reference's signature): the row cover of THIS pix_to_face from _rasterize_meshes_covered."""
-    dev = _same_device(("face_verts", face_verts), ("pix_to_face", pix_to_face), ("grad_zbuf", grad_zbuf),
-                       ("grad_bary", grad_bary), ("grad_dists", grad_dists))
-    # float atomics: the accumulation order is not deterministic (rasterize_meshes.cu:587)
-    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
-        raise RuntimeError("RasterizeMeshesBackwardCuda does not have a deterministic implementation")
-    fv = _c(face_verts, torch.float32)
+    _same_device(("face_verts", face_verts), ("pix_to_face", pix_to_face), ("grad_zbuf", grad_zbuf), ("grad_bary", grad_bary),
+                 ("grad_dists", grad_dists))
     if _cover is None:
         _cover = _recall_cover(pix_to_face)  # the forward of this very tensor left its row cover (see rasterize_meshes)
-    p2f = _c(pix_to_face, torch.int64)
-    gz, gb, gd = _c(grad_zbuf, torch.float32), _c(grad_bary, torch.float32), _c(grad_dists, torch.float32)
-    N, H, W, K = p2f.shape
-    F = fv.size(0)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
-        if F == 0:
-            return out
-        if FACE_PRE and perspective_correct and clip_barycentric_coords and K in (4, 8):
-            # the per-face reciprocals first (one small launch into a scratch tensor), then the kernel that gathers them per sample
-            has_list = cover_has_list(_cover, N, H, W)
-            ws = _workspace(0, dev) if has_list else backward_workspace(_cover, N, H, W, dev)
-            pre = torch.empty((F, 4), dtype=torch.float32, device=dev)
-            rc = lib.p3d_rasterize_meshes_backward_pre(
-                _ptr(fv), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), cover_ptr(_cover, N, H, W), int(has_list), F, N, H, W, K, 1, 1,
-                _ptr(out), _ptr(pre), _ptr(ws), ws.numel(), _stream(dev))
-        elif cover_has_list(_cover, N, H, W):
-            rc = lib.p3d_rasterize_meshes_backward_with_cover_list(
-                _ptr(fv), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), cover_ptr(_cover, N, H, W), F, N, H, W, K,
-                int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), _ptr(out), _stream(dev))
-        else:
-            ws = backward_workspace(_cover, N, H, W, dev)
-            rc = lib.p3d_rasterize_meshes_backward_with_cover(
-                _ptr(fv), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), cover_ptr(_cover, N, H, W), F, N, H, W, K,
-                int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "rasterize_meshes_backward")
-    return out
+    return _mesh_backward(face_verts, None, 0, pix_to_face, grad_zbuf, grad_bary, grad_dists, perspective_correct,
+                          clip_barycentric_coords, _cover)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -13,9 +13,18 @@ LIB_PATH = os.environ.get("P3D_LIB_PATH") or os.path.join(_HERE, "libp3d_amd.so"
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
+c_uint = ctypes.c_uint
 c_f32 = ctypes.c_float
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
+
+ABI_VERSION = 2  # P3D_ABI_VERSION of include/p3d_amd.h
+
+# flags of p3d_rasterize_meshes_ex / p3d_rasterize_meshes_backward_ex (include/p3d_amd.h)
+RASTER_COVER_LIST = 1
+RASTER_CUDA_TIE_ORDER = 2
+BWD_COVER_HAS_LIST = 1
+BWD_MAKE_FACE_PRE = 2
 
 _SIGNATURES = {
     # name: (restype, [argtypes])
@@ -36,36 +45,16 @@ _SIGNATURES = {
                                           c_ptr]),
     "p3d_rasterize_meshes_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int,
                                               c_int, c_int, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_backward_verts": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int,
-                                                    c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
     "p3d_rasterize_meshes_cover_bytes": (c_size, [c_int, c_int, c_int]),
     "p3d_rasterize_meshes_cover_check": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_with_cover": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int,
-                                                c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,
-                                                c_ptr]),
     "p3d_rasterize_meshes_cover_list_bytes": (c_size, [c_int, c_int, c_int]),
-    "p3d_rasterize_meshes_with_cover_list": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int,
-                                                     c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,
-                                                     c_ptr]),
-    "p3d_rasterize_meshes_backward_with_cover_list": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int,
-                                                              c_int, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_backward_verts_with_cover_list": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64,
-                                                                    c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_cuda_order": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int,
-                                                c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,
-                                                c_ptr]),
+    "p3d_rasterize_meshes_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int, c_int, c_int,
+                                        c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_uint, c_ptr, c_size, c_ptr]),
     "p3d_rasterize_meshes_backward_workspace_bytes": (c_size, [c_int, c_int, c_int]),
-    "p3d_rasterize_meshes_backward_with_cover": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int,
-                                                         c_int, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_meshes_backward_verts_with_cover": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64,
-                                                               c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_size,
-                                                               c_ptr]),
     "p3d_gather_face_verts": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "p3d_gather_face_verts_pre": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_backward_pre": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_int, c_int, c_int,
-                                                  c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_meshes_backward_verts_pre": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64,
-                                                        c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
+    "p3d_rasterize_meshes_backward_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int,
+                                                 c_int, c_int, c_int, c_int, c_uint, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_scatter_face_grads": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "p3d_transform_gather_face_verts": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
     "p3d_transform_verts_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
@@ -181,12 +170,14 @@ def load():
             lib = ctypes.CDLL(LIB_PATH)
         except OSError as e:  # e.g. libamdhip64 missing
             raise ExtensionMissing(f"cannot load {LIB_PATH}: {e}") from e
+        # the version first: a library of another ABI may lack symbols of this one (or keep removed ones)
+        lib.p3d_abi_version.restype, lib.p3d_abi_version.argtypes = c_int, []
+        if lib.p3d_abi_version() != ABI_VERSION:
+            raise ExtensionMissing(f"{LIB_PATH}: ABI version {lib.p3d_abi_version()} != {ABI_VERSION}; rebuild")
         for name, (res, args) in _SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args
-        if lib.p3d_abi_version() != 1:
-            raise ExtensionMissing(f"{LIB_PATH}: ABI version {lib.p3d_abi_version()} != 1; rebuild")
         _lib = lib
     return _lib
 

@@ -110,7 +110,7 @@ struct BinWorkspace {
 // A caller that has a fallback for the overflow case may therefore carve with list_entries >= 0: the list gets
 // max(list_entries, what is left of the arena) ids, capped at the worst case.  The offsets scan compares the lists' total
 // with the capacity and raises plan_hdr[2]; bin_fill then writes nothing, and the caller's consumers test the flag ON THE
-// DEVICE (raster_mesh.hip: p3d_rasterize_meshes_with_cover launches the binned kernel, which returns at once when the
+// DEVICE (raster_mesh.hip: p3d_rasterize_meshes_ex launches the binned kernel, which returns at once when the
 // flag is up, and the naive kernel, which returns at once when it is not) -- no host sync, exact either way.  offset[rows]
 // holds the total the call needed; a caller reads it back later to size its next workspace.
 int64_t bin_capacity(int64_t E, int N, const BinGeom& g, int M);

@@ -36,6 +36,23 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? P3D_OK : P
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Work items in scattered order: b -> (b * multiplier) mod items is a bijection for an odd multiplier coprime to items; near
+// items / golden ratio it spreads neighbours far apart
+inline unsigned scatter_multiplier(uint64_t items) {
+  if (items <= 1) return 1;
+  auto gcd = [](uint64_t x, uint64_t y) {
+    while (y) {
+      const uint64_t r = x % y;
+      x = y;
+      y = r;
+    }
+    return x;
+  };
+  uint64_t m = (uint64_t)((double)items * 0.6180339887) | 1u;
+  while (gcd(m, items) != 1) m += 2;
+  return (unsigned)(m % items);
+}
+
 // Bump allocator over the caller's workspace.
 struct Arena {
   char* base;

@@ -64,9 +64,9 @@ struct MeshArgs {
   float* zbuf;
   float* bary;
   float* dists;
-  int* cover;  // row cover of the output (include/p3d_amd.h: p3d_rasterize_meshes_with_cover), zeroed by the launcher; or null
+  int* cover;  // row cover of the output (include/p3d_amd.h: p3d_rasterize_meshes_ex), zeroed by the launcher; or null
   int CY, CX;  // its 16 x 16 pixel blocks per image
-  // p3d_rasterize_meshes_with_cover_list: the words of the cover that hold a face, appended by the wave that sets a word's first bit
+  // P3D_RASTER_COVER_LIST: the words of the cover that hold a face, appended by the wave that sets a word's first bit
   // (its atomicOr returns 0): area_count[0] entries of area_list, zeroed with the cover.  Null without.
   int* area_count;
   int* area_list;
@@ -1125,7 +1125,7 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// CUDA tie order (p3d_rasterize_meshes_cuda_order).  The kernels above keep the K nearest faces of a pixel under the total
+// CUDA tie order (P3D_RASTER_CUDA_TIE_ORDER).  The kernels above keep the K nearest faces of a pixel under the total
 // order (z, face index) -- what the reference's CPU and Python implementations return.  Its CUDA kernels return the same
 // depths but, where faces tie EXACTLY in depth at the K-th place, possibly other faces: they keep an unsorted array, replace
 // "the" largest entry only by a strictly nearer candidate, and which of several equally far entries is "the" largest depends
@@ -1526,9 +1526,10 @@ P3D_API size_t p3d_rasterize_meshes_cover_list_bytes(int N, int H, int W) {
   return words == 0 ? 0 : (2 * words + 16) * sizeof(int32_t);  // cover | count + 15 spare | list
 }
 
-// the cover starts empty; the waves that write a pixel with a face set its bit.  with_list: cover is a buffer of
-// p3d_rasterize_meshes_cover_list_bytes -- the counter of the area list behind the words is zeroed in the same memset
-static int cover_begin(MeshArgs* a, int32_t* cover, hipStream_t s, bool with_list = false) {
+// the row cover of a launch (null: none); with_list: cover is a buffer of p3d_rasterize_meshes_cover_list_bytes, the list of its
+// non-empty words behind them.  zero: the cover starts empty -- the waves that write a pixel with a face set its bit -- and the
+// counter of the list is zeroed in the same memset (not for the stand-by launch of a binned one: that one did it)
+static int cover_begin(MeshArgs* a, int32_t* cover, bool with_list, bool zero, hipStream_t s) {
   a->cover = cover;
   a->CY = (a->H + 15) / 16;
   a->CX = (a->W + 15) / 16;
@@ -1540,38 +1541,14 @@ static int cover_begin(MeshArgs* a, int32_t* cover, hipStream_t s, bool with_lis
     a->area_count = cover + bytes / sizeof(int32_t);
     a->area_list = a->area_count + 16;
   }
-  return (bytes == 0 || hipMemsetAsync(cover, 0, bytes + (with_list ? 16 * sizeof(int32_t) : 0), s) == hipSuccess) ? P3D_OK : P3D_ERR_LAUNCH;
+  if (!zero || bytes == 0) return P3D_OK;
+  return hipMemsetAsync(cover, 0, bytes + (with_list ? 16 * sizeof(int32_t) : 0), s) == hipSuccess ? P3D_OK : P3D_ERR_LAUNCH;
 }
 
-// CUDA tie order: where the TIES kernels leave their lane masks (MeshArgs::tie_words), or words == null: marks in place only
-struct TieMarks {
-  unsigned long long* words = nullptr;
-  int SY = 0, SX = 0;
-};
-
-static int mesh_naive_impl(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                           const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K, int persp,
-                           int clip, int cull, int64_t* p2f, float* zbuf, float* bary, float* dists, int32_t* cover,
-                           p3d_stream_t stream, const int* overflow = nullptr, bool ties = false, TieMarks marks = TieMarks(),
-                           bool with_list = false) {
-  (void)F;
-  const int rc = check_common(N, H, W, K);
-  if (rc != P3D_OK) return rc;
-  MeshArgs z{};
-  z.N = N;
-  z.H = H;
-  z.W = W;
-  if (cover != nullptr && overflow == nullptr) {  // (as the fallback of a binned launch: that one zeroed the cover)
-    const int st = cover_begin(&z, cover, (hipStream_t)stream, with_list);  // also for K == 0: nothing is covered
-    if (st != P3D_OK) return st;
-  } else if (cover != nullptr && with_list) {
-    const size_t words = p3d_rasterize_meshes_cover_bytes(N, H, W) / sizeof(int32_t);
-    z.area_count = cover + words;
-    z.area_list = z.area_count + 16;
-  }
-  if ((int64_t)N * H * W * K == 0) return P3D_OK;
-  if ((!face_verts || !neighbor) && F > 0) return P3D_ERR_INVALID_ARG;
-  if (!mesh_first || !mesh_count || !p2f || !zbuf || !bary || !dists) return P3D_ERR_INVALID_ARG;
+// the caller's arguments as every launch of this file takes them; the launchers below add the cover, the bins and the tiles
+static MeshArgs mesh_args(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count, const int64_t* neighbor,
+                          int N, int H, int W, float blur_radius, int K, int persp, int clip, int cull, int64_t* p2f, float* zbuf,
+                          float* bary, float* dists) {
   MeshArgs a{};
   a.face_verts = face_verts;
   a.neighbor = neighbor;
@@ -1590,111 +1567,48 @@ static int mesh_naive_impl(const float* face_verts, const int64_t* mesh_first, c
   a.zbuf = zbuf;
   a.bary = bary;
   a.dists = dists;
-  a.cover = cover;  // zeroed above
-  a.CY = (H + 15) / 16;
-  a.CX = (W + 15) / 16;
-  a.area_count = cover != nullptr ? z.area_count : nullptr;
-  a.area_list = cover != nullptr ? z.area_list : nullptr;
-  a.overflow = overflow;
-  a.ties = ties ? 1 : 0;
-  a.tie_words = marks.words;
-  a.SY = marks.SY;
-  a.SX = marks.SX;
-  set_tiles(&a, H > W ? H : W, 1, 1);
-  return launch_mesh_raster<false>(a, (hipStream_t)stream);
+  return a;
+}
+
+// every tile tests every face of its mesh; a.overflow set: the stand-by of a binned launch (it writes only when the lists did not fit)
+static int mesh_naive_impl(MeshArgs a, int64_t F, int32_t* cover, bool with_list, hipStream_t s) {
+  const int st = cover_begin(&a, cover, with_list, a.overflow == nullptr, s);  // (also for K == 0: nothing is covered)
+  if (st != P3D_OK) return st;
+  if ((int64_t)a.N * a.H * a.W * a.K == 0) return P3D_OK;
+  if ((!a.face_verts || !a.neighbor) && F > 0) return P3D_ERR_INVALID_ARG;
+  if (!a.mesh_first || !a.mesh_count || !a.p2f || !a.zbuf || !a.bary || !a.dists) return P3D_ERR_INVALID_ARG;
+  set_tiles(&a, a.H > a.W ? a.H : a.W, 1, 1);
+  return launch_mesh_raster<false>(a, s);
 }
 
 P3D_API int p3d_rasterize_meshes_naive(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
                                        const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K,
                                        int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary,
                                        float* dists, p3d_stream_t stream) {
-  return mesh_naive_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, persp, clip, cull, p2f,
-                         zbuf, bary, dists, nullptr, stream);
+  const int rc = check_common(N, H, W, K);
+  if (rc != P3D_OK) return rc;
+  return mesh_naive_impl(mesh_args(face_verts, mesh_first, mesh_count, neighbor, N, H, W, blur_radius, K, persp, clip, cull, p2f, zbuf,
+                                   bary, dists),
+                         F, nullptr, false, (hipStream_t)stream);
 }
 
-static int mesh_fine_from_csr(const float* face_verts, const int64_t* neighbor, const BinCSR& csr, int N, int H, int W,
-                              const BinGeom& g, float blur_radius, int K, int persp, int clip, int cull, int64_t* p2f,
-                              float* zbuf, float* bary, float* dists, hipStream_t stream, int32_t* cover = nullptr,
-                              const int* overflow = nullptr, bool ties = false, TieMarks marks = TieMarks(), bool with_list = false) {
-  MeshArgs a{};
-  a.face_verts = face_verts;
-  a.neighbor = neighbor;
+static int mesh_fine_from_csr(MeshArgs a, const BinCSR& csr, const BinGeom& g, int32_t* cover, bool with_list, hipStream_t s) {
   a.csr = csr;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.K = K;
-  a.blur = blur_radius;
-  a.sqrt_blur = sqrtf(blur_radius);
-  a.persp = persp;
-  a.clip = clip;
-  a.cull = cull;
-  a.p2f = p2f;
-  a.zbuf = zbuf;
-  a.bary = bary;
-  a.dists = dists;
-  const int st = cover_begin(&a, cover, stream, with_list);
+  const int st = cover_begin(&a, cover, with_list, true, s);
   if (st != P3D_OK) return st;
-  a.overflow = overflow;
-  a.ties = ties ? 1 : 0;
-  a.tie_words = marks.words;
-  a.SY = marks.SY;
-  a.SX = marks.SX;
   set_tiles(&a, g.bin_size, g.BH, g.BW);
-  return launch_mesh_raster<true>(a, stream);
+  return launch_mesh_raster<true>(a, s);
 }
 
-// b -> (b * multiplier) mod items is a bijection for an odd multiplier coprime to items; near items / golden ratio it spreads
-// neighbours far apart
-static unsigned scatter_multiplier(uint64_t items) {
-  if (items <= 1) return 1;
-  auto gcd = [](uint64_t x, uint64_t y) {
-    while (y) {
-      const uint64_t r = x % y;
-      x = y;
-      y = r;
-    }
-    return x;
-  };
-  uint64_t m = (uint64_t)((double)items * 0.6180339887) | 1u;
-  while (gcd(m, items) != 1) m += 2;
-  return (unsigned)(m % items);
-}
-
-// the replay of p3d_rasterize_meshes_cuda_order over the outputs of the launches before it; csr: the bin lists (null: every
-// face of the pixel's mesh), overflow: the short-workspace flag the launch obeys (or null)
-static int cuda_order_replay(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                             const int64_t* neighbor, const BinCSR* csr, const BinGeom* g, int N, int H, int W, float blur_radius,
-                             int K, int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary, float* dists,
-                             const int* overflow, hipStream_t s, TieMarks marks) {
+// the replay of P3D_RASTER_CUDA_TIE_ORDER over the outputs of the launches before it; csr: the bin lists (null: every face of the
+// pixel's mesh); a.overflow: the short-workspace flag the launch obeys (or null)
+static int cuda_order_replay(MeshArgs a, const BinCSR* csr, const BinGeom* g, hipStream_t s) {
   // diagnostic (profiles/tie_order_timing.py --count-marks): leave the marks in the output instead of replaying them
   static const bool skip = getenv("P3D_TIE_SKIP_REPLAY") != nullptr;
   if (skip) return P3D_OK;
-  MeshArgs a{};
-  a.tie_words = marks.words;
-  a.SY = marks.SY;
-  a.SX = marks.SX;
-  a.face_verts = face_verts;
-  a.neighbor = neighbor;
-  a.mesh_first = mesh_first;
-  a.mesh_count = mesh_count;
-  a.N = N;
-  a.H = H;
-  a.W = W;
-  a.K = K;
-  a.blur = blur_radius;
-  a.sqrt_blur = sqrtf(blur_radius);
-  a.persp = persp;
-  a.clip = clip;
-  a.cull = cull;
-  a.p2f = p2f;
-  a.zbuf = zbuf;
-  a.bary = bary;
-  a.dists = dists;
-  a.overflow = overflow;
   LaunchScope ls("mesh_cuda_order", s);
-  const uint64_t nwords = (uint64_t)N * (uint64_t)marks.SY * (uint64_t)marks.SX;
-  const bool words = marks.words != nullptr && nwords > 0 && nwords < 0xffffffffull;
+  const uint64_t nwords = (uint64_t)a.N * (uint64_t)a.SY * (uint64_t)a.SX;
+  const bool words = a.tie_words != nullptr && nwords > 0 && nwords < 0xffffffffull;
   const unsigned wgrid = (unsigned)ceil_div((int64_t)nwords, kTieWordsPerWave);
   const unsigned mult = words ? scatter_multiplier(nwords) : 1u;
   if (!words) a.tie_words = nullptr;
@@ -1706,7 +1620,7 @@ static int cuda_order_replay(const float* face_verts, const int64_t* mesh_first,
     else
       mesh_cuda_order_kernel<true><<<tile_grid(a.tm), kStage, 0, s>>>(a);
   } else {
-    set_tiles(&a, H > W ? H : W, 1, 1);
+    set_tiles(&a, a.H > a.W ? a.H : a.W, 1, 1);
     if (words)
       mesh_cuda_order_words_kernel<false><<<wgrid, kTieWaves * kWave, 0, s>>>(a, (unsigned)nwords, mult);
     else
@@ -1715,16 +1629,22 @@ static int cuda_order_replay(const float* face_verts, const int64_t* mesh_first,
   return launch_status();
 }
 
-static int raster_meshes_impl(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                              const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K, int bin_size,
-                              int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary,
-                              float* dists, int32_t* cover, void* workspace, size_t workspace_bytes, p3d_stream_t stream,
-                              bool cuda_order, bool with_list = false) {
+P3D_API int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
+                                    const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K, int bin_size,
+                                    int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary,
+                                    float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
+                                    p3d_stream_t stream) {
+  const bool cuda_order = (flags & P3D_RASTER_CUDA_TIE_ORDER) != 0, with_list = (flags & P3D_RASTER_COVER_LIST) != 0;
+  if ((flags & ~(P3D_RASTER_COVER_LIST | P3D_RASTER_CUDA_TIE_ORDER)) != 0 || (cuda_order && with_list) || (with_list && cover == nullptr))
+    return P3D_ERR_INVALID_ARG;
+  const int rc = check_common(N, H, W, K);
+  if (rc != P3D_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const bool any_output = (int64_t)N * H * W * K != 0;
-  // CUDA tie order: the lane masks of the marked pixels live in the LAST bytes of the workspace when it has room for them
-  // (p3d_rasterize_meshes_workspace_bytes counts them in); the binning carves the rest as ever
-  TieMarks marks;
+  MeshArgs a = mesh_args(face_verts, mesh_first, mesh_count, neighbor, N, H, W, blur_radius, K, persp, clip, cull, p2f, zbuf, bary, dists);
+  a.ties = cuda_order ? 1 : 0;
+  // CUDA tie order: the lane masks of the marked pixels (MeshArgs::tie_words) live in the LAST bytes of the workspace when it has
+  // room for them (p3d_rasterize_meshes_workspace_bytes counts them in); the binning carves the rest as ever
   const size_t full_workspace_bytes = workspace_bytes;
   // The words are indexed by (sy0 >> 3, sx0 >> 3) and decoded as pixels (8 sy + L / 8, 8 sx + L % 8): sub-tile origins must be
   // multiples of 8.  They are whenever a bin is a whole number of 8 x 8 sub-tiles -- not with a caller's bin_size of 9..15
@@ -1736,30 +1656,20 @@ static int raster_meshes_impl(const float* face_verts, const int64_t* mesh_first
     if (workspace_bytes >= mb + 256) {
       const size_t at = (workspace_bytes - mb) & ~(size_t)255;
       if (((uintptr_t)workspace & 7u) == 0) {
-        marks.words = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + at);
-        marks.SY = (H + 7) / 8;
-        marks.SX = (W + 7) / 8;
+        a.tie_words = reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + at);
+        a.SY = (H + 7) / 8;
+        a.SX = (W + 7) / 8;
         workspace_bytes = at;
-        if (hipMemsetAsync(marks.words, 0, mb, s) != hipSuccess) return P3D_ERR_LAUNCH;
+        if (hipMemsetAsync(a.tie_words, 0, mb, s) != hipSuccess) return P3D_ERR_LAUNCH;
       }
     }
   }
   if (bin_size <= 0 || max_faces_per_bin <= 0) {
-    const int st = mesh_naive_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, persp, clip, cull,
-                                   p2f, zbuf, bary, dists, cover, stream, nullptr, cuda_order, marks, with_list);
+    const int st = mesh_naive_impl(a, F, cover, with_list, s);
     if (st != P3D_OK || !cuda_order || !any_output) return st;
-    return cuda_order_replay(face_verts, mesh_first, mesh_count, neighbor, nullptr, nullptr, N, H, W, blur_radius, K, persp, clip,
-                             cull, p2f, zbuf, bary, dists, nullptr, s, marks);
+    return cuda_order_replay(a, nullptr, nullptr, s);
   }
-  const int rc = check_common(N, H, W, K);
-  if (rc != P3D_OK) return rc;
-  if (cover != nullptr && !any_output) {
-    MeshArgs z{};
-    z.N = N;
-    z.H = H;
-    z.W = W;
-    return cover_begin(&z, cover, s, with_list);
-  }
+  if (cover != nullptr && !any_output) return cover_begin(&a, cover, with_list, true, s);
   if (!any_output) return P3D_OK;
   if ((!face_verts || !neighbor) && F > 0) return P3D_ERR_INVALID_ARG;
   if (!mesh_first || !mesh_count || !p2f || !zbuf || !bary || !dists) return P3D_ERR_INVALID_ARG;
@@ -1772,57 +1682,25 @@ static int raster_meshes_impl(const float* face_verts, const int64_t* mesh_first
   if (!workspace) return P3D_ERR_WORKSPACE;
   if (!bin_carve(arena, F, N, g, max_faces_per_bin, &ws, /*list_entries=*/1)) {
     // the marks of the CUDA tie order took the room the fixed arrays need: give it back (the replay reads the marks in place)
-    if (marks.words == nullptr) return P3D_ERR_WORKSPACE;
-    marks = TieMarks();
+    if (a.tie_words == nullptr) return P3D_ERR_WORKSPACE;
+    a.tie_words = nullptr;
+    a.SY = a.SX = 0;
     workspace_bytes = full_workspace_bytes;
     arena = Arena(workspace, workspace_bytes);
     if (!bin_carve(arena, F, N, g, max_faces_per_bin, &ws, /*list_entries=*/1)) return P3D_ERR_WORKSPACE;
   }
   const bool is_short = ws.capacity < ws.worst;
-  const int* overflow = is_short ? ws.plan_hdr + 2 : nullptr;
+  a.overflow = is_short ? ws.plan_hdr + 2 : nullptr;
   int st = bin_build(kTriangles, face_verts, nullptr, mesh_first, mesh_count, F, N, g, max_faces_per_bin,
                      sqrtf(blur_radius), ws, s);
   if (st != P3D_OK) return st;
   BinCSR csr{ws.offset, ws.total, ws.list, TilePlan{ws.arank, ws.bg_list, ws.plan_hdr, ws.order}};
-  st = mesh_fine_from_csr(face_verts, neighbor, csr, N, H, W, g, blur_radius, K, persp, clip, cull, p2f, zbuf, bary, dists, s,
-                          cover, overflow, cuda_order, marks, with_list);
-  if (st == P3D_OK && is_short)
-    st = mesh_naive_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, persp, clip, cull, p2f, zbuf,
-                         bary, dists, cover, stream, overflow, cuda_order, marks, with_list);
+  st = mesh_fine_from_csr(a, csr, g, cover, with_list, s);
+  if (st == P3D_OK && is_short) st = mesh_naive_impl(a, F, cover, with_list, s);
   if (st != P3D_OK || !cuda_order) return st;
-  st = cuda_order_replay(face_verts, mesh_first, mesh_count, neighbor, &csr, &g, N, H, W, blur_radius, K, persp, clip, cull, p2f,
-                         zbuf, bary, dists, overflow, s, marks);
+  st = cuda_order_replay(a, &csr, &g, s);
   if (st != P3D_OK || !is_short) return st;
-  return cuda_order_replay(face_verts, mesh_first, mesh_count, neighbor, nullptr, nullptr, N, H, W, blur_radius, K, persp, clip,
-                           cull, p2f, zbuf, bary, dists, overflow, s, marks);
-}
-
-P3D_API int p3d_rasterize_meshes_with_cover(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                                            const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius,
-                                            int K, int bin_size, int max_faces_per_bin, int persp, int clip, int cull,
-                                            int64_t* p2f, float* zbuf, float* bary, float* dists, int32_t* cover,
-                                            void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
-  return raster_meshes_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size, max_faces_per_bin,
-                            persp, clip, cull, p2f, zbuf, bary, dists, cover, workspace, workspace_bytes, stream, false);
-}
-
-P3D_API int p3d_rasterize_meshes_with_cover_list(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                                                 const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius,
-                                                 int K, int bin_size, int max_faces_per_bin, int persp, int clip, int cull,
-                                                 int64_t* p2f, float* zbuf, float* bary, float* dists, int32_t* cover_and_list,
-                                                 void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
-  return raster_meshes_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size, max_faces_per_bin,
-                            persp, clip, cull, p2f, zbuf, bary, dists, cover_and_list, workspace, workspace_bytes, stream, false,
-                            cover_and_list != nullptr);
-}
-
-P3D_API int p3d_rasterize_meshes_cuda_order(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                                            const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius,
-                                            int K, int bin_size, int max_faces_per_bin, int persp, int clip, int cull,
-                                            int64_t* p2f, float* zbuf, float* bary, float* dists, int32_t* cover,
-                                            void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
-  return raster_meshes_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size, max_faces_per_bin,
-                            persp, clip, cull, p2f, zbuf, bary, dists, cover, workspace, workspace_bytes, stream, true);
+  return cuda_order_replay(a, nullptr, nullptr, s);
 }
 
 P3D_API int p3d_rasterize_meshes(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
@@ -1830,9 +1708,8 @@ P3D_API int p3d_rasterize_meshes(const float* face_verts, const int64_t* mesh_fi
                                  int bin_size, int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f,
                                  float* zbuf, float* bary, float* dists, void* workspace, size_t workspace_bytes,
                                  p3d_stream_t stream) {
-  return p3d_rasterize_meshes_with_cover(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size,
-                                         max_faces_per_bin, persp, clip, cull, p2f, zbuf, bary, dists, nullptr, workspace,
-                                         workspace_bytes, stream);
+  return p3d_rasterize_meshes_ex(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size, max_faces_per_bin,
+                                 persp, clip, cull, p2f, zbuf, bary, dists, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
 P3D_API int p3d_rasterize_meshes_coarse(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
@@ -1885,6 +1762,7 @@ P3D_API int p3d_rasterize_meshes_fine(const float* face_verts, const int32_t* bi
   g.BW = BW;
   g.nbins = BH * BW;
   BinCSR csr{offset, total, list, TilePlan{nullptr, nullptr, nullptr, nullptr}};
-  return mesh_fine_from_csr(face_verts, neighbor, csr, N, H, W, g, blur_radius, K, persp, clip, cull, p2f, zbuf, bary,
-                            dists, s);
+  return mesh_fine_from_csr(mesh_args(face_verts, nullptr, nullptr, neighbor, N, H, W, blur_radius, K, persp, clip, cull, p2f, zbuf, bary,
+                                      dists),
+                            csr, g, nullptr, false, s);
 }

@@ -58,7 +58,7 @@ struct BwdArgs {
   const int* area_list;       // rows kernel: the 16 x 16 areas that hold a face (area_list_kernel), or null: all of them
   const int* area_count;
   int persp, clip;
-  const int* cover;  // row cover written by the forward (p3d_rasterize_meshes_with_cover) or null; (N, CY, CX) words
+  const int* cover;  // row cover written by the forward (p3d_rasterize_meshes_ex) or null; (N, CY, CX) words
   int CY, CX;
   const float4* face_pre;  // (F) per-face reciprocals (p3d_geom.h: BwdFacePre, written by p3d_gather_face_verts_pre) or null
 };
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void cover_check_kernel(const int64_t* __restr
 }
 
 // The per-face reciprocals (p3d_geom.h: BwdFacePre) from face_verts, a thread per face: what p3d_gather_face_verts_pre writes beside its
-// gather, for callers that arrive with face_verts already made (the reference's own signature: p3d_rasterize_meshes_backward_pre).
+// gather, for callers that arrive with face_verts already made (the reference's own signature: P3D_BWD_MAKE_FACE_PRE).
 __global__ __launch_bounds__(256) void face_pre_kernel(const float* __restrict__ face_verts, int64_t F, float4* __restrict__ face_pre) {
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += (int64_t)gridDim.x * 256) {
     const float* q = face_verts + f * 9;
@@ -521,25 +521,10 @@ using namespace p3d;
 P3D_API size_t p3d_rasterize_meshes_backward_workspace_bytes(int N, int H, int W);
 
 namespace {
-unsigned scatter_multiplier(uint64_t items) {
-  if (items <= 1) return 1;
-  auto gcd = [](uint64_t x, uint64_t y) {
-    while (y) {
-      const uint64_t r = x % y;
-      x = y;
-      y = r;
-    }
-    return x;
-  };
-  uint64_t m = (uint64_t)((double)items * 0.6180339887) | 1u;
-  while (gcd(m, items) != 1) m += 2;
-  return (unsigned)(m % items);
-}
-
 int launch_mesh_backward(const float* face_verts, const int64_t* faces, int64_t V, const int64_t* p2f, const float* grad_zbuf,
                          const float* grad_bary, const float* grad_dists, int N, int H, int W, int K, int persp, int clip,
                          float* grad_out, const int32_t* cover, void* workspace, size_t workspace_bytes, hipStream_t s,
-                         bool cover_has_list = false, const float* face_pre = nullptr) {
+                         bool cover_has_list, const float* face_pre) {
   BwdArgs a;
   a.face_pre = reinterpret_cast<const float4*>(face_pre);
   a.V = V;
@@ -564,15 +549,15 @@ int launch_mesh_backward(const float* face_verts, const int64_t* faces, int64_t 
   a.area_list = nullptr;
   a.area_count = nullptr;
   const bool rows_kernel = K == 4 || K == 8 || K == 16 || K == 32;  // (32: round 4, with the on-chip forward queues for K > 16)
-  // Work items in scattered order: workgroups reach XCDs and CUs round robin by index, and in (image, row, column) order
-  // the index says where in the image the item is -- the CUs that drew the borders ran empty while the ones with the image
-  // centres queued work.  b -> (b * scatter) mod items, odd multiplier near items / golden ratio, coprime: a bijection.
+  // Work items in scattered order (scatter_multiplier): workgroups reach XCDs and CUs round robin by index, and in (image, row,
+  // column) order the index says where in the image the item is -- the CUs that drew the borders ran empty while the ones with
+  // the image centres queued work.
   const int64_t items = rows_kernel ? (int64_t)N * a.CY * a.CX : (int64_t)N * a.RY * a.RX;
   if (items > 0x7fffffffll) return P3D_ERR_INVALID_ARG;
   a.nblocks = (unsigned)items;
   a.scatter = scatter_multiplier((uint64_t)items);
   if (rows_kernel && cover != nullptr && cover_has_list) {
-    // the forward listed the areas itself (p3d_rasterize_meshes_with_cover_list): no pass over the cover, no counter to clear
+    // the forward listed the areas itself (P3D_RASTER_COVER_LIST): no pass over the cover, no counter to clear
     const int* count = reinterpret_cast<const int*>(cover) + items;
     a.area_list = count + 16;
     a.area_count = count;
@@ -622,53 +607,43 @@ P3D_API size_t p3d_rasterize_meshes_backward_workspace_bytes(int N, int H, int W
   return ((size_t)N * (size_t)((H + 15) / 16) * (size_t)((W + 15) / 16) + 16) * sizeof(int);
 }
 
-P3D_API int p3d_rasterize_meshes_backward_with_cover(const float* face_verts, const int64_t* p2f, const float* grad_zbuf,
-                                                     const float* grad_bary, const float* grad_dists, const int32_t* cover,
-                                                     int64_t F, int N, int H, int W, int K, int persp, int clip,
-                                                     float* grad_face_verts, void* workspace, size_t workspace_bytes,
-                                                     p3d_stream_t stream) {
-  if (F < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if (F == 0) return P3D_OK;
-  if (!grad_face_verts || !face_verts) return P3D_ERR_INVALID_ARG;
+P3D_API int p3d_rasterize_meshes_backward_ex(const float* face_verts, const int64_t* faces, float* face_pre, const int64_t* p2f,
+                                              const float* grad_zbuf, const float* grad_bary, const float* grad_dists, const int32_t* cover,
+                                              int64_t F, int64_t V, int N, int H, int W, int K, int persp, int clip, unsigned flags,
+                                              float* grad_out, void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
+  if (F < 0 || V < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
+  if ((flags & ~(P3D_BWD_COVER_HAS_LIST | P3D_BWD_MAKE_FACE_PRE)) != 0 || ((uintptr_t)face_pre & 15u)) return P3D_ERR_INVALID_ARG;
+  // grad_out: (F, 3, 3) per face, or (V, 3) per vertex through faces
+  const int64_t out_floats = faces ? V * 3 : F * 9;
+  if (out_floats == 0) return P3D_OK;
+  if (!grad_out) return P3D_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_face_verts, 0, (size_t)F * 9 * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
-  if ((int64_t)N * H * W * K == 0) return P3D_OK;
-  if (!p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
-  return launch_mesh_backward(face_verts, nullptr, -1, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip,
-                              grad_face_verts, cover, workspace, workspace_bytes, s);
+  if (hipMemsetAsync(grad_out, 0, (size_t)out_floats * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
+  if (F == 0 || (int64_t)N * H * W * K == 0) return P3D_OK;
+  if (!face_verts || !p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
+  if (flags & P3D_BWD_MAKE_FACE_PRE) {
+    if (face_pre != nullptr && persp && clip && (K == 4 || K == 8)) {  // (the kernels that read the records)
+      int64_t blocks = ceil_div(F, 256);
+      if (blocks > 256 * 16) blocks = 256 * 16;
+      LaunchScope ls("face_pre", s);
+      face_pre_kernel<<<(unsigned)blocks, 256, 0, s>>>(face_verts, F, reinterpret_cast<float4*>(face_pre));
+      const int st = launch_status();
+      if (st != P3D_OK) return st;
+    } else {
+      face_pre = nullptr;
+    }
+  }
+  const bool list = cover != nullptr && (flags & P3D_BWD_COVER_HAS_LIST) != 0;
+  return launch_mesh_backward(face_verts, faces, faces ? V : -1, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip,
+                              grad_out, cover, list ? nullptr : workspace, list ? 0 : workspace_bytes, s, list, face_pre);
 }
 
 P3D_API int p3d_rasterize_meshes_backward(const float* face_verts, const int64_t* p2f, const float* grad_zbuf,
                                           const float* grad_bary, const float* grad_dists, int64_t F, int N, int H,
                                           int W, int K, int persp, int clip, float* grad_face_verts,
                                           p3d_stream_t stream) {
-  return p3d_rasterize_meshes_backward_with_cover(face_verts, p2f, grad_zbuf, grad_bary, grad_dists, nullptr, F, N, H, W, K,
-                                                  persp, clip, grad_face_verts, nullptr, 0, stream);
-}
-
-P3D_API int p3d_rasterize_meshes_backward_verts_with_cover(const float* face_verts, const int64_t* faces, const int64_t* p2f,
-                                                           const float* grad_zbuf, const float* grad_bary,
-                                                           const float* grad_dists, const int32_t* cover, int64_t F,
-                                                           int64_t V, int N, int H, int W, int K, int persp, int clip,
-                                                           float* grad_verts, void* workspace, size_t workspace_bytes,
-                                                           p3d_stream_t stream) {
-  if (F < 0 || V < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if (V == 0) return P3D_OK;
-  if (!grad_verts) return P3D_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_verts, 0, (size_t)V * 3 * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
-  if (F == 0 || (int64_t)N * H * W * K == 0) return P3D_OK;
-  if (!face_verts || !faces || !p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
-  return launch_mesh_backward(face_verts, faces, V, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip,
-                              grad_verts, cover, workspace, workspace_bytes, s);
-}
-
-P3D_API int p3d_rasterize_meshes_backward_verts(const float* face_verts, const int64_t* faces, const int64_t* p2f,
-                                                const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
-                                                int64_t F, int64_t V, int N, int H, int W, int K, int persp, int clip,
-                                                float* grad_verts, p3d_stream_t stream) {
-  return p3d_rasterize_meshes_backward_verts_with_cover(face_verts, faces, p2f, grad_zbuf, grad_bary, grad_dists, nullptr, F, V,
-                                                        N, H, W, K, persp, clip, grad_verts, nullptr, 0, stream);
+  return p3d_rasterize_meshes_backward_ex(face_verts, nullptr, nullptr, p2f, grad_zbuf, grad_bary, grad_dists, nullptr, F, 0, N, H, W, K,
+                                          persp, clip, 0, grad_face_verts, nullptr, 0, stream);
 }
 
 P3D_API int p3d_rasterize_meshes_cover_check(const int64_t* p2f, const int32_t* cover, int N, int H, int W, int K, int32_t* stale,
@@ -685,74 +660,4 @@ P3D_API int p3d_rasterize_meshes_cover_check(const int64_t* p2f, const int32_t* 
   LaunchScope ls("mesh_cover_check", s);
   cover_check_kernel<<<(unsigned)blocks, 256, 0, s>>>(p2f, reinterpret_cast<const int*>(cover), N, H, W, K, CY, CX, reinterpret_cast<int*>(stale));
   return launch_status();
-}
-
-P3D_API int p3d_rasterize_meshes_backward_with_cover_list(const float* face_verts, const int64_t* p2f, const float* grad_zbuf,
-                                                          const float* grad_bary, const float* grad_dists, const int32_t* cover_and_list,
-                                                          int64_t F, int N, int H, int W, int K, int persp, int clip,
-                                                          float* grad_face_verts, p3d_stream_t stream) {
-  if (F < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if (F == 0) return P3D_OK;
-  if (!grad_face_verts || !face_verts) return P3D_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_face_verts, 0, (size_t)F * 9 * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
-  if ((int64_t)N * H * W * K == 0) return P3D_OK;
-  if (!p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
-  return launch_mesh_backward(face_verts, nullptr, -1, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip, grad_face_verts,
-                              cover_and_list, nullptr, 0, s, cover_and_list != nullptr);
-}
-
-P3D_API int p3d_rasterize_meshes_backward_verts_with_cover_list(const float* face_verts, const int64_t* faces, const int64_t* p2f,
-                                                                const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
-                                                                const int32_t* cover_and_list, int64_t F, int64_t V, int N, int H, int W,
-                                                                int K, int persp, int clip, float* grad_verts, p3d_stream_t stream) {
-  if (F < 0 || V < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if (V == 0) return P3D_OK;
-  if (!grad_verts) return P3D_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_verts, 0, (size_t)V * 3 * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
-  if (F == 0 || (int64_t)N * H * W * K == 0) return P3D_OK;
-  if (!face_verts || !faces || !p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
-  return launch_mesh_backward(face_verts, faces, V, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip, grad_verts,
-                              cover_and_list, nullptr, 0, s, cover_and_list != nullptr);
-}
-
-P3D_API int p3d_rasterize_meshes_backward_verts_pre(const float* face_verts, const float* face_pre, const int64_t* faces, const int64_t* p2f,
-                                                    const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
-                                                    const int32_t* cover_and_list, int64_t F, int64_t V, int N, int H, int W, int K,
-                                                    int persp, int clip, float* grad_verts, p3d_stream_t stream) {
-  if (F < 0 || V < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if (V == 0) return P3D_OK;
-  if (!grad_verts) return P3D_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_verts, 0, (size_t)V * 3 * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
-  if (F == 0 || (int64_t)N * H * W * K == 0) return P3D_OK;
-  if (!face_verts || !faces || !p2f || !grad_zbuf || !grad_bary || !grad_dists || ((uintptr_t)face_pre & 15u)) return P3D_ERR_INVALID_ARG;
-  return launch_mesh_backward(face_verts, faces, V, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip, grad_verts,
-                              cover_and_list, nullptr, 0, s, cover_and_list != nullptr, face_pre);
-}
-
-P3D_API int p3d_rasterize_meshes_backward_pre(const float* face_verts, const int64_t* p2f, const float* grad_zbuf, const float* grad_bary,
-                                              const float* grad_dists, const int32_t* cover, int cover_has_list, int64_t F, int N, int H,
-                                              int W, int K, int persp, int clip, float* grad_face_verts, float* face_pre_scratch,
-                                              void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
-  if (F < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if (F == 0) return P3D_OK;
-  if (!grad_face_verts || !face_verts || ((uintptr_t)face_pre_scratch & 15u)) return P3D_ERR_INVALID_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_face_verts, 0, (size_t)F * 9 * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
-  if ((int64_t)N * H * W * K == 0) return P3D_OK;
-  if (!p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
-  const bool use_pre = face_pre_scratch != nullptr && persp && clip && (K == 4 || K == 8);  // (the kernels that read the records)
-  if (use_pre) {
-    int64_t blocks = ceil_div(F, 256);
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    LaunchScope ls("face_pre", s);
-    face_pre_kernel<<<(unsigned)blocks, 256, 0, s>>>(face_verts, F, reinterpret_cast<float4*>(face_pre_scratch));
-    const int st = launch_status();
-    if (st != P3D_OK) return st;
-  }
-  const bool list = cover != nullptr && cover_has_list != 0;
-  return launch_mesh_backward(face_verts, nullptr, -1, p2f, grad_zbuf, grad_bary, grad_dists, N, H, W, K, persp, clip, grad_face_verts, cover,
-                              list ? nullptr : workspace, list ? 0 : workspace_bytes, s, list, use_pre ? face_pre_scratch : nullptr);
 }

@@ -7,7 +7,7 @@
 // twins of all of them.  SURVEY.md 8(f) row 3: here the transform happens INSIDE the face gather
 // (p3d_transform_gather_face_verts: world vertices + faces + two 4x4 matrices per mesh -> NDC face_verts (F,3,3), one
 // launch, no NDC vertex tensor, no padded layout), and its backward is one per-vertex kernel applied to the NDC vertex
-// gradient that p3d_rasterize_meshes_backward_verts has already reduced per vertex.
+// gradient that p3d_rasterize_meshes_backward_ex (faces given) has already reduced per vertex.
 //
 // Matrices follow the reference's row-vector convention: out_j = sum_i in_i * M[i][j] with in = (x, y, z, 1), then
 // xyz / w.  matrices: (N, 2, 4, 4) f32 row-major: [n][0] world -> view, [n][1] view -> NDC (projection composed with

@@ -7,15 +7,10 @@ runs on the HIP kernels of pytorch3d_amd.clip.
 """
 from typing import List, Optional, Tuple, Union
 
-import os
-
 import numpy as np
 import torch
 
 from . import _C
-
-# the fused gather also writes the backward's per-face reciprocals (P3D_FACE_PRE=0: the backward forms them per sample)
-FACE_PRE = os.environ.get("P3D_FACE_PRE", "1") not in ("", "0")
 
 kMaxFacesPerBin = 22  # rasterize_meshes.py:29
 
@@ -38,6 +33,21 @@ def default_bin_size(max_image_size: int) -> int:
     if max_image_size <= 64:
         return 8
     return int(2 ** max(np.ceil(np.log2(max_image_size)) - 4, 4))
+
+
+def _bins(im_size, bin_size, max_faces_per_bin, num_faces):
+    """rasterize_meshes.py:186-210: the defaults of bin_size and max_faces_per_bin, and the bin-count check."""
+    max_image_size = max(*im_size)
+    if bin_size is None:
+        bin_size = default_bin_size(max_image_size)
+    if bin_size != 0:
+        faces_per_bin = 1 + (max_image_size - 1) // bin_size
+        if faces_per_bin >= kMaxFacesPerBin:
+            raise ValueError("bin_size too small, number of faces per bin must be less than %d; got %d" %
+                             (kMaxFacesPerBin, faces_per_bin))
+    if max_faces_per_bin is None:
+        max_faces_per_bin = int(max(10000, num_faces / 5))
+    return bin_size, max_faces_per_bin
 
 
 def rasterize_meshes(
@@ -63,7 +73,6 @@ def rasterize_meshes(
     mesh_to_face_first_idx = meshes.mesh_to_faces_packed_first_idx()
     num_faces_per_mesh = meshes.num_faces_per_mesh()
     im_size = parse_image_size(image_size)
-    max_image_size = max(*im_size)
 
     clipped_faces = None
     clipped_faces_neighbor_idx = None
@@ -83,15 +92,7 @@ def rasterize_meshes(
             size=(faces_packed.shape[0] if fused_verts else face_verts.shape[0],), fill_value=-1,
             device=verts_packed.device, dtype=torch.int64)
 
-    if bin_size is None:
-        bin_size = default_bin_size(max_image_size)
-    if bin_size != 0:
-        faces_per_bin = 1 + (max_image_size - 1) // bin_size
-        if faces_per_bin >= kMaxFacesPerBin:
-            raise ValueError("bin_size too small, number of faces per bin must be less than %d; got %d" %
-                             (kMaxFacesPerBin, faces_per_bin))
-    if max_faces_per_bin is None:
-        max_faces_per_bin = int(max(10000, meshes._F / 5))
+    bin_size, max_faces_per_bin = _bins(im_size, bin_size, max_faces_per_bin, meshes._F)
 
     if fused_verts:
         return _RasterizeMeshVerts.apply(
@@ -188,22 +189,14 @@ class _RasterizeFaceVerts(torch.autograd.Function):
         cover = _C.checked_cover(pix_to_face, cover)  # (P3D_CHECK=1: verified on the device before it is trusted)
         if grad_zbuf is None and grad_barycentric_coords is None and grad_dists is None:
             return (None,) * 12
-        if grad_zbuf is None:
-            grad_zbuf = torch.zeros(pix_to_face.shape, dtype=torch.float32, device=pix_to_face.device)
-        if grad_dists is None:
-            grad_dists = torch.zeros(pix_to_face.shape, dtype=torch.float32, device=pix_to_face.device)
-        if grad_barycentric_coords is None:
-            grad_barycentric_coords = torch.zeros(pix_to_face.shape + (3,), dtype=torch.float32,
-                                                  device=pix_to_face.device)
-        grad_face_verts = _C.rasterize_meshes_backward(face_verts, pix_to_face, grad_zbuf, grad_barycentric_coords,
-                                                       grad_dists, ctx.perspective_correct,
-                                                       ctx.clip_barycentric_coords, _cover=cover)
+        grad_face_verts = _C._mesh_backward(face_verts, None, 0, pix_to_face, grad_zbuf, grad_barycentric_coords, grad_dists,
+                                            ctx.perspective_correct, ctx.clip_barycentric_coords, cover)
         return (grad_face_verts,) + (None,) * 11
 
 
 class _RasterizeMeshVerts(torch.autograd.Function):
     """`verts_packed[faces_packed]` + _RasterizeFaceVerts as ONE node: forward = the gather kernel + the rasterizer,
-    backward = p3d_rasterize_meshes_backward_verts, which flushes the per-face partials straight to grad_verts."""
+    backward = p3d_rasterize_meshes_backward_ex with faces, which flushes the per-face partials straight to grad_verts."""
 
     @staticmethod
     def forward(ctx, verts, faces, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size,
@@ -217,7 +210,7 @@ class _RasterizeMeshVerts(torch.autograd.Function):
         with torch.cuda.device(verts.device):
             face_verts = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
             # per-face reciprocals for the backward (include/p3d_amd.h: p3d_gather_face_verts_pre), written by the gather
-            face_pre = torch.empty((F, 4), dtype=torch.float32, device=verts.device) if (FACE_PRE and ctx.needs_input_grad[0]) else None
+            face_pre = torch.empty((F, 4), dtype=torch.float32, device=verts.device) if (_C.FACE_PRE and ctx.needs_input_grad[0]) else None
             if F and face_pre is not None:
                 rc = lib.p3d_gather_face_verts_pre(_C._ptr(verts_c), _C._ptr(faces_c), V, F, _C._ptr(face_verts), _C._ptr(face_pre),
                                                    _C._stream(verts.device))
@@ -238,41 +231,12 @@ class _RasterizeMeshVerts(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_pix_to_face, grad_zbuf, grad_barycentric_coords, grad_dists):
-        from . import _lib
-
         face_verts, faces, pix_to_face, cover, face_pre = ctx.saved_tensors
-
         cover = _C.checked_cover(pix_to_face, cover)  # (P3D_CHECK=1: verified on the device before it is trusted)
         if grad_zbuf is None and grad_barycentric_coords is None and grad_dists is None:
             return (None,) * 13
-        _refuse_when_deterministic()
-        dev = pix_to_face.device
-        N, H, W, K = pix_to_face.shape
-        zeros = lambda *tail: torch.zeros(tuple(pix_to_face.shape) + tail, dtype=torch.float32, device=dev)
-        gz = grad_zbuf.contiguous() if grad_zbuf is not None else zeros()
-        gd = grad_dists.contiguous() if grad_dists is not None else zeros()
-        gb = grad_barycentric_coords.contiguous() if grad_barycentric_coords is not None else zeros(3)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            grad_verts = torch.empty((ctx.V, 3), dtype=torch.float32, device=dev)
-            has_list = _C.cover_has_list(cover, N, H, W)
-            if face_pre is not None and (has_list or cover is None):
-                rc = lib.p3d_rasterize_meshes_backward_verts_pre(
-                    _C._ptr(face_verts), _C._ptr(face_pre), _C._ptr(faces), _C._ptr(pix_to_face), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
-                    _C.cover_ptr(cover, N, H, W), faces.shape[0], ctx.V, N, H, W, K, ctx.flags[0], ctx.flags[1], _C._ptr(grad_verts),
-                    _C._stream(dev))
-            elif has_list:  # the forward listed the areas that hold a face: no list builder, no workspace
-                rc = lib.p3d_rasterize_meshes_backward_verts_with_cover_list(
-                    _C._ptr(face_verts), _C._ptr(faces), _C._ptr(pix_to_face), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
-                    _C.cover_ptr(cover, N, H, W), faces.shape[0], ctx.V, N, H, W, K, ctx.flags[0], ctx.flags[1], _C._ptr(grad_verts),
-                    _C._stream(dev))
-            else:
-                ws = _C.backward_workspace(cover, N, H, W, dev)
-                rc = lib.p3d_rasterize_meshes_backward_verts_with_cover(
-                    _C._ptr(face_verts), _C._ptr(faces), _C._ptr(pix_to_face), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
-                    _C.cover_ptr(cover, N, H, W), faces.shape[0], ctx.V, N, H, W, K, ctx.flags[0], ctx.flags[1], _C._ptr(grad_verts),
-                    _C._ptr(ws), ws.numel(), _C._stream(dev))
-            _lib.check(rc, "rasterize_meshes_backward")
+        grad_verts = _C._mesh_backward(face_verts, faces, ctx.V, pix_to_face, grad_zbuf, grad_barycentric_coords, grad_dists,
+                                       *ctx.flags, cover, face_pre)
         return (grad_verts,) + (None,) * 12
 
 
@@ -337,16 +301,7 @@ def rasterize_meshes_world(meshes_world, world_to_view, view_to_ndc, image_size=
                                 max_faces_per_bin, perspective_correct, clip_barycentric_coords, cull_backfaces)
     mats = _pack_matrices(w2v, v2n, n, verts.device)
     im_size = parse_image_size(image_size)
-    max_image_size = max(*im_size)
-    if bin_size is None:
-        bin_size = default_bin_size(max_image_size)
-    if bin_size != 0:
-        faces_per_bin = 1 + (max_image_size - 1) // bin_size
-        if faces_per_bin >= kMaxFacesPerBin:
-            raise ValueError("bin_size too small, number of faces per bin must be less than %d; got %d" %
-                             (kMaxFacesPerBin, faces_per_bin))
-    if max_faces_per_bin is None:
-        max_faces_per_bin = int(max(10000, meshes_world._F / 5))
+    bin_size, max_faces_per_bin = _bins(im_size, bin_size, max_faces_per_bin, meshes_world._F)
     nbr = torch.full((faces.shape[0],), -1, dtype=torch.int64, device=verts.device)
     return _RasterizeMeshWorld.apply(verts, faces, meshes_world.mesh_to_faces_packed_first_idx(),
                                      meshes_world.num_faces_per_mesh(), meshes_world.mesh_to_verts_packed_first_idx(), mats, nbr,
@@ -426,15 +381,9 @@ class _PackedVertsView:
         return self._meshes._F
 
 
-def _refuse_when_deterministic():
-    """The backward scatters with float atomics, like the reference's (rasterize_meshes.cu:587 alertNotDeterministic)."""
-    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
-        raise RuntimeError("RasterizeMeshesBackwardCuda does not have a deterministic implementation")
-
-
 class _RasterizeMeshWorld(torch.autograd.Function):
     """world vertices -> fragments as ONE node: p3d_transform_gather_face_verts + the rasterizer; backward =
-    p3d_rasterize_meshes_backward_verts (per-vertex NDC gradient) + p3d_transform_verts_backward."""
+    p3d_rasterize_meshes_backward_ex with faces (per-vertex NDC gradient) + p3d_transform_verts_backward."""
 
     @staticmethod
     def forward(ctx, verts, faces, face_first, num_faces, vert_first, mats, nbr, static):
@@ -467,28 +416,11 @@ class _RasterizeMeshWorld(torch.autograd.Function):
         cover = _C.checked_cover(pix_to_face, cover)  # (P3D_CHECK=1: verified on the device before it is trusted)
         if grad_zbuf is None and grad_bary is None and grad_dists is None:
             return (None,) * 8
-        _refuse_when_deterministic()
-        dev = pix_to_face.device
-        N, H, W, K = pix_to_face.shape
-        zeros = lambda *tail: torch.zeros(tuple(pix_to_face.shape) + tail, dtype=torch.float32, device=dev)
-        gz = grad_zbuf.contiguous() if grad_zbuf is not None else zeros()
-        gd = grad_dists.contiguous() if grad_dists is not None else zeros()
-        gb = grad_bary.contiguous() if grad_bary is not None else zeros(3)
-        lib = _lib.load()
         V = verts.shape[0]
+        g_ndc = _C._mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad_dists, *ctx.flags, cover)
+        lib = _lib.load()
+        dev = pix_to_face.device
         with torch.cuda.device(dev):
-            g_ndc = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            if _C.cover_has_list(cover, N, H, W):
-                rc = lib.p3d_rasterize_meshes_backward_verts_with_cover_list(
-                    _C._ptr(face_verts), _C._ptr(faces), _C._ptr(pix_to_face), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
-                    _C.cover_ptr(cover, N, H, W), faces.shape[0], V, N, H, W, K, ctx.flags[0], ctx.flags[1], _C._ptr(g_ndc), _C._stream(dev))
-            else:
-                ws = _C.backward_workspace(cover, N, H, W, dev)
-                rc = lib.p3d_rasterize_meshes_backward_verts_with_cover(
-                    _C._ptr(face_verts), _C._ptr(faces), _C._ptr(pix_to_face), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
-                    _C.cover_ptr(cover, N, H, W), faces.shape[0], V, N, H, W, K, ctx.flags[0], ctx.flags[1], _C._ptr(g_ndc), _C._ptr(ws),
-                    ws.numel(), _C._stream(dev))
-            _lib.check(rc, "rasterize_meshes_backward")
             g_world = torch.empty((V, 3), dtype=torch.float32, device=dev)
             rc = lib.p3d_transform_verts_backward(_C._ptr(verts), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g_ndc), V,
                                                   vert_first.shape[0], mats.shape[0], _C._ptr(g_world), _C._stream(dev))

@@ -60,11 +60,11 @@ def test_library_contains_gfx950_code_object():
     assert b"gfx950" in blob and b"mesh_raster_kernel" in blob
 
 
-def test_library_loads_and_answers_without_a_device():
+def test_abi_v2_library_loads_and_answers_without_a_device():
     from pytorch3d_amd import _lib
 
     lib = _lib.load()
-    assert lib.p3d_abi_version() == 1
+    assert lib.p3d_abi_version() == 2
     assert b"150" in lib.p3d_error_string(-2) or b"K" in lib.p3d_error_string(-2)
     assert lib.p3d_error_string(0)
     # workspace sizing is pure host arithmetic
@@ -107,6 +107,51 @@ def test_library_loads_and_answers_without_a_device():
     # empty problems return OK before touching the device
     rc = lib.p3d_rasterize_meshes_naive(null, null, null, null, 0, 0, 8, 8, 0.0, 4, 0, 0, 0, null, null, null, null, null)
     assert rc == 0
+
+
+def test_mesh_ex_entries_validate_before_any_launch():
+    """p3d_rasterize_meshes_ex / p3d_rasterize_meshes_backward_ex: the checks that precede any device work, with null pointers."""
+    from pytorch3d_amd import _lib
+
+    lib = _lib.load()
+    null = ctypes.c_void_p(None)
+    some = ctypes.c_void_p(4096)  # never dereferenced: every call below returns before it would touch the device
+    odd = ctypes.c_void_p(4096 + 4)  # not 16-byte aligned
+    COVER_LIST, TIE = _lib.RASTER_COVER_LIST, _lib.RASTER_CUDA_TIE_ORDER
+
+    def fwd(N, H, W, K, cover, flags):
+        return lib.p3d_rasterize_meshes_ex(null, null, null, null, 0, N, H, W, 0.0, K, 0, 0, 0, 0, 0, null, null, null, null,
+                                           cover, flags, null, 0, null)
+
+    assert fwd(1, 8, 8, 151, null, 0) == -2  # K > 150
+    assert fwd(-1, 8, 8, 4, null, 0) == -1 and fwd(1, -8, 8, 4, null, 0) == -1 and fwd(1, 8, 8, -4, null, 0) == -1
+    assert fwd(1, 8, 8, 4, some, 4) == -1  # unknown flag bit
+    assert fwd(1, 8, 8, 4, some, COVER_LIST | TIE) == -1
+    assert fwd(1, 8, 8, 4, null, COVER_LIST) == -1  # a list needs its buffer
+    assert fwd(0, 8, 8, 4, null, TIE) == 0 and fwd(1, 8, 8, 0, null, 0) == 0  # empty problems: OK
+
+    def bwd(F, V, faces, face_pre, flags, N=1, K=4):
+        return lib.p3d_rasterize_meshes_backward_ex(null, faces, face_pre, null, null, null, null, null, F, V, N, 8, 8, K, 1, 1,
+                                                    flags, null, null, 0, null)
+
+    for neg in ((-1, 0, 1, 4), (1, -1, 1, 4), (1, 0, -1, 4), (1, 0, 1, -4)):
+        F, V, N, K = neg
+        assert bwd(F, V, some, null, 0, N=N, K=K) == -1
+    assert bwd(0, 0, null, null, 4) == -1  # unknown flag bit
+    assert bwd(0, 0, null, odd, _lib.BWD_MAKE_FACE_PRE) == -1 and bwd(0, 5, some, odd, 0) == -1  # misaligned face_pre
+    assert bwd(0, 0, null, some, _lib.BWD_MAKE_FACE_PRE | _lib.BWD_COVER_HAS_LIST) == 0  # F == 0: grad_face_verts is empty
+    assert bwd(10, 0, some, some, 0) == 0  # V == 0: grad_verts is empty
+    assert bwd(10, 0, null, null, 0) == -1  # F > 0 per face: the output is missing
+
+
+def test_stale_library_fails_in_load(monkeypatch):
+    """A library of another ABI version is refused by _lib.load() before any symbol of this one is looked up."""
+    from pytorch3d_amd import _lib
+
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI_VERSION", _lib.ABI_VERSION + 1)
+    with pytest.raises(_lib.ExtensionMissing, match="ABI version"):
+        _lib.load()
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):

@@ -1,4 +1,4 @@
-"""Row cover (include/p3d_amd.h: p3d_rasterize_meshes_with_cover): the forward's summary of which 16-pixel row segments of
+"""Row cover (include/p3d_amd.h: p3d_rasterize_meshes_ex): the forward's summary of which 16-pixel row segments of
 pix_to_face hold a face, saved by the autograd nodes next to pix_to_face so that the backward does not read the empty ones.
 
   * the cover equals the one computed from pix_to_face itself, bit for bit, on every forward kernel variant (K with and
@@ -71,7 +71,7 @@ def test_cover_with_clipped_face_neighbours():
 
 
 @pytest.mark.parametrize("K", [1, 2, 4, 6, 8, 16])
-def test_backward_with_cover_equals_backward_without(K):
+def test_backward_ex_with_cover_equals_backward_without(K):
     from pytorch3d_amd import _C, _lib
 
     m, fv, first, cnt = _batch(4, seed=40 + K, fmin=300, fmax=1500)
@@ -96,10 +96,10 @@ def test_backward_with_cover_equals_backward_without(K):
     for cv in (None, cover):
         g = torch.empty((V, 3), dtype=torch.float32, device=fv.device)
         ws = _C.backward_workspace(cv, N, H, W, fv.device)
-        rc = lib.p3d_rasterize_meshes_backward_verts_with_cover(
-            _C._ptr(fv), _C._ptr(faces), _C._ptr(out[0]), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd), _C.cover_ptr(cv, N, H, W),
-            faces.shape[0], V, N, H, W, K, 1, 1, _C._ptr(g), _C._ptr(ws), ws.numel(), _C._stream(fv.device))
-        _lib.check(rc, "backward_verts_with_cover")
+        rc = lib.p3d_rasterize_meshes_backward_ex(
+            _C._ptr(fv), _C._ptr(faces), None, _C._ptr(out[0]), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd), _C.cover_ptr(cv, N, H, W),
+            faces.shape[0], V, N, H, W, K, 1, 1, 0, _C._ptr(g), _C._ptr(ws), ws.numel(), _C._stream(fv.device))
+        _lib.check(rc, "backward_ex (faces, cover)")
         res.append(g)
     assert torch.allclose(res[0], res[1], rtol=1e-4, atol=1e-5 * res[0].abs().max().item())
 
@@ -279,7 +279,7 @@ def test_writes_the_version_counter_cannot_see():
 
 @pytest.mark.parametrize("K,size,bin_size", [(8, (96, 80), 32), (8, (50, 37), 16), (4, (64, 64), 0), (1, (33, 130), 32), (12, (40, 40), 16)])
 def test_the_forward_lists_the_words_of_its_cover_and_the_backward_takes_the_list(K, size, bin_size):
-    """include/p3d_amd.h: p3d_rasterize_meshes_with_cover_list (round 6).  The buffer behind the cover that `_C._rasterize_meshes_covered`
+    """include/p3d_amd.h: P3D_RASTER_COVER_LIST (round 6).  The buffer behind the cover that `_C._rasterize_meshes_covered`
     returns holds the number of non-empty cover words and, in the order the forward's tiles finished, their indices -- each exactly
     once; the backward that takes the list (no list-builder kernel, no workspace) returns what the backward without any cover returns;
     a clone of the cover carries no list and takes the old road."""

@@ -353,8 +353,8 @@ def test_backward_every_kernel_vs_oracle(K):
 
 
 @pytest.mark.parametrize("K", [4, 8])
-def test_backward_with_per_face_reciprocals(K):
-    """p3d_gather_face_verts_pre + p3d_rasterize_meshes_backward_verts_pre (round 6): the gather writes 1 / area and 1 / |edge|^2 per
+def test_backward_ex_with_per_face_reciprocals(K):
+    """p3d_gather_face_verts_pre + p3d_rasterize_meshes_backward_ex with the records (round 6): the gather writes 1 / area and 1 / |edge|^2 per
     face (-1 for an edge of squared length <= 1e-8: geometry_utils.cuh:345), the perspective + clip backward reads them instead of
     forming them per sample.  A soup with needles (one degenerate edge each) and slivers: the records against torch, the gradient
     against the float64 restatement and against the backward that forms them per sample, with and without the cover list."""
@@ -404,10 +404,11 @@ def test_backward_with_per_face_reciprocals(K):
 
     def backward(with_pre, with_cover):
         out = torch.full((3 * F, 3), float("nan"), device=d)
-        rc = lib.p3d_rasterize_meshes_backward_verts_pre(
-            _C._ptr(face_verts), _C._ptr(pre) if with_pre else None, _C._ptr(faces), _C._ptr(p2f), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
-            _C.cover_ptr(cover, 2, *size) if with_cover else None, F, 3 * F, 2, size[0], size[1], K, 1, 1, _C._ptr(out), _C._stream(d))
-        _lib.check(rc, "backward_verts_pre")
+        rc = lib.p3d_rasterize_meshes_backward_ex(
+            _C._ptr(face_verts), _C._ptr(faces), _C._ptr(pre) if with_pre else None, _C._ptr(p2f), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd),
+            _C.cover_ptr(cover, 2, *size) if with_cover else None, F, 3 * F, 2, size[0], size[1], K, 1, 1, _lib.BWD_COVER_HAS_LIST,
+            _C._ptr(out), None, 0, _C._stream(d))
+        _lib.check(rc, "backward_ex (faces, records)")
         return out.cpu().reshape(F, 3, 3)  # (face 5's wrapped ids address its own rows)
 
     plain = backward(False, True)
@@ -417,9 +418,9 @@ def test_backward_with_per_face_reciprocals(K):
                                      gd.cpu(), True, True, rtol=2e-3, reference=plain)
     # not perspective + clip: the records are ignored, not misread
     out = torch.empty((3 * F, 3), device=d)
-    _lib.check(lib.p3d_rasterize_meshes_backward_verts_pre(
-        _C._ptr(face_verts), _C._ptr(pre), _C._ptr(faces), _C._ptr(p2f), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd), None, F, 3 * F, 2,
-        size[0], size[1], K, 0, 0, _C._ptr(out), _C._stream(d)), "backward_verts_pre")
+    _lib.check(lib.p3d_rasterize_meshes_backward_ex(
+        _C._ptr(face_verts), _C._ptr(faces), _C._ptr(pre), _C._ptr(p2f), _C._ptr(gz), _C._ptr(gb), _C._ptr(gd), None, F, 3 * F, 2,
+        size[0], size[1], K, 0, 0, _lib.BWD_COVER_HAS_LIST, _C._ptr(out), None, 0, _C._stream(d)), "backward_ex (faces, records)")
     want_ff = _C.rasterize_meshes_backward(face_verts, p2f.clone(), gz, gb, gd, False, False)
     U.assert_face_grads_vs_truth(f"backward with face records K={K}, flat", out.cpu().reshape(F, 3, 3), fv, p2f.cpu(), gz.cpu(), gb.cpu(),
                                  gd.cpu(), False, False, rtol=2e-3, reference=want_ff.cpu())
@@ -428,7 +429,7 @@ def test_backward_with_per_face_reciprocals(K):
 @pytest.mark.parametrize("K", [4, 8])
 def test_reference_signature_backward_with_and_without_face_records(K):
     """`_C.rasterize_meshes_backward` as the reference calls it (face_verts in, grad_face_verts out): with _C.FACE_PRE the call first
-    writes the per-face reciprocals (p3d_rasterize_meshes_backward_pre) -- same gradients as the per-sample form within the gate, with
+    writes the per-face reciprocals (P3D_BWD_MAKE_FACE_PRE) -- same gradients as the per-sample form within the gate, with
     the forward's cover (list), a cloned cover (no list: workspace) and none."""
     from pytorch3d_amd import _C
 

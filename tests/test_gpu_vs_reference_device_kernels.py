@@ -114,7 +114,7 @@ def cuda_tie_order():
 
 @pytest.mark.parametrize("K", [1, 2, 3, 4, 8, 12, 20, 60])
 def test_cuda_tie_order_is_the_references_device_result_where_depths_tie_exactly(cuda_tie_order, K):
-    """`_C.CUDA_TIE_ORDER` (include/p3d_amd.h: p3d_rasterize_meshes_cuda_order): a soup in which every face exists three times
+    """`_C.CUDA_TIE_ORDER` (include/p3d_amd.h: P3D_RASTER_CUDA_TIE_ORDER): a soup in which every face exists three times
     (exact depth ties at every sample, at every place of the queue) and every eighth face has a clipped-face neighbour: with the
     switch on, ALL FOUR outputs equal the reference's device kernels bit for bit -- naive and binned, three flag sets; with it
     off the indices differ (the test has teeth).  270 faces: ONE 512-face chunk of the reference's coarse stage, whose bins
@@ -148,9 +148,9 @@ def test_cuda_tie_order_is_the_references_device_result_where_depths_tie_exactly
 
 
 @pytest.mark.parametrize("K", [2, 5, 8, 20])
-def test_cuda_tie_order_with_and_without_room_for_the_marks(K):
+def test_cuda_tie_order_flag_with_and_without_room_for_the_marks(K):
     """The replay finds its pixels through the lane masks the fine kernel leaves in the LAST bytes of the workspace, or -- when the
-    caller's workspace has no room for them (include/p3d_amd.h: p3d_rasterize_meshes_cuda_order) -- through the marks in the
+    caller's workspace has no room for them (include/p3d_amd.h: P3D_RASTER_CUDA_TIE_ORDER) -- through the marks in the
     output itself (the naive launch without a workspace): same bits either way, and the same as the binned launch on a worst-case,
     a short and an overflowing workspace, on the soup of the test above (every face three times: exact depth ties everywhere, every eighth face with a clipped neighbour)."""
     import ctypes
@@ -175,10 +175,10 @@ def test_cuda_tie_order_with_and_without_room_for_the_marks(K):
     def run(bin_size, M, nbytes):
         out = _C._mesh_outputs(N, H, W, K, d)
         ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=d) if nbytes is not None else None
-        rc = lib.p3d_rasterize_meshes_cuda_order(_C._ptr(fv), _C._ptr(first), _C._ptr(count), _C._ptr(nbr), F, N, H, W, 0.004, K, bin_size,
-                                                 M, 1, 1, 0, _C._ptr(out[0]), _C._ptr(out[1]), _C._ptr(out[2]), _C._ptr(out[3]), None,
-                                                 _C._ptr(ws) if ws is not None else None, nbytes or 0, stream)
-        _lib.check(rc, "rasterize_meshes_cuda_order")
+        rc = lib.p3d_rasterize_meshes_ex(_C._ptr(fv), _C._ptr(first), _C._ptr(count), _C._ptr(nbr), F, N, H, W, 0.004, K, bin_size,
+                                         M, 1, 1, 0, _C._ptr(out[0]), _C._ptr(out[1]), _C._ptr(out[2]), _C._ptr(out[3]), None,
+                                         _lib.RASTER_CUDA_TIE_ORDER, _C._ptr(ws) if ws is not None else None, nbytes or 0, stream)
+        _lib.check(rc, "rasterize_meshes_ex (CUDA tie order)")
         torch.cuda.synchronize()
         assert int((out[0] == -2).sum()) == 0, "a mark survived the replay"
         return out
