@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define P3D_ABI_VERSION 2
+#define P3D_ABI_VERSION 3
 
 #define P3D_OK 0
 #define P3D_ERR_INVALID_ARG (-1)   /* null pointer / negative size / bad mode                    */
@@ -146,7 +146,7 @@ int p3d_rasterize_meshes_cover_check(const int64_t* pix_to_face, const int32_t* 
  * finished. */
 size_t p3d_rasterize_meshes_cover_list_bytes(int N, int H, int W);
 
-/* flags of p3d_rasterize_meshes_ex */
+/* flags of p3d_rasterize_meshes_ex (both) and p3d_rasterize_points_ex (P3D_RASTER_CUDA_TIE_ORDER only) */
 #define P3D_RASTER_COVER_LIST 1u     /* `cover` is a cover-list buffer: the forward also writes the list behind the words       */
 #define P3D_RASTER_CUDA_TIE_ORDER 2u /* the replay of the reference's CUDA tie procedure (below)                                 */
 
@@ -242,29 +242,43 @@ int p3d_transform_verts_backward(const float* verts_world, const int64_t* mesh_t
 /* ---- point clouds -------------------------------------------------------------------- */
 
 size_t p3d_rasterize_points_workspace_bytes(int64_t P, int N, int H, int W, int bin_size, int max_points_per_bin);
-/* Short workspaces for p3d_rasterize_points, exactly as for the meshes (above): any workspace of at least
- * p3d_rasterize_points_short_workspace_bytes(..., 0) bytes is accepted, the lists take what is left, the device decides whether
- * they fit and the naive kernel writes the same outputs when they do not.  (1M points, 512 x 512, max_points_per_bin = P / 5:
- * worst case 0.8 GB for one cloud, 1.3 M entries = 5 MB needed.) */
 size_t p3d_rasterize_points_short_workspace_bytes(int64_t P, int N, int H, int W, int bin_size, int max_points_per_bin,
                                                   int64_t list_entries);
 size_t p3d_rasterize_points_workspace_need_offset(int64_t P, int N, int H, int W, int bin_size, int max_points_per_bin);
 
+/* The point forward.  Outputs idxs (N,H,W,K) i32, zbuf, dists (squared) f32; bin_size == 0 or max_points_per_bin == 0 -> naive
+ * path, else coarse binning + fine rasterization.
+ *   Short workspaces, exactly as for the meshes (above): any workspace of at least p3d_rasterize_points_short_workspace_bytes(...,
+ *     0) bytes is accepted, the lists take what is left, the device decides whether they fit and the naive kernel writes the same
+ *     outputs when they do not.  (1M points, 512 x 512, max_points_per_bin = P / 5: worst case 0.8 GB for one cloud, 1.3 M entries
+ *     = 5 MB needed.)
+ *   flags: 0 or P3D_RASTER_CUDA_TIE_ORDER.  The reference's point kernels keep the same unsorted array as its mesh kernels
+ *     (rasterize_points.cu:38-84) and sort it by depth ALONE (rasterize_points.cu:26-28, stable): where points tie exactly in depth,
+ *     the survivors at the K-th place and the order of the tied entries follow the array positions.  With the flag a replay re-runs
+ *     that procedure, points in ascending index, for every pixel whose K slots are full.
+ *   images non-null: PointsRenderer's chain in the same call (round 6; renderer/points/renderer.py:56-76: fragments =
+ *     rasterize_points(...), weights = 1 - dists / r^2, images = alpha_composite(idx, weights, features); the reference has no
+ *     single operator for it, the patched PointsRenderer (pytorch3d_amd.shim) and pytorch3d_amd.render_points use it).  images
+ *     (N, H, W, C) f32 = the compositing of features (P, C) f32 rows, C in 1..4, with alpha = 1 - dists * inv_r2, inv_r2 =
+ *     float(1) / float(r * r) (how torch evaluates `dists / (r * r)`); composite_mode P3D_COMPOSITE_ALPHA (AlphaCompositor,
+ *     alpha_composite.cu:24-68) or P3D_COMPOSITE_NORM_SUM (NormWeightedCompositor, norm_weighted_sum.cu:24-154; the constants are
+ *     defined with the compositing operators below).  The pixel is formed in the fine kernel's epilogue while its K entries are in
+ *     LDS (K <= 28, binned; with a short workspace whose lists did not fit: by a pass behind the stand-by kernel, decided on the
+ *     device), else by a pass behind the rasterizer.  Bit-equal to the three operators run one after the other.  images null:
+ *     composite_mode, features, C and inv_r2 are ignored.
+ * Unknown flag bits, P3D_RASTER_COVER_LIST, or P3D_RASTER_CUDA_TIE_ORDER together with images: P3D_ERR_INVALID_ARG. */
+int p3d_rasterize_points_ex(const float* points, const int64_t* cloud_to_packed_first_idx, const int64_t* num_points_per_cloud,
+                            const float* radius, int64_t P, int N, int H, int W, int points_per_pixel, int bin_size,
+                            int max_points_per_bin, int32_t* idxs, float* zbuf, float* dists, int composite_mode,
+                            const float* features, int C, float inv_r2, float* images, unsigned flags, void* workspace,
+                            size_t workspace_bytes, p3d_stream_t stream);
+
 /* replaces RasterizePoints, pytorch3d/csrc/rasterize_points/rasterize_points.h:343-374 (_C.rasterize_points).
- * Outputs idxs (N,H,W,K) i32, zbuf, dists (squared) f32. */
+ * = p3d_rasterize_points_ex(no images, flags 0). */
 int p3d_rasterize_points(const float* points, const int64_t* cloud_to_packed_first_idx,
                          const int64_t* num_points_per_cloud, const float* radius, int64_t P, int N, int H, int W,
                          int points_per_pixel, int bin_size, int max_points_per_bin, int32_t* idxs, float* zbuf,
                          float* dists, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
-
-/* p3d_rasterize_points, then the CUDA tie order (see P3D_RASTER_CUDA_TIE_ORDER): the reference's point kernels keep the same
- * unsorted array (rasterize_points.cu:38-84) and sort it by depth ALONE (rasterize_points.cu:26-28, stable): where points tie
- * exactly in depth, the survivors at the K-th place and the order of the tied entries follow the array positions.  The replay
- * re-runs that procedure, points in ascending index, for every pixel whose K slots are full. */
-int p3d_rasterize_points_cuda_order(const float* points, const int64_t* cloud_to_packed_first_idx,
-                                    const int64_t* num_points_per_cloud, const float* radius, int64_t P, int N, int H, int W,
-                                    int points_per_pixel, int bin_size, int max_points_per_bin, int32_t* idxs, float* zbuf,
-                                    float* dists, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
 /* replaces RasterizePointsNaive, rasterize_points.h:70-99 (_C._rasterize_points_naive). */
 int p3d_rasterize_points_naive(const float* points, const int64_t* cloud_to_packed_first_idx,
@@ -282,26 +296,10 @@ int p3d_rasterize_points_fine(const float* points, const int32_t* bin_points, co
                               int BH, int BW, int M, int H, int W, int bin_size, int points_per_pixel, int32_t* idxs,
                               float* zbuf, float* dists, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
-/* PointsRenderer's chain as two launches (round 6; renderer/points/renderer.py:56-76: fragments = rasterize_points(...),
- * weights = 1 - dists / r^2, images = alpha_composite(idx, weights, features)).  The reference has no single operator for it; the
- * patched PointsRenderer (pytorch3d_amd.shim) and pytorch3d_amd.render_points call these.  mode: P3D_COMPOSITE_ALPHA (AlphaCompositor) or
- * P3D_COMPOSITE_NORM_SUM (NormWeightedCompositor: norm_weighted_sum.cu:24-154 in place of alpha_composite.cu below; the constants are
- * defined further down with the compositing operators).
- *   p3d_rasterize_points_composite: p3d_rasterize_points (same arguments, same workspace, same idxs / zbuf / dists) that also writes
- *     images (N, H, W, C) f32 = the alpha compositing (alpha_composite.cu:24-68) of features (P, C) f32 rows, C in 1..4, with
- *     alpha = 1 - dists * inv_r2, inv_r2 = float(1) / float(r * r) (how torch evaluates `dists / (r * r)`): the pixel is formed in the
- *     fine kernel's epilogue while its K entries are in LDS (K <= 28, binned; with a short workspace whose lists did not fit: by a pass
- *     behind the stand-by kernel, decided on the device), else by a pass behind the rasterizer.
- *     Bit-equal to the three operators run one after the other.
- *   p3d_rasterize_points_composite_backward: grad_points (P, 3) [z column zero: the chain does not expose zbuf] and grad_features
- *     (P, C), both fully written, from grad_images (N, H, W, C): alphaCompositeCudaBackwardKernel (alpha_composite.cu:72-141),
- *     grad_dists = -grad_alphas * inv_r2 and RasterizePointsBackwardCudaKernel (rasterize_points.cu:366-411) as ONE kernel whose two
- *     scatters share a wave-private table.  K <= 16, C in 1..4 (P3D_ERR_INVALID_ARG otherwise: run the three operators instead). */
-int p3d_rasterize_points_composite(int mode, const float* points, const int64_t* cloud_to_packed_first_idx,
-                                   const int64_t* num_points_per_cloud, const float* radius, const float* features, int64_t P, int C,
-                                   int N, int H, int W, int points_per_pixel, int bin_size, int max_points_per_bin, float inv_r2,
-                                   int32_t* idxs, float* zbuf, float* dists, float* images, void* workspace, size_t workspace_bytes,
-                                   p3d_stream_t stream);
+/* The backward of p3d_rasterize_points_ex with images: grad_points (P, 3) [z column zero: the chain does not expose zbuf] and
+ * grad_features (P, C), both fully written, from grad_images (N, H, W, C): alphaCompositeCudaBackwardKernel (alpha_composite.cu:72-141),
+ * grad_dists = -grad_alphas * inv_r2 and RasterizePointsBackwardCudaKernel (rasterize_points.cu:366-411) as ONE kernel whose two
+ * scatters share a wave-private table.  K <= 16, C in 1..4 (P3D_ERR_INVALID_ARG otherwise: run the three operators instead). */
 int p3d_rasterize_points_composite_backward(int mode, const float* points, const float* features, const int32_t* idxs,
                                             const float* dists, const float* grad_images, int64_t P, int C, int N, int H, int W,
                                             int points_per_pixel, float inv_r2, float* grad_points, float* grad_features,
@@ -318,32 +316,23 @@ int p3d_rasterize_points_backward(const float* points, const int32_t* idxs, cons
 #define P3D_COMPOSITE_NORM_SUM 1 /* weightedSumNorm*, compositing/norm_weighted_sum.h:57-115  */
 #define P3D_COMPOSITE_SUM 2      /* weightedSum*,     compositing/weighted_sum.h:55-111       */
 
-/* features (C,P) f32 contiguous; alphas / points_idx are logically (N,K,H,W) and addressed through
- * element strides (so the permuted (N,H,W,K) views the renderers pass need no copy);
- * result (N,C,H,W) f32 contiguous. */
-int p3d_composite_forward(int mode, const float* features, const float* alphas, const int64_t* points_idx, int N, int C,
-                          int64_t P, int K, int H, int W, const int64_t alphas_strides[4],
+/* alphas / points_idx are logically (N,K,H,W) and addressed through element strides (so the permuted (N,H,W,K) views the renderers
+ * pass need no copy); result (N,C,H,W) f32 contiguous.  features are logically (C,P) f32, addressed through the element strides
+ * (channel, point) of feature_strides: (P, 1) is the contiguous (C,P) tensor of the reference's operators, (1, C) the transposed
+ * view of a (P, C) tensor -- what PointsRenderer passes (renderer/points/renderer.py:67: `features_packed().permute(1, 0)`; the
+ * reference's launchers copy it to (C,P) first, compositing/alpha_composite.h:63-65).  With (1, C) a point's channels share a cache
+ * line: the gathers of a pixel cost one memory request per entry instead of C.  Null strides: (P, 1).  Any other layout:
+ * P3D_ERR_INVALID_ARG. */
+int p3d_composite_forward(int mode, const float* features, const int64_t feature_strides[2], const float* alphas,
+                          const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W, const int64_t alphas_strides[4],
                           const int64_t idx_strides[4], float* result, p3d_stream_t stream);
 
-/* grad_features (C,P) and grad_alphas (N,K,H,W) contiguous, both fully written. */
-int p3d_composite_backward(int mode, const float* grad_outputs, const float* features, const float* alphas,
-                           const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
+/* grad_alphas (N,K,H,W) contiguous and grad_features (C * P floats of one allocation in the layout grad_feature_strides names, null:
+ * (P, 1)), both fully written. */
+int p3d_composite_backward(int mode, const float* grad_outputs, const float* features, const int64_t feature_strides[2],
+                           const float* alphas, const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
                            const int64_t alphas_strides[4], const int64_t idx_strides[4], float* grad_features,
-                           float* grad_alphas, p3d_stream_t stream);
-
-/* The same operators with the FEATURES addressed through element strides (channel, point): (P, 1) is the contiguous (C,P) tensor
- * above, (1, C) the transposed view of a (P, C) tensor -- what PointsRenderer passes (renderer/points/renderer.py:67:
- * `features_packed().permute(1, 0)`; the reference's launchers copy it to (C,P) first, compositing/alpha_composite.h:63-65).
- * With (1, C) a point's channels share a cache line: the gathers of a pixel cost one memory request per entry instead of C.
- * grad_features: C * P floats of one allocation in the layout grad_feature_strides names, fully written. */
-int p3d_composite_forward_strided(int mode, const float* features, const int64_t feature_strides[2], const float* alphas,
-                                  const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
-                                  const int64_t alphas_strides[4], const int64_t idx_strides[4], float* result,
-                                  p3d_stream_t stream);
-int p3d_composite_backward_strided(int mode, const float* grad_outputs, const float* features, const int64_t feature_strides[2],
-                                   const float* alphas, const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
-                                   const int64_t alphas_strides[4], const int64_t idx_strides[4], float* grad_features,
-                                   const int64_t grad_feature_strides[2], float* grad_alphas, p3d_stream_t stream);
+                           const int64_t grad_feature_strides[2], float* grad_alphas, p3d_stream_t stream);
 
 /* ---- interpolate_face_attributes ----------------------------------------------------- */
 

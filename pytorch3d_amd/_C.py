@@ -82,6 +82,12 @@ def _check_k(K):
         raise RuntimeError(f"Must have points_per_pixel <= {kMaxPointsPerPixel}")
 
 
+def _refuse_when_deterministic(op_name):
+    """The backwards scatter with float atomics, like the reference's (rasterize_meshes.cu:587 alertNotDeterministic)."""
+    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
+        raise RuntimeError(f"{op_name} does not have a deterministic implementation")
+
+
 def _num_bins(H, W, bin_size, who):
     by, bx = 1 + (H - 1) // bin_size, 1 + (W - 1) // bin_size
     if by >= kMaxItemsPerBin or bx >= kMaxItemsPerBin:
@@ -461,12 +467,6 @@ def backward_workspace(cover, N, H, W, dev):
     return _workspace(n, dev)
 
 
-def _refuse_when_deterministic():
-    """The backward scatters with float atomics, like the reference's (rasterize_meshes.cu:587 alertNotDeterministic)."""
-    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
-        raise RuntimeError("RasterizeMeshesBackwardCuda does not have a deterministic implementation")
-
-
 # The one call into p3d_rasterize_meshes_backward_ex, for rasterize_meshes_backward below and the autograd nodes of
 # pytorch3d_amd/rasterize_meshes.py.  Which kernels a backward launches depends on the caller and the switches as follows:
 #
@@ -485,7 +485,7 @@ def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad
                    cover, face_pre=None):
     """grad_face_verts (F,3,3) when faces is None, else grad_verts (V,3) through faces (F,3).  Missing grads count as zeros;
     cover: the row cover of THIS pix_to_face or None; face_pre: the records of p3d_gather_face_verts_pre (faces given) or None."""
-    _refuse_when_deterministic()
+    _refuse_when_deterministic("RasterizeMeshesBackwardCuda")
     dev = pix_to_face.device
     zeros = lambda *tail: torch.zeros(tuple(pix_to_face.shape) + tail, dtype=torch.float32, device=dev)
     gz = _c(grad_zbuf, torch.float32) if grad_zbuf is not None else zeros()
@@ -546,14 +546,21 @@ def _point_outputs(N, H, W, K, device):
     return idx, zbuf, dists
 
 
-def rasterize_points(points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius, points_per_pixel,
-                     bin_size, max_points_per_bin):
-    """RasterizePoints, rasterize_points.h:343-374.  Returns (idxs int32, zbuf, dists2)."""
+_SPLAT_MODES = {"alpha": 0, "norm": 1}  # P3D_COMPOSITE_ALPHA / _NORM_SUM: AlphaCompositor / NormWeightedCompositor
+
+
+def _rasterize_points(who, points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius, points_per_pixel, bin_size,
+                      max_points_per_bin, features=None, inv_r2=0.0, mode="alpha"):
+    """The one call into p3d_rasterize_points_ex, for rasterize_points and rasterize_points_composite: ((idxs int32, zbuf, dists2),
+    images (N, H, W, C) or None).  features None: no compositing, in the tie order CUDA_TIE_ORDER asks for; else the default order."""
+    splat = features is not None
     dev = _same_device(("points", points), ("cloud_to_packed_first_idx", cloud_to_packed_first_idx),
-                       ("num_points_per_cloud", num_points_per_cloud), ("radius", radius))
+                       ("num_points_per_cloud", num_points_per_cloud), ("radius", radius), *((("features", features),) if splat else ()))
     _check_points(points)
     if radius.dim() != 1 or radius.size(0) != points.size(0):
         raise RuntimeError("radius must be of shape (P,)")
+    if splat and (features.dim() != 2 or features.size(0) != points.size(0) or not 1 <= features.size(1) <= 4):
+        raise RuntimeError("features must be of shape (P, C) with C in 1..4")
     K = int(points_per_pixel)
     _check_k(K)
     H, W = _hw(image_size)
@@ -562,21 +569,31 @@ def rasterize_points(points, cloud_to_packed_first_idx, num_points_per_cloud, im
     if binned:
         _num_bins(H, W, bin_size, "RasterizeCoarseCuda")
     pts, rad = _c(points, torch.float32), _c(radius, torch.float32)
+    feats = _c(features, torch.float32) if splat else None
     first, count = _c(cloud_to_packed_first_idx, torch.int64), _c(num_points_per_cloud, torch.int64)
-    N, P = count.size(0), pts.size(0)
+    N, P, C = count.size(0), pts.size(0), feats.size(1) if splat else 0
     lib = _lib.load()
     with torch.cuda.device(dev):
         out = _point_outputs(N, H, W, K, dev)
-        if out[0].numel() == 0:
-            return out
+        images = torch.empty((N, H, W, C), dtype=torch.float32, device=dev) if splat else None
+        if (images if splat else out[0]).numel() == 0:
+            return out, images
         ws, need, need_at, entries = _mesh_workspace(lib, P, N, H, W, bin_size, M, dev, "points") if binned else (_workspace(0, dev), None, 0, None)
-        entry = lib.p3d_rasterize_points_cuda_order if CUDA_TIE_ORDER else lib.p3d_rasterize_points
-        rc = entry(_ptr(pts), _ptr(first), _ptr(count), _ptr(rad), P, N, H, W, K, bin_size if binned else 0, M if binned else 0,
-                   _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "rasterize_points")
+        flags = _lib.RASTER_CUDA_TIE_ORDER if CUDA_TIE_ORDER and not splat else 0
+        rc = lib.p3d_rasterize_points_ex(_ptr(pts), _ptr(first), _ptr(count), _ptr(rad), P, N, H, W, K, bin_size if binned else 0,
+                                         M if binned else 0, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _SPLAT_MODES[mode] if splat else 0,
+                                         _ptr(feats), C, float(inv_r2), _ptr(images), flags, _ptr(ws), ws.numel(), _stream(dev))
+        _lib.check(rc, who)
         if need is not None:
             need.report_later(ws, need_at, entries)
-    return out
+    return out, images
+
+
+def rasterize_points(points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius, points_per_pixel,
+                     bin_size, max_points_per_bin):
+    """RasterizePoints, rasterize_points.h:343-374.  Returns (idxs int32, zbuf, dists2)."""
+    return _rasterize_points("rasterize_points", points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius,
+                             points_per_pixel, bin_size, max_points_per_bin)[0]
 
 
 def _rasterize_points_naive(points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius,
@@ -637,8 +654,7 @@ def _rasterize_points_fine(points, bin_points, image_size, radius, bin_size, poi
 def rasterize_points_backward(points, idxs, grad_zbuf, grad_dists):
     """RasterizePointsBackward, rasterize_points.h:281-305.  Returns grad_points (P,3)."""
     dev = _same_device(("points", points), ("idxs", idxs), ("grad_zbuf", grad_zbuf), ("grad_dists", grad_dists))
-    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
-        raise RuntimeError("RasterizePointsBackwardCuda does not have a deterministic implementation")
+    _refuse_when_deterministic("RasterizePointsBackwardCuda")
     pts = _c(points, torch.float32)
     ix = _c(idxs, torch.int32)
     gz, gd = _c(grad_zbuf, torch.float32), _c(grad_dists, torch.float32)
@@ -663,51 +679,20 @@ def inv_r2_of(radius):
     return float(np.float32(1.0) / np.float32(float(radius) * float(radius)))
 
 
-_SPLAT_MODES = {"alpha": 0, "norm": 1}  # P3D_COMPOSITE_ALPHA / _NORM_SUM: AlphaCompositor / NormWeightedCompositor
-
-
 def rasterize_points_composite(points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius, features, inv_r2,
                                points_per_pixel, bin_size, max_points_per_bin, mode="alpha"):
-    """include/p3d_amd.h: p3d_rasterize_points_composite.  rasterize_points's arguments + features (P, C), C in 1..4, inv_r2
-    (inv_r2_of) and the compositor ("alpha" / "norm").  Returns (idxs int32, zbuf, dists2, images (N, H, W, C))."""
-    dev = _same_device(("points", points), ("cloud_to_packed_first_idx", cloud_to_packed_first_idx),
-                       ("num_points_per_cloud", num_points_per_cloud), ("radius", radius), ("features", features))
-    _check_points(points)
-    if radius.dim() != 1 or radius.size(0) != points.size(0):
-        raise RuntimeError("radius must be of shape (P,)")
-    if features.dim() != 2 or features.size(0) != points.size(0) or not 1 <= features.size(1) <= 4:
-        raise RuntimeError("features must be of shape (P, C) with C in 1..4")
-    K = int(points_per_pixel)
-    _check_k(K)
-    H, W = _hw(image_size)
-    bin_size, M = int(bin_size), int(max_points_per_bin)
-    binned = bin_size > 0 and M > 0
-    if binned:
-        _num_bins(H, W, bin_size, "RasterizeCoarseCuda")
-    pts, rad, feats = _c(points, torch.float32), _c(radius, torch.float32), _c(features, torch.float32)
-    first, count = _c(cloud_to_packed_first_idx, torch.int64), _c(num_points_per_cloud, torch.int64)
-    N, P, C = count.size(0), pts.size(0), feats.size(1)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = _point_outputs(N, H, W, K, dev)
-        images = torch.empty((N, H, W, C), dtype=torch.float32, device=dev)
-        if images.numel() == 0:
-            return out + (images,)
-        ws, need, need_at, entries = _mesh_workspace(lib, P, N, H, W, bin_size, M, dev, "points") if binned else (_workspace(0, dev), None, 0, None)
-        rc = lib.p3d_rasterize_points_composite(_SPLAT_MODES[mode], _ptr(pts), _ptr(first), _ptr(count), _ptr(rad), _ptr(feats), P, C, N, H, W, K,
-                                                bin_size if binned else 0, M if binned else 0, float(inv_r2), _ptr(out[0]), _ptr(out[1]),
-                                                _ptr(out[2]), _ptr(images), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "rasterize_points_composite")
-        if need is not None:
-            need.report_later(ws, need_at, entries)
+    """include/p3d_amd.h: p3d_rasterize_points_ex with images.  rasterize_points's arguments + features (P, C), C in 1..4, inv_r2
+    (inv_r2_of) and the compositor ("alpha" / "norm"); CUDA_TIE_ORDER does not apply.  Returns (idxs int32, zbuf, dists2, images
+    (N, H, W, C))."""
+    out, images = _rasterize_points("rasterize_points_composite", points, cloud_to_packed_first_idx, num_points_per_cloud, image_size,
+                                    radius, points_per_pixel, bin_size, max_points_per_bin, features, inv_r2, mode)
     return out + (images,)
 
 
 def rasterize_points_composite_backward(points, features, idxs, dists, grad_images, inv_r2, mode="alpha"):
     """include/p3d_amd.h: p3d_rasterize_points_composite_backward.  Returns (grad_points (P, 3), grad_features (P, C))."""
     dev = _same_device(("points", points), ("features", features), ("idxs", idxs), ("dists", dists), ("grad_images", grad_images))
-    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
-        raise RuntimeError("RasterizePointsBackwardCuda does not have a deterministic implementation")
+    _refuse_when_deterministic("RasterizePointsBackwardCuda")
     pts, feats = _c(points, torch.float32), _c(features, torch.float32)
     ix, ds, gi = _c(idxs, torch.int32), _c(dists, torch.float32), _c(grad_images, torch.float32)
     N, H, W, K = ix.shape
@@ -751,7 +736,7 @@ def _feature_layout(features):
     """(tensor to hand over, its (channel, point) element strides, interleaved?).  Two layouts go to the kernels as they are: the
     contiguous (C, P) tensor of the reference's operators, and the transposed view of a contiguous (P, C) tensor -- what
     PointsRenderer passes (renderer/points/renderer.py:67); there a point's channels are adjacent and the gathers of a pixel cost
-    one memory request per entry instead of C (include/p3d_amd.h: p3d_composite_forward_strided).  Anything else is copied."""
+    one memory request per entry instead of C (include/p3d_amd.h: p3d_composite_forward).  Anything else is copied."""
     C, P = features.shape
     st = features.stride()
     if C > 1 and P > 1 and st[0] == 1 and st[1] == C:
@@ -774,8 +759,8 @@ def _composite_forward(mode, name, features, alphas, points_idx):
         out = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
         if out.numel() == 0:
             return out
-        rc = lib.p3d_composite_forward_strided(mode, _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
-                                               _strides4(alphas), _strides4(points_idx), _ptr(out), _stream(dev))
+        rc = lib.p3d_composite_forward(mode, _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
+                                       _strides4(alphas), _strides4(points_idx), _ptr(out), _stream(dev))
         _lib.check(rc, name)
     return out
 
@@ -796,9 +781,8 @@ def _composite_backward(mode, name, grad_outputs, features, alphas, points_idx):
         else:
             gf = torch.empty((C, P), dtype=torch.float32, device=dev)
         ga = torch.empty((N, K, H, W), dtype=torch.float32, device=dev)
-        rc = lib.p3d_composite_backward_strided(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K,
-                                                H, W, _strides4(alphas), _strides4(points_idx), _ptr(gf), _strides2(fst), _ptr(ga),
-                                                _stream(dev))
+        rc = lib.p3d_composite_backward(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
+                                        _strides4(alphas), _strides4(points_idx), _ptr(gf), _strides2(fst), _ptr(ga), _stream(dev))
         _lib.check(rc, name)
     return gf, ga
 
@@ -869,8 +853,7 @@ def interp_face_attrs_backward(pix_to_face, barycentric_coords, face_attrs, grad
                        ("face_attributes", face_attrs), ("pix_attrs", grad_pix_attrs))
     if not (barycentric_coords.dtype == face_attrs.dtype == grad_pix_attrs.dtype) or face_attrs.dtype not in _DTYPES:
         raise RuntimeError("barycentric_coords, face_attributes and pix_attrs must have the same floating dtype")
-    if torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled():
-        raise RuntimeError("InterpFaceAttrsBackwardCuda does not have a deterministic implementation")
+    _refuse_when_deterministic("InterpFaceAttrsBackwardCuda")
     P = pix_to_face.size(0)
     if barycentric_coords.dim() != 2 or barycentric_coords.size(0) != P or barycentric_coords.size(1) != 3:
         raise RuntimeError("barycentric_coords must have size (P, 3)")

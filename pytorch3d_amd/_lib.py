@@ -18,9 +18,9 @@ c_f32 = ctypes.c_float
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 2  # P3D_ABI_VERSION of include/p3d_amd.h
+ABI_VERSION = 3  # P3D_ABI_VERSION of include/p3d_amd.h
 
-# flags of p3d_rasterize_meshes_ex / p3d_rasterize_meshes_backward_ex (include/p3d_amd.h)
+# flags of p3d_rasterize_meshes_ex, p3d_rasterize_points_ex (TIE_ORDER only) / p3d_rasterize_meshes_backward_ex (include/p3d_amd.h)
 RASTER_COVER_LIST = 1
 RASTER_CUDA_TIE_ORDER = 2
 BWD_COVER_HAS_LIST = 1
@@ -62,31 +62,25 @@ _SIGNATURES = {
     "p3d_rasterize_points_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
     "p3d_rasterize_points_short_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int, c_i64]),
     "p3d_rasterize_points_workspace_need_offset": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
+    "p3d_rasterize_points_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
+                                        c_ptr, c_int, c_ptr, c_int, c_f32, c_ptr, c_uint, c_ptr, c_size, c_ptr]),
     "p3d_rasterize_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr,
                                      c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_cuda_order": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr,
-                                                c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_rasterize_points_naive": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
                                            c_ptr, c_ptr]),
     "p3d_rasterize_points_coarse": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr,
                                             c_ptr, c_size, c_ptr]),
     "p3d_rasterize_points_fine": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_composite": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                               ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_rasterize_points_composite_backward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int,
                                                         ctypes.c_float, c_ptr, c_ptr, c_ptr]),
     "p3d_rasterize_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr,
                                               c_ptr]),
-    "p3d_composite_forward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int,
+    "p3d_composite_forward": (c_int, [c_int, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int,
                                       ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, c_ptr]),
-    "p3d_composite_backward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int,
-                                       ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, c_ptr, c_ptr]),
-    "p3d_composite_forward_strided": (c_int, [c_int, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int,
-                                              ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, c_ptr]),
-    "p3d_composite_backward_strided": (c_int, [c_int, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int,
-                                               c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, ctypes.POINTER(c_i64), c_ptr,
-                                               c_ptr]),
+    "p3d_composite_backward": (c_int, [c_int, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int,
+                                       c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, ctypes.POINTER(c_i64), c_ptr,
+                                       c_ptr]),
     "p3d_interp_face_attrs_forward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
     "p3d_interp_face_attrs_backward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr,
                                                c_ptr]),

@@ -291,8 +291,8 @@ Tensor composite_forward(int mode, const char* name, const Tensor& features, con
   if (out.numel() == 0) return out;
   const int64_t as[4] = {alphas.stride(0), alphas.stride(1), alphas.stride(2), alphas.stride(3)};
   const int64_t is[4] = {points_idx.stride(0), points_idx.stride(1), points_idx.stride(2), points_idx.stride(3)};
-  ok(p3d_composite_forward_strided(mode, feats.data_ptr<float>(), fst, alphas.data_ptr<float>(), points_idx.data_ptr<int64_t>(), N, C, P, K, H, W,
-                                   as, is, out.data_ptr<float>(), stream_of(feats)),
+  ok(p3d_composite_forward(mode, feats.data_ptr<float>(), fst, alphas.data_ptr<float>(), points_idx.data_ptr<int64_t>(), N, C, P, K, H, W, as,
+                           is, out.data_ptr<float>(), stream_of(feats)),
      name);
   return out;
 }
@@ -312,9 +312,8 @@ std::tuple<Tensor, Tensor> composite_backward(int mode, const char* name, const 
   auto ga = at::empty({N, K, H, W}, feats.options());
   const int64_t as[4] = {alphas.stride(0), alphas.stride(1), alphas.stride(2), alphas.stride(3)};
   const int64_t is[4] = {points_idx.stride(0), points_idx.stride(1), points_idx.stride(2), points_idx.stride(3)};
-  ok(p3d_composite_backward_strided(mode, go.data_ptr<float>(), feats.data_ptr<float>(), fst, alphas.data_ptr<float>(),
-                                    points_idx.data_ptr<int64_t>(), N, C, P, K, H, W, as, is, gf.data_ptr<float>(), fst, ga.data_ptr<float>(),
-                                    stream_of(feats)),
+  ok(p3d_composite_backward(mode, go.data_ptr<float>(), feats.data_ptr<float>(), fst, alphas.data_ptr<float>(), points_idx.data_ptr<int64_t>(),
+                            N, C, P, K, H, W, as, is, gf.data_ptr<float>(), fst, ga.data_ptr<float>(), stream_of(feats)),
      name);
   return {gf, ga};
 }

@@ -481,11 +481,13 @@ int launch_fwd(const CompArgs& a, unsigned grid, hipStream_t s) {
   return launch_status();
 }
 
-// The two feature layouts the kernels address (include/p3d_amd.h): (P, 1) planes or (1, C) rows.  A dimension of size 1 may
-// carry any stride -- but the kernels of K <= 16 read the layout off (fs0, fs1) themselves, so what is accepted is NORMALISED
-// to one of the two before the launch: a single channel (its P values contiguous) is one plane, a single point (its C values
-// contiguous) one row.  Anything else is refused, whatever K.
-bool feature_strides_ok(const int64_t st[2], int C, int64_t P, int64_t out[2]) {
+// The two feature layouts the kernels address (include/p3d_amd.h): (P, 1) planes or (1, C) rows; null strides: planes.  A
+// dimension of size 1 may carry any stride -- but the kernels of K <= 16 read the layout off (fs0, fs1) themselves, so what is
+// accepted is NORMALISED to one of the two before the launch: a single channel (its P values contiguous) is one plane, a single
+// point (its C values contiguous) one row.  Anything else is refused, whatever K.
+bool feature_strides_ok(const int64_t* st, int C, int64_t P, int64_t out[2]) {
+  const int64_t planes[2] = {P, 1};
+  if (st == nullptr) st = planes;
   const bool planar = (st[0] == P || C <= 1) && (st[1] == 1 || P <= 1);
   const bool rows = (st[0] == 1 || C <= 1) && (st[1] == C || P <= 1);
   if (!planar && !rows) return false;
@@ -531,14 +533,13 @@ unsigned pick_grid(int64_t npix) {
 
 using namespace p3d;
 
-P3D_API int p3d_composite_forward_strided(int mode, const float* features, const int64_t feature_strides[2], const float* alphas,
-                                          const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
-                                          const int64_t alphas_strides[4], const int64_t idx_strides[4], float* result,
-                                          p3d_stream_t stream) {
+P3D_API int p3d_composite_forward(int mode, const float* features, const int64_t feature_strides[2], const float* alphas,
+                                  const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
+                                  const int64_t alphas_strides[4], const int64_t idx_strides[4], float* result, p3d_stream_t stream) {
   if (mode < 0 || mode > 2 || N < 0 || C < 0 || K < 0 || H < 0 || W < 0 || P < 0) return P3D_ERR_INVALID_ARG;
   const int64_t nout = (int64_t)N * C * H * W;
   if (nout == 0) return P3D_OK;
-  if (!result || !alphas_strides || !idx_strides || !feature_strides) return P3D_ERR_INVALID_ARG;
+  if (!result || !alphas_strides || !idx_strides) return P3D_ERR_INVALID_ARG;
   int64_t fst[2];
   if (!feature_strides_ok(feature_strides, C, P, fst)) return P3D_ERR_INVALID_ARG;
   if (K > 0 && (!alphas || !points_idx || !features)) return P3D_ERR_INVALID_ARG;
@@ -571,20 +572,11 @@ P3D_API int p3d_composite_forward_strided(int mode, const float* features, const
   return launch_fwd<P3D_COMPOSITE_SUM>(a, grid, s);
 }
 
-P3D_API int p3d_composite_forward(int mode, const float* features, const float* alphas, const int64_t* points_idx, int N,
-                                  int C, int64_t P, int K, int H, int W, const int64_t alphas_strides[4],
-                                  const int64_t idx_strides[4], float* result, p3d_stream_t stream) {
-  const int64_t planar[2] = {P, 1};
-  return p3d_composite_forward_strided(mode, features, planar, alphas, points_idx, N, C, P, K, H, W, alphas_strides, idx_strides, result,
-                                       stream);
-}
-
-P3D_API int p3d_composite_backward_strided(int mode, const float* grad_outputs, const float* features, const int64_t feature_strides[2],
-                                           const float* alphas, const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
-                                           const int64_t alphas_strides[4], const int64_t idx_strides[4], float* grad_features,
-                                           const int64_t grad_feature_strides[2], float* grad_alphas, p3d_stream_t stream) {
+P3D_API int p3d_composite_backward(int mode, const float* grad_outputs, const float* features, const int64_t feature_strides[2],
+                                   const float* alphas, const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
+                                   const int64_t alphas_strides[4], const int64_t idx_strides[4], float* grad_features,
+                                   const int64_t grad_feature_strides[2], float* grad_alphas, p3d_stream_t stream) {
   if (mode < 0 || mode > 2 || N < 0 || C < 0 || K < 0 || H < 0 || W < 0 || P < 0) return P3D_ERR_INVALID_ARG;
-  if (!feature_strides || !grad_feature_strides) return P3D_ERR_INVALID_ARG;
   int64_t fst[2], gst[2];
   if (!feature_strides_ok(feature_strides, C, P, fst) || !feature_strides_ok(grad_feature_strides, C, P, gst)) return P3D_ERR_INVALID_ARG;
   // grad_features: C * P floats of ONE allocation in either layout ((P, 1) planes or (1, C) rows): zeroed as a block
@@ -632,13 +624,4 @@ P3D_API int p3d_composite_backward_strided(int mode, const float* grad_outputs, 
   if (mode == P3D_COMPOSITE_ALPHA) return launch_bwd<P3D_COMPOSITE_ALPHA>(a, grid, s);
   if (mode == P3D_COMPOSITE_NORM_SUM) return launch_bwd<P3D_COMPOSITE_NORM_SUM>(a, grid, s);
   return launch_bwd<P3D_COMPOSITE_SUM>(a, grid, s);
-}
-
-P3D_API int p3d_composite_backward(int mode, const float* grad_outputs, const float* features, const float* alphas,
-                                   const int64_t* points_idx, int N, int C, int64_t P, int K, int H, int W,
-                                   const int64_t alphas_strides[4], const int64_t idx_strides[4], float* grad_features,
-                                   float* grad_alphas, p3d_stream_t stream) {
-  const int64_t planar[2] = {P, 1};
-  return p3d_composite_backward_strided(mode, grad_outputs, features, planar, alphas, points_idx, N, C, P, K, H, W, alphas_strides,
-                                        idx_strides, grad_features, planar, grad_alphas, stream);
 }

@@ -37,7 +37,7 @@ struct PointArgs {
   // short workspaces (binning.h): the device flag "the lists did not fit", or null.  A binned launch returns at once when it
   // is up, the naive launch behind it returns at once when it is not (as in raster_mesh.hip: MeshArgs::overflow).
   const int* overflow;
-  // The compositor behind the fine stage (p3d_rasterize_points_composite; null features: plain rasterization).  PointsRenderer
+  // The compositor behind the fine stage (p3d_rasterize_points_ex with images; null features: plain rasterization).  PointsRenderer
   // (renderer/points/renderer.py:56-76) turns the fragments into weights = 1 - dists / r^2 and alpha-composites the points' features
   // front to back (alpha_composite.cu:24-68): when a pixel's K entries are final they are in the workgroup's LDS, so the pixel of the
   // image is formed there instead of by three more launches that read idx and dists back.
@@ -113,12 +113,13 @@ struct SplatPixel {
   }
 };
 
+// The naive launch (one list per image: every tile walks its cloud's whole range) with register queues, K <= kQueueMaxK.
 // PAYLOAD: the queue carries dist2 next to (z, idx).  Without it (long queues: 2 registers per entry instead of 3) the
 // distance is recomputed from the point's coordinates when the pixel is written -- the same two subtractions, two
 // products and one sum as in the test (rasterize_points.cu:55-60), so the same bits.
 // WAVES: minimum waves per SIMD the register allocation has to leave room for (512 / WAVES VGPRs per lane).
 // EXACTK: K == KT is known at compile time (the pair queues' insertion then has no test on K left).
-template <typename Queue, int KT, bool IN_REGS, bool BINNED, bool PAYLOAD = true, int WAVES = 2, bool EXACTK = false>
+template <typename Queue, int KT, bool PAYLOAD = true, int WAVES = 2, bool EXACTK = false>
 __global__ __launch_bounds__(kStage, WAVES) void point_raster_kernel(PointArgs a) {
   __shared__ float4 s_box[kStage];  // x-r, x+r, y-r, y+r
   __shared__ float4 s_pt[kStage];   // x, y, z, r*r
@@ -129,7 +130,7 @@ __global__ __launch_bounds__(kStage, WAVES) void point_raster_kernel(PointArgs a
   __shared__ ChunkOrderScratch s_ord;
   __shared__ int s_wcnt[kStage / kWave];
 
-  if (a.overflow != nullptr && (*a.overflow != 0) == BINNED) return;  // uniform (scalar load)
+  if (a.overflow != nullptr && *a.overflow == 0) return;  // uniform (scalar load): the stand-by of a binned launch whose lists fit
   TileCoord tc;
   if (!tile_of_block(a.tm, blockIdx.x, &tc)) return;
   const int n = tc.n, by = tc.by, bx = tc.bx, ty = tc.ty, tx = tc.tx;
@@ -163,16 +164,8 @@ __global__ __launch_bounds__(kStage, WAVES) void point_raster_kernel(PointArgs a
   const float sub_x0 = col_centre(min(sx0, x_end - 1)), sub_x1 = col_centre(max(min(sx0 + 8, x_end) - 1, tx0));
   const float sub_y0 = row_centre(min(sy0, y_end - 1)), sub_y1 = row_centre(max(min(sy0 + 8, y_end) - 1, ty0));
 
-  int64_t src_base;
-  int count;
-  if (BINNED) {
-    const int64_t row = ((int64_t)n * a.tm.BH + by) * a.tm.BW + bx;
-    src_base = a.csr.offset[row];
-    count = a.csr.total[row];
-  } else {
-    src_base = a.first[n];
-    count = (int)a.count[n];
-  }
+  const int64_t src_base = a.first[n];
+  const int count = (int)a.count[n];
 
   Queue q;
   q.init();
@@ -184,7 +177,7 @@ __global__ __launch_bounds__(kStage, WAVES) void point_raster_kernel(PointArgs a
     float px = 0.f, py = 0.f, pz = 0.f, r = 0.f;
     int pid = -1;
     if (i < count) {
-      pid = BINNED ? a.csr.list[(src_base + i) * a.csr.stride] : (int)(src_base + i);
+      pid = (int)(src_base + i);
       const float* g = a.points + (int64_t)pid * 3;
       px = g[0];
       py = g[1];
@@ -252,33 +245,24 @@ __global__ __launch_bounds__(kStage, WAVES) void point_raster_kernel(PointArgs a
 
   if (pix_ok) {
     const int64_t base = (((int64_t)n * H + (H - 1 - yi)) * W + (W - 1 - xi)) * K;
-    if constexpr (IN_REGS) {
 #pragma unroll
-      for (int k = 0; k < KT; ++k) {
-        if (k < K) {
-          const bool ok = q.valid(k);
-          a.idxs[base + k] = ok ? q.ix(k) : -1;
-          a.zbuf[base + k] = ok ? q.zf(k) : -1.0f;
-          if constexpr (PAYLOAD) {
-            a.dists[base + k] = ok ? q.pay(0, k) : -1.0f;
-          } else {
-            float d2 = -1.0f;
-            if (ok) {
-              const float* g = a.points + (int64_t)q.ix(k) * 3;
-              const float dx = xf - g[0];
-              const float dy = yf - g[1];
-              d2 = dx * dx + dy * dy;
-            }
-            a.dists[base + k] = d2;
-          }
-        }
-      }
-    } else {
-      for (int k = 0; k < K; ++k) {
+    for (int k = 0; k < KT; ++k) {
+      if (k < K) {
         const bool ok = q.valid(k);
         a.idxs[base + k] = ok ? q.ix(k) : -1;
         a.zbuf[base + k] = ok ? q.zf(k) : -1.0f;
-        a.dists[base + k] = ok ? q.pay(0, k) : -1.0f;
+        if constexpr (PAYLOAD) {
+          a.dists[base + k] = ok ? q.pay(0, k) : -1.0f;
+        } else {
+          float d2 = -1.0f;
+          if (ok) {
+            const float* g = a.points + (int64_t)q.ix(k) * 3;
+            const float dx = xf - g[0];
+            const float dy = yf - g[1];
+            d2 = dx * dx + dy * dy;
+          }
+          a.dists[base + k] = d2;
+        }
       }
     }
   }
@@ -746,7 +730,6 @@ __device__ __forceinline__ int tile_bucket_of(unsigned zbits, float zlo, float s
   return b < 0 ? 0 : (b > kStage - 1 ? kStage - 1 : b);
 }
 
-template <bool BINNED>
 __global__ __launch_bounds__(kStage, 2) void point_tile_sorted_kernel(PointArgs a) {
   extern __shared__ __align__(16) unsigned long long s_queues[];  // [wave][k][lane]
   __shared__ TileSortLds s_ts;
@@ -757,7 +740,7 @@ __global__ __launch_bounds__(kStage, 2) void point_tile_sorted_kernel(PointArgs 
   __shared__ int s_wcnt[kStage / kWave];
   __shared__ int s_cut[2];                      // [0] end of the chunk (list position), [1] largest bucket population of the tile
 
-  if (a.overflow != nullptr && (*a.overflow != 0) == BINNED) return;  // uniform (scalar load)
+  if (a.overflow != nullptr && *a.overflow != 0) return;  // uniform (scalar load): the lists did not fit
   TileCoord tc;
   if (!tile_of_block(a.tm, blockIdx.x, &tc)) return;
   const int n = tc.n, by = tc.by, bx = tc.bx, H = a.H, W = a.W, K = a.K;
@@ -779,21 +762,14 @@ __global__ __launch_bounds__(kStage, 2) void point_tile_sorted_kernel(PointArgs 
   const float sub_x0 = col_centre(min(sx0, x_end - 1)), sub_x1 = col_centre(max(min(sx0 + 8, x_end) - 1, tx0));
   const float sub_y0 = row_centre(min(sy0, y_end - 1)), sub_y1 = row_centre(max(min(sy0 + 8, y_end) - 1, ty0));
 
-  int64_t src_base;
-  int count;
-  if (BINNED) {
-    const int64_t row = ((int64_t)n * a.tm.BH + by) * a.tm.BW + bx;
-    src_base = a.csr.offset[row];
-    count = a.csr.total[row];
-  } else {
-    src_base = a.first[n];
-    count = (int)a.count[n];
-  }
+  const int64_t row = ((int64_t)n * a.tm.BH + by) * a.tm.BW + bx;
+  const int64_t src_base = a.csr.offset[row];
+  const int count = a.csr.total[row];
   unsigned long long* queue = s_queues + (size_t)w * K * kWave;
   int cnt = 0;
   unsigned long long kth = ~0ull;
   // the stream is in queue order (hits can be appended) while every chunk's keys sort after the previous chunk's
-  const bool sorted_list = BINNED && count <= kTileCap;
+  const bool sorted_list = count <= kTileCap;
   bool monotone = sorted_list;
   float zlo = 0.0f, scale = 0.0f;
   if (sorted_list && count > 0) {
@@ -834,7 +810,7 @@ __global__ __launch_bounds__(kStage, 2) void point_tile_sorted_kernel(PointArgs 
     float px = 0.f, py = 0.f, pz = 0.f, r = 0.f;
     int pid = -1;
     if (i < hi_pos) {
-      pid = !BINNED ? (int)(src_base + i) : (sorted_list ? s_ts.sorted[i] : a.csr.list[(src_base + i) * a.csr.stride]);
+      pid = sorted_list ? s_ts.sorted[i] : a.csr.list[(src_base + i) * a.csr.stride];
       const float* g = a.points + (int64_t)pid * 3;
       px = g[0];
       py = g[1];
@@ -1000,7 +976,7 @@ __global__ __launch_bounds__(kStage, 2) void point_tile_sorted_kernel(PointArgs 
   }
 }
 
-// The compositor as a pass of its own over finished fragments: what p3d_rasterize_points_composite launches behind the rasterizer
+// The compositor as a pass of its own over finished fragments: what p3d_rasterize_points_ex launches behind the rasterizer
 // kernels that do not carry it in their epilogue (K beyond the tile-sorted kernel, naive launches, short workspaces).
 __global__ __launch_bounds__(256) void splat_composite_kernel(PointArgs a) {
   // short workspaces: the binned kernel carried the compositor in its epilogue and wrote the image unless the lists did not fit
@@ -1027,15 +1003,14 @@ __global__ __launch_bounds__(256) void splat_composite_kernel(PointArgs a) {
 constexpr int kQueueMaxK = 16;
 
 #define P3D_COMMA ,
-template <bool BINNED>
 int launch_point_raster_queues(const PointArgs& a, hipStream_t stream) {
   const unsigned grid = tile_grid(a.tm);
-  LaunchScope ls(BINNED ? "points_fine" : "points_naive", stream);
+  LaunchScope ls("points_naive", stream);
   const int K = a.K;
   // The common capacities as payload-free pair queues with one 64-bit key compare per entry (topk.h: TopKPairs<KT, true, 0>;
   // the distance is recomputed at the store; staged depths are >= +0).  Other K take the register queue of the next capacity.
 #define P3D_PQ(KT_, WAVES_) \
-  point_raster_kernel<TopKPairs<KT_ P3D_COMMA true P3D_COMMA 0>, KT_, true, BINNED, false, WAVES_, true><<<grid, kStage, 0, stream>>>(a)
+  point_raster_kernel<TopKPairs<KT_ P3D_COMMA true P3D_COMMA 0>, KT_, false, WAVES_, true><<<grid, kStage, 0, stream>>>(a)
   switch (K) {
     case 8: P3D_PQ(8, 2); return launch_status();
     case 10: P3D_PQ(10, 2); return launch_status();
@@ -1044,19 +1019,19 @@ int launch_point_raster_queues(const PointArgs& a, hipStream_t stream) {
   }
 #undef P3D_PQ
   if (K == 1)
-    point_raster_kernel<TopKReg<1, 1>, 1, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<1, 1>, 1><<<grid, kStage, 0, stream>>>(a);
   else if (K == 2)
-    point_raster_kernel<TopKReg<2, 1>, 2, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<2, 1>, 2><<<grid, kStage, 0, stream>>>(a);
   else if (K <= 4)
-    point_raster_kernel<TopKReg<4, 1>, 4, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<4, 1>, 4><<<grid, kStage, 0, stream>>>(a);
   else if (K <= 8)
-    point_raster_kernel<TopKReg<8, 1>, 8, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<8, 1>, 8><<<grid, kStage, 0, stream>>>(a);
   else if (K <= 10)  // the insertion is the kernel's dominant VALU cost and scales with the queue length
-    point_raster_kernel<TopKReg<10, 1>, 10, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<10, 1>, 10><<<grid, kStage, 0, stream>>>(a);
   else if (K <= 12)
-    point_raster_kernel<TopKReg<12, 1>, 12, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<12, 1>, 12><<<grid, kStage, 0, stream>>>(a);
   else
-    point_raster_kernel<TopKReg<16, 1>, 16, true, BINNED><<<grid, kStage, 0, stream>>>(a);
+    point_raster_kernel<TopKReg<16, 1>, 16><<<grid, kStage, 0, stream>>>(a);
   return launch_status();
 }
 
@@ -1074,15 +1049,15 @@ int launch_point_raster(const PointArgs& a, hipStream_t stream) {
       LaunchScope ls("points_fine", stream);
       const size_t dyn = (size_t)(kStage / kWave) * a.K * kWave * sizeof(unsigned long long);
       if (dyn > 48 * 1024 &&
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&point_tile_sorted_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+          hipFuncSetAttribute(reinterpret_cast<const void*>(&point_tile_sorted_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)dyn) != hipSuccess)
         return P3D_ERR_LAUNCH;
-      point_tile_sorted_kernel<true><<<tile_grid(a.tm), kStage, dyn, stream>>>(a);
+      point_tile_sorted_kernel<<<tile_grid(a.tm), kStage, dyn, stream>>>(a);
       return launch_status();
     }
   }
   if constexpr (!BINNED) {
-    if (a.K <= kQueueMaxK) return launch_point_raster_queues<false>(a, stream);
+    if (a.K <= kQueueMaxK) return launch_point_raster_queues(a, stream);
   }
   const size_t grid = (size_t)tile_grid(a.tm) * 4;  // one single-wave workgroup per 8x8 sub-tile
   if (grid > 0x7fffffffull) return P3D_ERR_INVALID_ARG;
@@ -1102,7 +1077,7 @@ int launch_point_raster(const PointArgs& a, hipStream_t stream) {
 
 void set_tiles(PointArgs* a, int bin_size, int BH, int BW) { a->tm = make_tile_map(a->N, a->H, a->W, bin_size, BH, BW, true); }
 
-// CUDA tie order for points (p3d_rasterize_points_cuda_order; see raster_mesh.hip: mesh_cuda_order_kernel for the meshes).  The
+// CUDA tie order for points (P3D_RASTER_CUDA_TIE_ORDER; see raster_mesh.hip: mesh_cuda_order_kernel for the meshes).  The
 // reference's point kernels keep the same unsorted array as its mesh kernels (rasterize_points.cu:38-84) but sort it by depth
 // ALONE at the end (rasterize_points.cu:26-28, a stable bubble sort): where points tie exactly in depth both the survivors at the
 // K-th place and the order of the tied entries follow the array positions.  The replay below re-runs that procedure, points in
@@ -1110,7 +1085,7 @@ void set_tiles(PointArgs* a, int bin_size, int BH, int BW) { a->tm = make_tile_m
 // has dropped nothing and holds its hits in ascending (depth, index), which is the reference's arrival order.
 template <bool BINNED>
 __global__ __launch_bounds__(kStage) void point_cuda_order_kernel(PointArgs a) {
-  if (a.overflow != nullptr && (*a.overflow != 0) == BINNED) return;  // short workspaces: as in point_raster_kernel
+  if (a.overflow != nullptr && (*a.overflow != 0) == BINNED) return;  // short workspaces: as in point_sorted_kernel
   TileCoord tc;
   if (!tile_of_block(a.tm, blockIdx.x, &tc)) return;
   const int n = tc.n, H = a.H, W = a.W, K = a.K;
@@ -1301,6 +1276,114 @@ void fill_args(PointArgs* a, const float* points, const float* radius, int N, in
   a->dists = dists;
 }
 
+// The naive launch and its CUDA-order replay: every tile walks its cloud's whole range.  overflow set: the stand-by of a binned
+// launch with a short workspace, which writes only when the lists did not fit.
+PointArgs naive_args(PointArgs a, const int64_t* first, const int64_t* count, const int* overflow) {
+  a.first = first;
+  a.count = count;
+  a.overflow = overflow;
+  set_tiles(&a, a.H > a.W ? a.H : a.W, 1, 1);
+  return a;
+}
+
+template <bool BINNED>
+int launch_point_cuda_order(const PointArgs& a, hipStream_t s) {
+  LaunchScope ls("points_cuda_order", s);
+  point_cuda_order_kernel<BINNED><<<tile_grid(a.tm), kStage, 0, s>>>(a);
+  return launch_status();
+}
+
+// a.overflow: the device flag under which the pass runs (null: always)
+int launch_splat_composite(const PointArgs& a, hipStream_t s) {
+  const int64_t npix = (int64_t)a.N * a.H * a.W;
+  int64_t blocks = ceil_div(npix, 256);
+  if (blocks > 256 * 32) blocks = 256 * 32;
+  LaunchScope ls("points_composite", s);
+  splat_composite_kernel<<<(unsigned)blocks, 256, 0, s>>>(a);
+  return launch_status();
+}
+
+// p3d_rasterize_points_ex and the two reference-signature entries over it, straight through: (1) the arguments; (2) the naive
+// launch, or the binning and the binned launch, with the naive stand-by behind it when the workspace is short; (3) the replay of the
+// CUDA tie order; (4) the compositor wherever the tile-sorted kernel's epilogue did not form the image.
+int rasterize_points(const float* points, const int64_t* first, const int64_t* count, const float* radius, int64_t P, int N, int H,
+                     int W, int K, int bin_size, int max_points_per_bin, int32_t* idxs, float* zbuf, float* dists, int mode,
+                     const float* features, int C, float inv_r2, float* images, unsigned flags, void* workspace,
+                     size_t workspace_bytes, hipStream_t s) {
+  // (1) a compositing call (images given) checks C and the mode first and has work for every K: its image
+  const bool cuda_order = (flags & P3D_RASTER_CUDA_TIE_ORDER) != 0, splat = images != nullptr;
+  if ((flags & ~P3D_RASTER_CUDA_TIE_ORDER) != 0 || (cuda_order && splat)) return P3D_ERR_INVALID_ARG;
+  if (splat && (C < 1 || C > 4 || (mode != P3D_COMPOSITE_ALPHA && mode != P3D_COMPOSITE_NORM_SUM))) return P3D_ERR_INVALID_ARG;
+  const int rc = check_common(N, H, W, K);
+  if (rc != P3D_OK) return rc;
+  const int64_t npix = (int64_t)N * H * W;
+  if (npix * (splat ? 1 : K) == 0) return P3D_OK;
+  if (splat && P > 0 && !features) return P3D_ERR_INVALID_ARG;
+  // nothing to composite (K == 0: no fragments; P == 0: all of them empty): a black image
+  auto black = [&] { return hipMemsetAsync(images, 0, (size_t)npix * C * sizeof(float), s) == hipSuccess ? P3D_OK : P3D_ERR_LAUNCH; };
+  if (K == 0) return black();
+  if ((P > 0 && (!points || !radius)) || !first || !count || !idxs || !zbuf || !dists) return P3D_ERR_INVALID_ARG;
+  const bool composite = splat && P > 0;
+  PointArgs base{};
+  fill_args(&base, points, radius, N, H, W, K, idxs, zbuf, dists);
+  auto with_splat = [&](PointArgs a) {
+    a.features = features;
+    a.images = images;
+    a.C = C;
+    a.inv_r2 = inv_r2;
+    a.comp_mode = mode;
+    return a;
+  };
+
+  // (2)
+  const bool binned = bin_size > 0 && max_points_per_bin > 0;
+  PointArgs fine = base;
+  const int* overflow = nullptr;  // short workspaces: the device flag "the lists did not fit"
+  bool fused = false;             // the tile-sorted kernel forms the image in its epilogue (binned, K <= kTileSortedMaxK)
+  int st;
+  if (!binned) {
+    st = launch_point_raster<false>(naive_args(base, first, count, nullptr), s);
+  } else {
+    const BinGeom gu = make_geom(H, W, bin_size);
+    if (gu.BH > P3D_MAX_BINS_PER_SIDE || gu.BW > P3D_MAX_BINS_PER_SIDE) return P3D_ERR_TOO_MANY_BINS;
+    const BinGeom g = make_internal_geom(H, W, bin_size);  // tile-sized bins: results do not depend on the binning
+    Arena arena(workspace, workspace_bytes);
+    BinWorkspace ws;
+    // a short workspace is welcome here (binning.h): the list takes what the caller gave, and the naive kernel stands by
+    // (with_z: bin_fill leaves every entry's depth beside its id -- the tile-sorted kernel's depth sort reads them with the list)
+    if (!workspace || !bin_carve(arena, P, N, g, max_points_per_bin, &ws, /*list_entries=*/1, /*with_z=*/true)) return P3D_ERR_WORKSPACE;
+    if (ws.capacity < ws.worst) overflow = ws.plan_hdr + 2;
+    // the K nearest under (z, point index) do not depend on the order inside a bin: unordered fast binning (the replay of the
+    // CUDA tie order walks the lists in ascending index: ordered binning then)
+    st = bin_build(kPoints, points, radius, first, count, P, N, g, max_points_per_bin, 0.0f, ws, s, /*ordered=*/cuda_order);
+    if (st != P3D_OK) return st;
+    fine.csr = BinCSR{ws.offset, ws.total, ws.list, TilePlan{ws.arank, ws.bg_list, ws.plan_hdr, ws.order}, ws.stride};
+    fine.overflow = overflow;
+    set_tiles(&fine, g.bin_size, g.BH, g.BW);
+    fused = composite && K <= kTileSortedMaxK;
+    if (fused) fine = with_splat(fine);
+    st = launch_point_raster<true>(fine, s);
+    if (st == P3D_OK && overflow) st = launch_point_raster<false>(naive_args(base, first, count, overflow), s);
+  }
+  if (st != P3D_OK) return st;
+
+  // (3) over what the launches above wrote, under the same gating
+  if (cuda_order) {
+    if (!binned) return launch_point_cuda_order<false>(naive_args(base, first, count, nullptr), s);
+    st = launch_point_cuda_order<true>(fine, s);
+    if (st != P3D_OK || !overflow) return st;
+    return launch_point_cuda_order<false>(naive_args(base, first, count, overflow), s);
+  }
+
+  // (4) K > kTileSortedMaxK, naive launches, and behind the stand-by (gated by the same device flag)
+  if (!splat) return P3D_OK;
+  if (!composite) return black();
+  if (fused && !overflow) return P3D_OK;
+  PointArgs pass = with_splat(binned ? fine : base);
+  pass.overflow = fused ? overflow : nullptr;
+  return launch_splat_composite(pass, s);
+}
+
 }  // namespace
 }  // namespace p3d
 
@@ -1329,179 +1412,27 @@ P3D_API size_t p3d_rasterize_points_workspace_need_offset(int64_t P, int N, int 
   return ws.need_at;
 }
 
-P3D_API int p3d_rasterize_points_naive(const float* points, const int64_t* first, const int64_t* count,
-                                       const float* radius, int64_t P, int N, int H, int W, int K, int32_t* idxs,
-                                       float* zbuf, float* dists, p3d_stream_t stream) {
-  const int rc = check_common(N, H, W, K);
-  if (rc != P3D_OK) return rc;
-  if ((int64_t)N * H * W * K == 0) return P3D_OK;
-  if ((P > 0 && (!points || !radius)) || !first || !count || !idxs || !zbuf || !dists) return P3D_ERR_INVALID_ARG;
-  PointArgs a{};
-  fill_args(&a, points, radius, N, H, W, K, idxs, zbuf, dists);
-  a.first = first;
-  a.count = count;
-  set_tiles(&a, H > W ? H : W, 1, 1);
-  return launch_point_raster<false>(a, (hipStream_t)stream);
-}
-
-static int point_cuda_order_replay(const PointArgs& fine, bool binned, const int64_t* first, const int64_t* count,
-                                   const int* overflow, hipStream_t s) {
-  PointArgs a = fine;
-  a.overflow = overflow;
-  LaunchScope ls("points_cuda_order", s);
-  if (binned) {
-    point_cuda_order_kernel<true><<<tile_grid(a.tm), kStage, 0, s>>>(a);
-  } else {
-    a.first = first;
-    a.count = count;
-    set_tiles(&a, a.H > a.W ? a.H : a.W, 1, 1);
-    point_cuda_order_kernel<false><<<tile_grid(a.tm), kStage, 0, s>>>(a);
-  }
-  return launch_status();
-}
-
-struct SplatArgs {
-  const float* features;
-  float* images;
-  int C;
-  float inv_r2;
-  int mode;
-};
-
-// only_if: device flag; the pass runs when it is set (null: always)
-static int splat_composite_pass(const PointArgs& fine, const SplatArgs& sp, hipStream_t s, const int* only_if = nullptr) {
-  PointArgs a = fine;
-  a.overflow = only_if;
-  a.features = sp.features;
-  a.images = sp.images;
-  a.C = sp.C;
-  a.inv_r2 = sp.inv_r2;
-  a.comp_mode = sp.mode;
-  const int64_t npix = (int64_t)a.N * a.H * a.W;
-  int64_t blocks = ceil_div(npix, 256);
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  LaunchScope ls("points_composite", s);
-  splat_composite_kernel<<<(unsigned)blocks, 256, 0, s>>>(a);
-  return launch_status();
-}
-
-static int raster_points_impl(const float* points, const int64_t* first, const int64_t* count, const float* radius, int64_t P, int N,
-                              int H, int W, int K, int bin_size, int max_points_per_bin, int32_t* idxs, float* zbuf, float* dists,
-                              void* workspace, size_t workspace_bytes, p3d_stream_t stream, bool cuda_order,
-                              const SplatArgs* splat = nullptr) {
-  hipStream_t s = (hipStream_t)stream;
-  if (splat && (bin_size <= 0 || max_points_per_bin <= 0)) {
-    const int st = p3d_rasterize_points_naive(points, first, count, radius, P, N, H, W, K, idxs, zbuf, dists, stream);
-    if (st != P3D_OK || (int64_t)N * H * W == 0) return st;
-    PointArgs a{};
-    fill_args(&a, points, radius, N, H, W, K, idxs, zbuf, dists);
-    return splat_composite_pass(a, *splat, s);
-  }
-  if (bin_size <= 0 || max_points_per_bin <= 0) {
-    const int st = p3d_rasterize_points_naive(points, first, count, radius, P, N, H, W, K, idxs, zbuf, dists, stream);
-    if (st != P3D_OK || !cuda_order || (int64_t)N * H * W * K == 0) return st;
-    PointArgs a{};
-    fill_args(&a, points, radius, N, H, W, K, idxs, zbuf, dists);
-    return point_cuda_order_replay(a, false, first, count, nullptr, s);
-  }
-  const int rc = check_common(N, H, W, K);
-  if (rc != P3D_OK) return rc;
-  if ((int64_t)N * H * W * K == 0) return P3D_OK;
-  if ((P > 0 && (!points || !radius)) || !first || !count || !idxs || !zbuf || !dists) return P3D_ERR_INVALID_ARG;
-  const BinGeom gu = make_geom(H, W, bin_size);
-  if (gu.BH > P3D_MAX_BINS_PER_SIDE || gu.BW > P3D_MAX_BINS_PER_SIDE) return P3D_ERR_TOO_MANY_BINS;
-  const BinGeom g = make_internal_geom(H, W, bin_size);  // tile-sized bins: results do not depend on the binning
-  Arena arena(workspace, workspace_bytes);
-  BinWorkspace ws;
-  // a short workspace is welcome here (binning.h): the list takes what the caller gave, and the naive kernel stands by
-  // (with_z: bin_fill leaves every entry's depth beside its id -- the tile-sorted kernel's depth sort reads them with the list)
-  if (!workspace || !bin_carve(arena, P, N, g, max_points_per_bin, &ws, /*list_entries=*/1, /*with_z=*/true)) return P3D_ERR_WORKSPACE;
-  const bool is_short = ws.capacity < ws.worst;
-  const int* overflow = is_short ? ws.plan_hdr + 2 : nullptr;
-  // the K nearest under (z, point index) do not depend on the order inside a bin: unordered fast binning (the replay of the
-  // CUDA tie order walks the lists in ascending index: ordered binning then)
-  int st = bin_build(kPoints, points, radius, first, count, P, N, g, max_points_per_bin, 0.0f, ws, s, /*ordered=*/cuda_order);
-  if (st != P3D_OK) return st;
-  PointArgs a{};
-  fill_args(&a, points, radius, N, H, W, K, idxs, zbuf, dists);
-  a.csr = BinCSR{ws.offset, ws.total, ws.list, TilePlan{ws.arank, ws.bg_list, ws.plan_hdr, ws.order}, ws.stride};
-  a.overflow = overflow;
-  set_tiles(&a, g.bin_size, g.BH, g.BW);
-  // the compositor rides in the tile-sorted kernel's epilogue when that kernel writes every pixel; otherwise it is a pass behind
-  // (short workspaces: the binned kernel returns at once when its lists did not fit; the naive kernel then writes the fragments and the
-  // pass behind it, gated by the same device flag, the image)
-  const bool splat_fused = splat && !cuda_order && K <= kTileSortedMaxK;
-  if (splat_fused) {
-    a.features = splat->features;
-    a.images = splat->images;
-    a.C = splat->C;
-    a.inv_r2 = splat->inv_r2;
-    a.comp_mode = splat->mode;
-  }
-  st = launch_point_raster<true>(a, s);
-  if (splat) {
-    if (st == P3D_OK && is_short) {
-      PointArgs b{};
-      fill_args(&b, points, radius, N, H, W, K, idxs, zbuf, dists);
-      b.first = first;
-      b.count = count;
-      b.overflow = overflow;
-      set_tiles(&b, H > W ? H : W, 1, 1);
-      st = launch_point_raster<false>(b, s);
-    }
-    if (st != P3D_OK) return st;
-    if (splat_fused && !is_short) return st;
-    return splat_composite_pass(a, *splat, s, splat_fused ? overflow : nullptr);
-  }
-  if (st == P3D_OK && is_short) {
-    PointArgs b{};
-    fill_args(&b, points, radius, N, H, W, K, idxs, zbuf, dists);
-    b.first = first;
-    b.count = count;
-    b.overflow = overflow;
-    set_tiles(&b, H > W ? H : W, 1, 1);
-    st = launch_point_raster<false>(b, s);
-  }
-  if (st != P3D_OK || !cuda_order) return st;
-  st = point_cuda_order_replay(a, true, first, count, overflow, s);
-  if (st != P3D_OK || !is_short) return st;
-  return point_cuda_order_replay(a, false, first, count, overflow, s);
+P3D_API int p3d_rasterize_points_ex(const float* points, const int64_t* first, const int64_t* count, const float* radius, int64_t P,
+                                    int N, int H, int W, int K, int bin_size, int max_points_per_bin, int32_t* idxs, float* zbuf,
+                                    float* dists, int composite_mode, const float* features, int C, float inv_r2, float* images,
+                                    unsigned flags, void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
+  return rasterize_points(points, first, count, radius, P, N, H, W, K, bin_size, max_points_per_bin, idxs, zbuf, dists, composite_mode,
+                          features, C, inv_r2, images, flags, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 P3D_API int p3d_rasterize_points(const float* points, const int64_t* first, const int64_t* count, const float* radius,
                                  int64_t P, int N, int H, int W, int K, int bin_size, int max_points_per_bin,
                                  int32_t* idxs, float* zbuf, float* dists, void* workspace, size_t workspace_bytes,
                                  p3d_stream_t stream) {
-  return raster_points_impl(points, first, count, radius, P, N, H, W, K, bin_size, max_points_per_bin, idxs, zbuf, dists, workspace,
-                            workspace_bytes, stream, false);
+  return rasterize_points(points, first, count, radius, P, N, H, W, K, bin_size, max_points_per_bin, idxs, zbuf, dists, 0, nullptr, 0,
+                          0.0f, nullptr, 0, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-P3D_API int p3d_rasterize_points_composite(int mode, const float* points, const int64_t* first, const int64_t* count,
-                                           const float* radius, const float* features, int64_t P, int C, int N, int H, int W, int K,
-                                           int bin_size, int max_points_per_bin, float inv_r2, int32_t* idxs, float* zbuf, float* dists,
-                                           float* images, void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
-  if (C < 1 || C > 4 || (mode != P3D_COMPOSITE_ALPHA && mode != P3D_COMPOSITE_NORM_SUM)) return P3D_ERR_INVALID_ARG;
-  const int rc = check_common(N, H, W, K);
-  if (rc != P3D_OK) return rc;
-  if ((int64_t)N * H * W == 0) return P3D_OK;
-  if (!images || (P > 0 && !features)) return P3D_ERR_INVALID_ARG;
-  if (K == 0 || P == 0) {  // nothing to composite: the fragments (K > 0: all empty) and a black image
-    const int st = raster_points_impl(points, first, count, radius, P, N, H, W, K, bin_size, max_points_per_bin, idxs, zbuf, dists,
-                                      workspace, workspace_bytes, stream, false);
-    if (st != P3D_OK) return st;
-    return hipMemsetAsync(images, 0, (size_t)N * H * W * C * sizeof(float), (hipStream_t)stream) == hipSuccess ? P3D_OK : P3D_ERR_LAUNCH;
-  }
-  const SplatArgs sp{features, images, C, inv_r2, mode};
-  return raster_points_impl(points, first, count, radius, P, N, H, W, K, bin_size, max_points_per_bin, idxs, zbuf, dists, workspace,
-                            workspace_bytes, stream, false, &sp);
-}
-
-P3D_API int p3d_rasterize_points_cuda_order(const float* points, const int64_t* first, const int64_t* count, const float* radius,
-                                            int64_t P, int N, int H, int W, int K, int bin_size, int max_points_per_bin,
-                                            int32_t* idxs, float* zbuf, float* dists, void* workspace, size_t workspace_bytes,
-                                            p3d_stream_t stream) {
-  return raster_points_impl(points, first, count, radius, P, N, H, W, K, bin_size, max_points_per_bin, idxs, zbuf, dists, workspace,
-                            workspace_bytes, stream, true);
+P3D_API int p3d_rasterize_points_naive(const float* points, const int64_t* first, const int64_t* count,
+                                       const float* radius, int64_t P, int N, int H, int W, int K, int32_t* idxs,
+                                       float* zbuf, float* dists, p3d_stream_t stream) {
+  return rasterize_points(points, first, count, radius, P, N, H, W, K, 0, 0, idxs, zbuf, dists, 0, nullptr, 0, 0.0f, nullptr, 0,
+                          nullptr, 0, (hipStream_t)stream);
 }
 
 P3D_API int p3d_rasterize_points_coarse(const float* points, const int64_t* first, const int64_t* count,

@@ -1,5 +1,5 @@
 // render_points.hip -- the backward of PointsRenderer's chain as ONE kernel (round 6; forward: raster_points.hip,
-// p3d_rasterize_points_composite).
+// p3d_rasterize_points_ex with images).
 //
 // The chain (pytorch3d/renderer/points/renderer.py:56-76): fragments = rasterize_points(...); weights = 1 - dists / r^2;
 // images = alpha_composite(idx, weights, features).  Its backward in the reference is alphaCompositeCudaBackwardKernel

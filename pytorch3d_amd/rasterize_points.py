@@ -24,6 +24,20 @@ def default_bin_size(longest_side: int) -> int:
     return 1 << max(int(math.ceil(math.log2(longest_side))) - 4, 4)
 
 
+def _bins(size, bin_size, max_points_per_bin, num_points):
+    """rasterize_points.py:104-125: the defaults of bin_size and max_points_per_bin, and the bin-count check."""
+    longest = max(size)
+    if bin_size is None:
+        bin_size = default_bin_size(longest)
+    if bin_size != 0:
+        bins = 1 + (longest - 1) // bin_size
+        if bins >= MAX_BINS_PER_SIDE:
+            raise ValueError("bin_size too small, number of points per bin must be less than %d; got %d" % (MAX_BINS_PER_SIDE, bins))
+    if max_points_per_bin is None:
+        max_points_per_bin = max(10000, num_points // 5)  # rasterize_points.py:125
+    return bin_size, max_points_per_bin
+
+
 def radius_per_packed_point(radius: Radius, clouds) -> torch.Tensor:
     """One float32 radius per packed point, on the points' device.
 
@@ -57,15 +71,7 @@ def rasterize_points(pointclouds, image_size: Union[int, Sequence[int]] = 256, r
                      points_per_pixel: int = 8, bin_size: Optional[int] = None,
                      max_points_per_bin: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     size = parse_image_size(image_size)
-    longest = max(size)
-    if bin_size is None:
-        bin_size = default_bin_size(longest)
-    if bin_size != 0:
-        bins = 1 + (longest - 1) // bin_size
-        if bins >= MAX_BINS_PER_SIDE:
-            raise ValueError("bin_size too small, number of points per bin must be less than %d; got %d" % (MAX_BINS_PER_SIDE, bins))
-    if max_points_per_bin is None:
-        max_points_per_bin = max(10000, pointclouds._P // 5)  # rasterize_points.py:125
+    bin_size, max_points_per_bin = _bins(size, bin_size, max_points_per_bin, pointclouds._P)
     return _PointFragments.apply(pointclouds.points_packed(), radius_per_packed_point(radius, pointclouds),
                                  pointclouds.cloud_to_packed_first_idx(), pointclouds.num_points_per_cloud(),
                                  (size, int(points_per_pixel), int(bin_size), int(max_points_per_bin)))

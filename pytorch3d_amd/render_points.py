@@ -3,7 +3,7 @@ node on two launches.
 
 The reference (pytorch3d/renderer/points/renderer.py:56-76) runs the rasterizer, two element-wise kernels, two permuted copies and the
 compositor, and in the backward the compositor's backward, the element-wise backwards and the rasterizer's backward.  Here the pixel of
-the image is formed in the fine kernel's epilogue (include/p3d_amd.h: p3d_rasterize_points_composite) and the backward is one kernel
+the image is formed in the fine kernel's epilogue (include/p3d_amd.h: p3d_rasterize_points_ex) and the backward is one kernel
 whose two scatters share a table (p3d_rasterize_points_composite_backward).  Same bits in the image as the operators one after the
 other; gradients within the compositor's and the rasterizer's own tolerances (tests/test_gpu_render_points.py).
 
@@ -16,7 +16,7 @@ import torch
 
 from . import _C
 from .rasterize_meshes import parse_image_size
-from .rasterize_points import MAX_BINS_PER_SIDE, default_bin_size, radius_per_packed_point
+from .rasterize_points import _bins, radius_per_packed_point
 
 MAX_FUSED_K = 16  # include/p3d_amd.h: p3d_rasterize_points_composite_backward
 MAX_FUSED_C = 4
@@ -44,15 +44,7 @@ def render_points_alpha(pointclouds, features_packed, image_size: Union[int, Seq
     if compositor not in ("alpha", "norm"):
         raise ValueError("compositor must be 'alpha' or 'norm'")
     size = parse_image_size(image_size)
-    longest = max(size)
-    if bin_size is None:
-        bin_size = default_bin_size(longest)
-    if bin_size != 0:
-        bins = 1 + (longest - 1) // bin_size
-        if bins >= MAX_BINS_PER_SIDE:
-            raise ValueError("bin_size too small, number of points per bin must be less than %d; got %d" % (MAX_BINS_PER_SIDE, bins))
-    if max_points_per_bin is None:
-        max_points_per_bin = max(10000, pointclouds._P // 5)  # rasterize_points.py:125
+    bin_size, max_points_per_bin = _bins(size, bin_size, max_points_per_bin, pointclouds._P)
     if not fusable(features_packed, radius if weight_radius is None else weight_radius, points_per_pixel):
         raise ValueError("render_points_alpha: float32 (P, C <= 4) GPU features, a scalar radius and points_per_pixel <= 16")
     rad = radius_per_point if radius_per_point is not None else radius_per_packed_point(radius, pointclouds)

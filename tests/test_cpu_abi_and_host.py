@@ -27,18 +27,21 @@ def _declared():
     return sorted(set(re.findall(r"\b(p3d_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_declares_the_operator_surface():
+def test_abi_v3_header_declares_the_operator_surface():
     names = _declared()
     for want in ("p3d_rasterize_meshes", "p3d_rasterize_meshes_naive", "p3d_rasterize_meshes_coarse",
                  "p3d_rasterize_meshes_fine", "p3d_rasterize_meshes_backward", "p3d_rasterize_points",
                  "p3d_rasterize_points_naive", "p3d_rasterize_points_coarse", "p3d_rasterize_points_fine",
-                 "p3d_rasterize_points_backward", "p3d_composite_forward", "p3d_composite_backward", "p3d_composite_forward_strided",
-                 "p3d_composite_backward_strided",
+                 "p3d_rasterize_points_ex", "p3d_rasterize_points_backward", "p3d_composite_forward", "p3d_composite_backward",
                  "p3d_interp_face_attrs_forward", "p3d_interp_face_attrs_backward", "p3d_sigmoid_alpha_blend_forward",
                  "p3d_sigmoid_alpha_blend_backward", "p3d_softmax_rgb_blend_forward", "p3d_softmax_rgb_blend_backward",
                  "p3d_gather_face_verts", "p3d_scatter_face_grads", "p3d_clip_faces_plan", "p3d_clip_faces_emit",
                  "p3d_clip_faces_backward", "p3d_convert_clipped_forward", "p3d_convert_clipped_backward"):
         assert want in names
+    # ABI 3 folded these into p3d_rasterize_points_ex and into the compositors' feature strides
+    for gone in ("p3d_rasterize_points_cuda_order", "p3d_rasterize_points_composite", "p3d_composite_forward_strided",
+                 "p3d_composite_backward_strided"):
+        assert gone not in names
 
 
 def test_library_exports_every_declared_symbol():
@@ -60,11 +63,11 @@ def test_library_contains_gfx950_code_object():
     assert b"gfx950" in blob and b"mesh_raster_kernel" in blob
 
 
-def test_abi_v2_library_loads_and_answers_without_a_device():
+def test_abi_v3_library_loads_and_answers_without_a_device():
     from pytorch3d_amd import _lib
 
     lib = _lib.load()
-    assert lib.p3d_abi_version() == 2
+    assert lib.p3d_abi_version() == 3
     assert b"150" in lib.p3d_error_string(-2) or b"K" in lib.p3d_error_string(-2)
     assert lib.p3d_error_string(0)
     # workspace sizing is pure host arithmetic
@@ -142,6 +145,49 @@ def test_mesh_ex_entries_validate_before_any_launch():
     assert bwd(0, 0, null, some, _lib.BWD_MAKE_FACE_PRE | _lib.BWD_COVER_HAS_LIST) == 0  # F == 0: grad_face_verts is empty
     assert bwd(10, 0, some, some, 0) == 0  # V == 0: grad_verts is empty
     assert bwd(10, 0, null, null, 0) == -1  # F > 0 per face: the output is missing
+
+
+def test_points_ex_entry_validates_before_any_launch():
+    """p3d_rasterize_points_ex and the compositors: the checks that precede any device work, with null pointers."""
+    from pytorch3d_amd import _lib
+
+    lib = _lib.load()
+    null = ctypes.c_void_p(None)
+    some = ctypes.c_void_p(4096)  # never dereferenced: every call below returns before it would touch the device
+    COVER_LIST, TIE = _lib.RASTER_COVER_LIST, _lib.RASTER_CUDA_TIE_ORDER
+
+    def fwd(N, H, W, K, flags=0, images=null, C=3, mode=0, P=0, features=null, ptr=null, bins=(0, 0)):
+        return lib.p3d_rasterize_points_ex(ptr, ptr, ptr, ptr, P, N, H, W, K, *bins, ptr, ptr, ptr, mode, features, C, 1.0, images, flags,
+                                           null, 0, null)
+
+    assert fwd(1, 8, 8, 151) == -2 and fwd(1, 8, 8, 151, images=some) == -2  # K > 150
+    assert fwd(-1, 8, 8, 4) == -1 and fwd(1, -8, 8, 4) == -1 and fwd(1, 8, -8, 4) == -1 and fwd(1, 8, 8, -4) == -1
+    assert fwd(1, 8, 8, 4, flags=4) == -1  # unknown flag bit
+    assert fwd(0, 8, 8, 4, flags=COVER_LIST) == -1  # the meshes' flag
+    assert fwd(0, 8, 8, 4, flags=TIE, images=some) == -1  # no caller reaches this combination
+    # with images: C outside 1..4 or a bad mode, checked before the sizes; without images C and the mode are ignored
+    for C, mode in ((0, 0), (5, 0), (3, 2), (3, -1)):
+        assert fwd(0, 8, 8, 4, images=some, C=C, mode=mode) == -1 and fwd(1, 8, 8, 151, images=some, C=C, mode=mode) == -1
+        assert fwd(0, 8, 8, 4, C=C, mode=mode) == 0
+    assert fwd(1, 8, 8, 4, images=some, P=10) == -1  # points but no features
+    # empty problems return OK; null outputs of a non-empty one do not
+    assert fwd(0, 8, 8, 4) == 0 and fwd(1, 0, 8, 4) == 0 and fwd(1, 8, 8, 0) == 0 and fwd(0, 8, 8, 4, flags=TIE) == 0
+    assert fwd(0, 8, 8, 4, images=some, P=10, features=some) == 0 and fwd(1, 8, 0, 4, images=some) == 0
+    assert fwd(1, 8, 8, 4) == -1 and fwd(1, 8, 8, 4, flags=TIE) == -1 and fwd(1, 8, 8, 4, images=some) == -1
+    # binned: too many bins, then the workspace
+    assert fwd(1, 64, 64, 4, ptr=some, bins=(2, 10)) == -3 and fwd(1, 64, 64, 4, ptr=some, bins=(16, 10)) == -4
+    # the reference-signature entries check the same way
+    assert lib.p3d_rasterize_points(null, null, null, null, 0, 1, 8, 8, 151, 0, 0, null, null, null, null, 0, null) == -2
+    assert lib.p3d_rasterize_points_naive(null, null, null, null, 0, 1, 8, 8, 151, null, null, null, null) == -2
+    assert lib.p3d_rasterize_points_naive(null, null, null, null, 0, 0, 8, 8, 4, null, null, null, null) == 0
+
+    # the compositors take (P, 1) planes, (1, C) rows or null (planes) as feature strides, nothing else
+    i64 = lambda *v: (ctypes.c_int64 * len(v))(*v)
+    st4 = i64(0, 0, 0, 0)
+    for bad in (i64(20, 2), i64(1, 1), i64(10, 3)):  # C = 3, P = 10
+        assert lib.p3d_composite_forward(0, some, bad, some, some, 1, 3, 10, 2, 4, 4, st4, st4, some, null) == -1
+        assert lib.p3d_composite_backward(0, some, some, bad, some, some, 1, 3, 10, 2, 4, 4, st4, st4, some, None, some, null) == -1
+        assert lib.p3d_composite_backward(0, some, some, None, some, some, 1, 3, 10, 2, 4, 4, st4, st4, some, bad, some, null) == -1
 
 
 def test_stale_library_fails_in_load(monkeypatch):

@@ -1,5 +1,5 @@
-"""GPU parity: PointsRenderer's chain as two launches (include/p3d_amd.h: p3d_rasterize_points_composite, _composite_backward;
-pytorch3d_amd.render_points) against
+"""GPU parity: PointsRenderer's chain as two launches (include/p3d_amd.h: p3d_rasterize_points_ex with images and
+p3d_rasterize_points_composite_backward; pytorch3d_amd.render_points) against
   * the C oracle's rasterize_points_naive + composite_forward on `weights = 1 - dists / r^2` (renderer/points/renderer.py:56-76):
     fragments and image bit-exact;
   * the package's own operators run one after the other (each pinned to the oracle in test_gpu_points_composite_interp.py): image
