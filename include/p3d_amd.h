@@ -522,6 +522,27 @@ int p3d_hard_rgb_blend_forward(const float* colors, const int64_t* pix_to_face, 
 int p3d_hard_rgb_blend_backward(const float* grad_out, const int64_t* pix_to_face, int64_t npix, int K, float* grad_colors,
                                 p3d_stream_t stream);
 
+/* replace HardDepthShader.forward / SoftDepthShader.forward (pytorch3d/renderer/mesh/shader.py:377-445).  Fragment rows
+ * (npix,K) as above: dists, zbuf f32, pix_to_face i64; 1 <= K <= 150 (P3D_ERR_K_TOO_LARGE above, P3D_ERR_INVALID_ARG below);
+ * rows that are a multiple of 16 bytes must start 16-byte aligned; depth / grad_depth (npix) f32; zfar one number; npix == 0
+ * is a no-op.  One launch each, no atomics: bit-identical from run to run.
+ *   hard: depth = pix_to_face[.,0] >= 0 ? zbuf[.,0] : zfar.  Backward: grad_zbuf (npix,K) fully written -- grad_depth in
+ *   slot 0 of covered pixels, zero elsewhere.
+ *   soft (sigma > 0): p_k = pix_to_face_k >= 0 ? sigmoid(-dists_k / sigma) : 0, c_k = p_0 + .. + p_k as a running float sum in
+ *   slot order, C_k = min(c_k, 1), w_k = C_k - C_{k-1}, depth = sum_k w_k zbuf_k + (1 - C_{K-1}) zfar; the slots are taken
+ *   in their stored order, sorted or not.  Backward: grad_zbuf_k = g w_k; grad_dists_j = -g p_j (1 - p_j) / sigma * sum over
+ *   k >= j with c_k <= 1 of (zbuf_k - zbuf_{k+1}), zbuf_K := zfar, zero where pix_to_face_j < 0.  A null grad_dists or
+ *   grad_zbuf is not wanted and not written; the other one is fully written. */
+int p3d_soft_depth_blend_forward(const float* dists, const float* zbuf, const int64_t* pix_to_face, float sigma, float zfar,
+                                 int64_t npix, int K, float* depth, p3d_stream_t stream);
+int p3d_soft_depth_blend_backward(const float* grad_depth, const float* dists, const float* zbuf, const int64_t* pix_to_face,
+                                  float sigma, float zfar, int64_t npix, int K, float* grad_dists, float* grad_zbuf,
+                                  p3d_stream_t stream);
+int p3d_hard_depth_blend_forward(const float* zbuf, const int64_t* pix_to_face, float zfar, int64_t npix, int K, float* depth,
+                                 p3d_stream_t stream);
+int p3d_hard_depth_blend_backward(const float* grad_depth, const int64_t* pix_to_face, int64_t npix, int K, float* grad_zbuf,
+                                  p3d_stream_t stream);
+
 /* ---- SplatterPhongShader's blend ------------------------------------------------------------------------------------
  *
  * replaces SplatterBlender.forward (pytorch3d/renderer/splatter_blend.py) after its camera call: masking, the 9-direction

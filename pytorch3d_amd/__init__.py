@@ -8,12 +8,14 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     clip_faces, softmax_rgb_blend, sigmoid_alpha_blend, hard_rgb_blend, phong_shading, sample_textures_uv,
     sample_textures_atlas            the neighbouring steps, fused
     splatter_blend, SplatterBlender  SplatterPhongShader's blend, fused
+    hard_depth_blend, soft_depth_blend  HardDepthShader's / SoftDepthShader's depth maps, one kernel each way
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
 """
 from . import _C  # noqa: F401
-from .blending import BlendParams, hard_rgb_blend, sigmoid_alpha_blend, softmax_rgb_blend  # noqa: F401
+from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_alpha_blend, soft_depth_blend,  # noqa: F401
+                       softmax_rgb_blend)
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401

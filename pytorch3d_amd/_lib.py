@@ -126,6 +126,10 @@ _SIGNATURES = {
     "p3d_sample_atlas_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
     "p3d_hard_rgb_blend_forward": (c_int, [c_ptr, c_ptr, ctypes.POINTER(c_f32), c_i64, c_int, c_ptr, c_ptr]),
     "p3d_hard_rgb_blend_backward": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
+    "p3d_soft_depth_blend_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_i64, c_int, c_ptr, c_ptr]),
+    "p3d_soft_depth_blend_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
+    "p3d_hard_depth_blend_forward": (c_int, [c_ptr, c_ptr, c_f32, c_i64, c_int, c_ptr, c_ptr]),
+    "p3d_hard_depth_blend_backward": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
     "p3d_splatter_blend_backward_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "p3d_splatter_blend_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_f32, ctypes.POINTER(c_f32), c_int, c_int, c_int, c_int,
                                            c_ptr, c_ptr]),

@@ -6,6 +6,9 @@
 reference's wrapper (blending.py:95-140).  `softmax_rgb_blend`, ~20 elementwise torch ops plus their autograd
 graph in the reference (blending.py:147-244), is ONE kernel forward and ONE backward here
 (include/p3d_amd.h: p3d_softmax_rgb_blend_forward / _backward); same arguments, defaults and return value.
+
+`hard_depth_blend` / `soft_depth_blend` are the bodies of HardDepthShader.forward / SoftDepthShader.forward
+(renderer/mesh/shader.py:377-445) after their camera lookup, one kernel each way as well.
 """
 import ctypes
 from typing import NamedTuple, Sequence, Union
@@ -166,3 +169,119 @@ def hard_rgb_blend(colors, fragments, blend_params: BlendParams) -> torch.Tensor
     if colors.shape != tuple(fragments.pix_to_face.shape) + (3,) or fragments.pix_to_face.shape[3] < 1:
         raise ValueError("colors must have shape (N, H, W, K, 3) with K >= 1 matching pix_to_face")
     return _HardRGBBlend.apply(colors, fragments.pix_to_face, _background(blend_params, colors.device, "hard_rgb_blend"))
+
+
+def _depth_zfar(zfar, who):
+    """The depth shaders' far plane: a Python number or a one-element tensor that does not require grad (the reference's
+    own forwards raise a shape error for anything longer; a gradient to zfar is not computed).  A device tensor is read
+    back once per call."""
+    if torch.is_tensor(zfar):
+        if zfar.numel() != 1 or zfar.requires_grad:
+            raise ValueError(who + ": zfar must be a number or a one-element tensor that does not require grad")
+        return float(zfar.detach().reshape(()).item())
+    if isinstance(zfar, bool) or not isinstance(zfar, (int, float)):
+        raise ValueError(who + ": zfar must be a number or a one-element tensor that does not require grad")
+    return float(zfar)
+
+
+def _check_depth_fragments(who, fragments, with_dists):
+    floats = {"zbuf": fragments.zbuf}
+    if with_dists:
+        floats["dists"] = fragments.dists
+    _C._check_fragments(who, fragments.pix_to_face, **floats)
+    shape = tuple(fragments.pix_to_face.shape)
+    if len(shape) != 4 or shape[3] < 1:
+        raise ValueError(who + ": pix_to_face must have shape (N, H, W, K) with K >= 1")
+    if shape[3] > _C.kMaxPointsPerPixel:
+        raise ValueError(f"{who}: K must be at most {_C.kMaxPointsPerPixel}")
+    for name, t in floats.items():
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{who}: {name} must have the shape of pix_to_face {shape}; got {tuple(t.shape)}")
+
+
+class _SoftDepthBlend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, dists, zbuf, pix_to_face, sigma, zfar):
+        N, H, W, K = pix_to_face.shape
+        dev = zbuf.device
+        d, z, p2f = dists.contiguous(), zbuf.contiguous(), pix_to_face.contiguous()
+        with torch.cuda.device(dev):
+            out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
+            if out.numel():
+                rc = _lib.load().p3d_soft_depth_blend_forward(_C._ptr(d), _C._ptr(z), _C._ptr(p2f), sigma, zfar, N * H * W, K,
+                                                              _C._ptr(out), _C._stream(dev))
+                _lib.check(rc, "soft_depth_blend")
+        ctx.save_for_backward(d, z, p2f)
+        ctx.params = (sigma, zfar)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_depth):
+        if grad_depth is None:
+            return None, None, None, None, None
+        d, z, p2f = ctx.saved_tensors
+        sigma, zfar = ctx.params
+        N, H, W, K = p2f.shape
+        dev = z.device
+        g = grad_depth.contiguous()
+        with torch.cuda.device(dev):
+            gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+            gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+            if p2f.numel() and (gd is not None or gz is not None):
+                rc = _lib.load().p3d_soft_depth_blend_backward(_C._ptr(g), _C._ptr(d), _C._ptr(z), _C._ptr(p2f), sigma, zfar,
+                                                               N * H * W, K, _C._ptr(gd), _C._ptr(gz), _C._stream(dev))
+                _lib.check(rc, "soft_depth_blend_backward")
+        return gd, gz, None, None, None
+
+
+def soft_depth_blend(fragments, blend_params: BlendParams, zfar: Union[float, torch.Tensor] = 100.0) -> torch.Tensor:
+    """SoftDepthShader.forward (shader.py:419-445) after its camera lookup: the depths of a pixel's K slots weighted by the
+    clamped running sum of their sigmoid(-dists / sigma) probabilities, zfar taking what is left of 1.  One kernel each way
+    (p3d_soft_depth_blend_forward / _backward).  fragments.{pix_to_face, zbuf, dists} (N,H,W,K) -> depth (N,H,W,1)."""
+    if fragments.dists is None:
+        raise ValueError("SoftDepthShader requires Fragments.dists to be present.")
+    _check_depth_fragments("soft_depth_blend", fragments, True)
+    sigma = float(blend_params.sigma)
+    if not sigma > 0.0:
+        raise ValueError("soft_depth_blend: blend_params.sigma must be positive")
+    return _SoftDepthBlend.apply(fragments.dists, fragments.zbuf, fragments.pix_to_face, sigma, _depth_zfar(zfar, "soft_depth_blend"))
+
+
+class _HardDepthBlend(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, zbuf, pix_to_face, zfar):
+        N, H, W, K = pix_to_face.shape
+        dev = zbuf.device
+        z, p2f = zbuf.contiguous(), pix_to_face.contiguous()
+        with torch.cuda.device(dev):
+            out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
+            if out.numel():
+                rc = _lib.load().p3d_hard_depth_blend_forward(_C._ptr(z), _C._ptr(p2f), zfar, N * H * W, K, _C._ptr(out),
+                                                              _C._stream(dev))
+                _lib.check(rc, "hard_depth_blend")
+        ctx.save_for_backward(p2f)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_depth):
+        if grad_depth is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        (p2f,) = ctx.saved_tensors
+        N, H, W, K = p2f.shape
+        dev = p2f.device
+        g = grad_depth.contiguous()
+        with torch.cuda.device(dev):
+            gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+            if gz.numel():
+                rc = _lib.load().p3d_hard_depth_blend_backward(_C._ptr(g), _C._ptr(p2f), N * H * W, K, _C._ptr(gz), _C._stream(dev))
+                _lib.check(rc, "hard_depth_blend_backward")
+        return gz, None, None
+
+
+def hard_depth_blend(fragments, zfar: Union[float, torch.Tensor] = 100.0) -> torch.Tensor:
+    """HardDepthShader.forward (shader.py:392-400) after its camera lookup: zbuf[..., 0] where slot 0 holds a face, zfar
+    elsewhere.  One kernel each way (p3d_hard_depth_blend_forward / _backward).  -> depth (N,H,W,1)."""
+    _check_depth_fragments("hard_depth_blend", fragments, False)
+    return _HardDepthBlend.apply(fragments.zbuf, fragments.pix_to_face, _depth_zfar(zfar, "hard_depth_blend"))

@@ -4,6 +4,8 @@
 //       (pytorch3d/csrc/blending/sigmoid_alpha_blend.cu:16-67, 109-166; `pytorch3d._C.sigmoid_alpha_blend[_backward]`)
 //   softmax_rgb_blend forward / backward    replaces ~20 elementwise torch ops over (N,H,W,K) tensors
 //       (pytorch3d/renderer/blending.py:147-244) and their autograd graph with one streaming kernel each.
+//   soft_depth / hard_depth forward / backward  replace SoftDepthShader.forward / HardDepthShader.forward
+//       (pytorch3d/renderer/mesh/shader.py:377-445): 16 B per (pixel, k), see the section below.
 //
 // All four are pure HBM streams: one lane per pixel reads its K-rows of pix_to_face / dists / zbuf / colors
 // with 16-byte loads (28 B per (pixel, k)), keeps everything in registers and writes each output once.
@@ -470,6 +472,195 @@ int blend_capacity(int K) { return K <= 1 ? 1 : K <= 2 ? 2 : K <= 4 ? 4 : K <= 8
     default: GENERIC<<<grid, kBlendBlock, 0, s>>>(__VA_ARGS__); break;                                   \
   }
 
+
+// ---- depth shaders (pytorch3d/renderer/mesh/shader.py:377-445) --------------------------------------------------------
+// SoftDepthShader: p_k = sigmoid(-d_k / sigma) on covered slots, c_k their running float sum in slot order (torch.cumsum),
+// C_k = min(c_k, 1), w_k = C_k - C_{k-1}, depth = sum_k w_k z_k + (1 - C_{K-1}) zfar.  The reference builds this from a
+// dozen (N,H,W,K+1) tensors; here one lane per pixel streams its three K-rows (16 B per slot) and keeps the rest in
+// registers.  The probabilities are >= 0, so the float32 running sum never decreases and [c_k <= 1] (where torch's clamp
+// passes the gradient, equality included) holds on a PREFIX of the row: `kcut` = its length is all the backward keeps.
+//   grad_z_k = g w_k,  grad_d_j = m_j g s_j (-p_j (1 - p_j) / sigma),  s_j = sum_{k = j .. kcut-1} (z_k - z_{k+1}),  z_K = zfar.
+// z_k is the stored value of empty slots as well (the terms telescope exactly as the reference's cat / diff do).
+__device__ __forceinline__ float depth_prob(bool valid, float d, float sigma) {
+  return valid ? 1.0f / (1.0f + expf(d / sigma)) : 0.0f;  // torch.sigmoid(-dists / sigma) * mask
+}
+
+template <int KT>
+__global__ __launch_bounds__(kBlendBlock) void soft_depth_fwd_kernel(const float* __restrict__ dists,
+                                                                    const float* __restrict__ zbuf,
+                                                                    const int64_t* __restrict__ p2f, float sigma, float zfar,
+                                                                    int64_t npix, int K, float* __restrict__ depth) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock) {
+    bool valid[KT];
+    float d[KT], z[KT];
+    load_i64_row<KT>(p2f + i * K, K, valid);
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) any |= valid[k];
+    if (!any) {
+      // no face: every probability and weight is exactly 0 and zfar has weight 1 -- known without the other two rows
+      depth[i] = zfar;
+      continue;
+    }
+    load_f32_row<KT>(dists + i * K, K, d);
+    load_f32_row<KT>(zbuf + i * K, K, z);
+    float c = 0.0f, Cprev = 0.0f, acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+      if (k < K) {
+        c += depth_prob(valid[k], d[k], sigma);
+        const float C = fminf(c, 1.0f);
+        acc += (C - Cprev) * z[k];
+        Cprev = C;
+      }
+    }
+    depth[i] = acc + (1.0f - Cprev) * zfar;
+  }
+}
+
+template <int KT>
+__global__ __launch_bounds__(kBlendBlock) void soft_depth_bwd_kernel(const float* __restrict__ grad_depth,
+                                                                    const float* __restrict__ dists,
+                                                                    const float* __restrict__ zbuf,
+                                                                    const int64_t* __restrict__ p2f, float sigma, float zfar,
+                                                                    int64_t npix, int K, float* __restrict__ grad_dists,
+                                                                    float* __restrict__ grad_zbuf) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock) {
+    bool valid[KT];
+    float d[KT], z[KT], gz[KT], gd[KT];
+    load_i64_row<KT>(p2f + i * K, K, valid);
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) any |= valid[k];
+    if (!any) {
+      // no face: all weights are 0 and every slot is masked -- zero rows, nothing else read
+#pragma unroll
+      for (int k = 0; k < KT; ++k) gz[k] = 0.0f;
+      if (grad_zbuf) store_f32_row<KT>(grad_zbuf + i * K, K, gz);
+      if (grad_dists) store_f32_row<KT>(grad_dists + i * K, K, gz);
+      continue;
+    }
+    load_f32_row<KT>(dists + i * K, K, d);
+    load_f32_row<KT>(zbuf + i * K, K, z);
+    const float g = grad_depth[i];
+    float c = 0.0f, Cprev = 0.0f;
+    int kcut = 0;
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+      if (k < K) {
+        d[k] = depth_prob(valid[k], d[k], sigma);  // d holds the probabilities from here on
+        c += d[k];
+        const float C = fminf(c, 1.0f);
+        gz[k] = g * (C - Cprev);
+        Cprev = C;
+        if (c <= 1.0f) kcut = k + 1;
+      } else {
+        gz[k] = 0.0f;
+      }
+    }
+    if (grad_zbuf) store_f32_row<KT>(grad_zbuf + i * K, K, gz);
+    if (grad_dists) {
+      const float inv_sigma = 1.0f / sigma;
+      float s = 0.0f;
+#pragma unroll
+      for (int k = KT - 1; k >= 0; --k) {
+        if (k < kcut) s += z[k] - (k + 1 < K ? z[k + 1 < KT ? k + 1 : k] : zfar);
+        gd[k] = valid[k] ? g * s * (-inv_sigma * d[k] * (1.0f - d[k])) : 0.0f;
+      }
+      store_f32_row<KT>(grad_dists + i * K, K, gd);
+    }
+  }
+}
+
+// any K (> 32): the row is walked in memory, once forward; the backward walks it a second time in reverse for s_j
+__global__ __launch_bounds__(kBlendBlock) void soft_depth_fwd_generic(const float* __restrict__ dists,
+                                                                     const float* __restrict__ zbuf,
+                                                                     const int64_t* __restrict__ p2f, float sigma, float zfar,
+                                                                     int64_t npix, int K, float* __restrict__ depth) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock) {
+    float c = 0.0f, Cprev = 0.0f, acc = 0.0f;
+    for (int k = 0; k < K; ++k) {
+      const int64_t j = i * K + k;
+      c += depth_prob(p2f[j] >= 0, dists[j], sigma);
+      const float C = fminf(c, 1.0f);
+      acc += (C - Cprev) * zbuf[j];
+      Cprev = C;
+    }
+    depth[i] = acc + (1.0f - Cprev) * zfar;
+  }
+}
+
+__global__ __launch_bounds__(kBlendBlock) void soft_depth_bwd_generic(const float* __restrict__ grad_depth,
+                                                                     const float* __restrict__ dists,
+                                                                     const float* __restrict__ zbuf,
+                                                                     const int64_t* __restrict__ p2f, float sigma, float zfar,
+                                                                     int64_t npix, int K, float* __restrict__ grad_dists,
+                                                                     float* __restrict__ grad_zbuf) {
+  const float inv_sigma = 1.0f / sigma;
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock) {
+    const float g = grad_depth[i];
+    float c = 0.0f, Cprev = 0.0f;
+    int kcut = 0;
+    for (int k = 0; k < K; ++k) {
+      const int64_t j = i * K + k;
+      c += depth_prob(p2f[j] >= 0, dists[j], sigma);
+      const float C = fminf(c, 1.0f);
+      if (grad_zbuf) grad_zbuf[j] = g * (C - Cprev);
+      Cprev = C;
+      if (c <= 1.0f) kcut = k + 1;
+    }
+    if (!grad_dists) continue;
+    float s = 0.0f, znext = zfar;
+    for (int k = K - 1; k >= 0; --k) {
+      const int64_t j = i * K + k;
+      const float zk = zbuf[j];
+      if (k < kcut) s += zk - znext;
+      znext = zk;
+      const bool valid = p2f[j] >= 0;
+      const float p = depth_prob(valid, dists[j], sigma);
+      grad_dists[j] = valid ? g * s * (-inv_sigma * p * (1.0f - p)) : 0.0f;
+    }
+  }
+}
+
+// HardDepthShader: the depth of slot 0 where it holds a face, zfar elsewhere; the gradient goes back to that slot
+__global__ __launch_bounds__(kBlendBlock) void hard_depth_fwd_kernel(const float* __restrict__ zbuf,
+                                                                    const int64_t* __restrict__ p2f, float zfar, int64_t npix,
+                                                                    int K, float* __restrict__ depth) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock)
+    depth[i] = p2f[i * K] >= 0 ? zbuf[i * K] : zfar;
+}
+
+template <int KT>
+__global__ __launch_bounds__(kBlendBlock) void hard_depth_bwd_kernel(const float* __restrict__ grad_depth,
+                                                                    const int64_t* __restrict__ p2f, int64_t npix, int K,
+                                                                    float* __restrict__ grad_zbuf) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock) {
+    float gz[KT];
+#pragma unroll
+    for (int k = 0; k < KT; ++k) gz[k] = 0.0f;
+    if (p2f[i * K] >= 0) gz[0] = grad_depth[i];
+    store_f32_row<KT>(grad_zbuf + i * K, K, gz);
+  }
+}
+
+__global__ __launch_bounds__(kBlendBlock) void hard_depth_bwd_generic(const float* __restrict__ grad_depth,
+                                                                     const int64_t* __restrict__ p2f, int64_t npix, int K,
+                                                                     float* __restrict__ grad_zbuf) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlendBlock + threadIdx.x; i < npix; i += (int64_t)gridDim.x * kBlendBlock) {
+    grad_zbuf[i * K] = p2f[i * K] >= 0 ? grad_depth[i] : 0.0f;
+    for (int k = 1; k < K; ++k) grad_zbuf[i * K + k] = 0.0f;
+  }
+}
+
+// the K-rows are read and written with 16-byte accesses when they are a multiple of 16 bytes: their bases must be aligned
+bool rows_aligned(int K, const int64_t* p2f, const float* a, const float* b, const float* c, const float* d) {
+  uintptr_t bits = 0;
+  if (K % 2 == 0) bits |= (uintptr_t)p2f;
+  if (K % 4 == 0) bits |= (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d;
+  return (bits & 15) == 0;
+}
+
 }  // namespace
 }  // namespace p3d
 
@@ -587,5 +778,67 @@ P3D_API int p3d_hard_rgb_blend_backward(const float* grad_out, const int64_t* pi
   LaunchScope ls("hard_blend_bwd", s);
   hard_blend_bwd_kernel<<<blend_grid(npix * K * 3), kBlendBlock, 0, s>>>(grad_out, pix_to_face, npix, K,
                                                                                grad_colors);
+  return launch_status();
+}
+
+static int depth_args_status(int64_t npix, int K) {
+  if (npix < 0 || K < 1) return P3D_ERR_INVALID_ARG;
+  return K > 150 ? P3D_ERR_K_TOO_LARGE : P3D_OK;
+}
+
+P3D_API int p3d_soft_depth_blend_forward(const float* dists, const float* zbuf, const int64_t* pix_to_face, float sigma,
+                                         float zfar, int64_t npix, int K, float* depth, p3d_stream_t stream) {
+  const int rc = depth_args_status(npix, K);
+  if (rc != P3D_OK) return rc;
+  if (!(sigma > 0.0f)) return P3D_ERR_INVALID_ARG;
+  if (npix == 0) return P3D_OK;
+  if (!dists || !zbuf || !pix_to_face || !depth || !rows_aligned(K, pix_to_face, dists, zbuf, nullptr, nullptr))
+    return P3D_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = blend_grid(npix);
+  LaunchScope ls("soft_depth_fwd", s);
+  P3D_BLEND_DISPATCH(soft_depth_fwd_kernel, soft_depth_fwd_generic, K, dists, zbuf, pix_to_face, sigma, zfar, npix, K, depth)
+  return launch_status();
+}
+
+P3D_API int p3d_soft_depth_blend_backward(const float* grad_depth, const float* dists, const float* zbuf,
+                                          const int64_t* pix_to_face, float sigma, float zfar, int64_t npix, int K,
+                                          float* grad_dists, float* grad_zbuf, p3d_stream_t stream) {
+  const int rc = depth_args_status(npix, K);
+  if (rc != P3D_OK) return rc;
+  if (!(sigma > 0.0f)) return P3D_ERR_INVALID_ARG;
+  if (npix == 0 || (!grad_dists && !grad_zbuf)) return P3D_OK;
+  if (!grad_depth || !dists || !zbuf || !pix_to_face || !rows_aligned(K, pix_to_face, dists, zbuf, grad_dists, grad_zbuf))
+    return P3D_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = blend_grid(npix);
+  LaunchScope ls("soft_depth_bwd", s);
+  P3D_BLEND_DISPATCH(soft_depth_bwd_kernel, soft_depth_bwd_generic, K, grad_depth, dists, zbuf, pix_to_face, sigma, zfar, npix, K, grad_dists, grad_zbuf)
+  return launch_status();
+}
+
+P3D_API int p3d_hard_depth_blend_forward(const float* zbuf, const int64_t* pix_to_face, float zfar, int64_t npix, int K,
+                                         float* depth, p3d_stream_t stream) {
+  const int rc = depth_args_status(npix, K);
+  if (rc != P3D_OK) return rc;
+  if (npix == 0) return P3D_OK;
+  if (!zbuf || !pix_to_face || !depth) return P3D_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  LaunchScope ls("hard_depth_fwd", s);
+  hard_depth_fwd_kernel<<<blend_grid(npix), kBlendBlock, 0, s>>>(zbuf, pix_to_face, zfar, npix, K, depth);
+  return launch_status();
+}
+
+P3D_API int p3d_hard_depth_blend_backward(const float* grad_depth, const int64_t* pix_to_face, int64_t npix, int K,
+                                          float* grad_zbuf, p3d_stream_t stream) {
+  const int rc = depth_args_status(npix, K);
+  if (rc != P3D_OK) return rc;
+  if (npix == 0) return P3D_OK;
+  if (!grad_depth || !pix_to_face || !grad_zbuf || !rows_aligned(K, nullptr, grad_zbuf, nullptr, nullptr, nullptr))
+    return P3D_ERR_INVALID_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = blend_grid(npix);
+  LaunchScope ls("hard_depth_bwd", s);
+  P3D_BLEND_DISPATCH(hard_depth_bwd_kernel, hard_depth_bwd_generic, K, grad_depth, pix_to_face, npix, K, grad_zbuf)
   return launch_status();
 }

@@ -29,6 +29,8 @@ reference classes runs on them end to end:
     renderer.mesh.shader.Hard{Phong,Gouraud,Flat}Shader.forward -> the shader sees the nearest slot only (hard_rgb_blend keeps
                                                                  nothing else): 1 / K of the shading and texture work
     renderer.mesh.shader.SoftSilhouetteShader.forward         -> no ones_like(bary_coords) (1.6 GB at the bench batch)
+    renderer.mesh.shader.HardDepthShader / SoftDepthShader .forward -> csrc/blend.hip: hard_depth / soft_depth, one kernel
+                                                                 each way instead of the cat / cumsum / clamp / diff chain
     structures.meshes.Meshes.offset_verts / offset_verts_     -> one add on the packed vertices, topology shared, no host sync
                                                                  (the reference re-runs Meshes.__init__: ~70 syncs per call)
 
@@ -297,6 +299,7 @@ def patch_reference_python():
     _patch_splatter_phong_shader(importlib.import_module(__package__ + ".splatter"))
     _patch_meshes_offset_verts()
     _patch_hard_and_silhouette_shaders()
+    _patch_depth_shaders(our_blend)
 
 
 def camera_matrices(cameras, kwargs):
@@ -759,6 +762,64 @@ def _patch_hard_and_silhouette_shaders():
         sil_forward.__wrapped__ = sil_orig
         sil.forward = sil_forward
         _PATCHED.append((sil, "forward", sil_orig, sil_forward))
+
+
+def _patch_depth_shaders(our_blend):
+    """HardDepthShader.forward (shader.py:392-400) and SoftDepthShader.forward (shader.py:419-445) -> pytorch3d_amd.blending's
+    hard_depth_blend / soft_depth_blend: one kernel each way instead of a dozen passes over (N,H,W,K+1) tensors.  Cameras, zfar
+    and sigma are resolved as the reference resolves them: cameras from the keyword or the shader (its ValueError when there
+    are none), zfar from the keyword, else cameras.zfar, else 100, sigma from the shader's own blend_params.  Falls back to
+    the reference's forward for CPU tensors, tensors that are not float32 / int64 / four-dimensional and a zfar that is not
+    a number or a one-element tensor without grad (the reference raises its shape error for a longer one)."""
+    import importlib
+
+    import torch
+
+    shader = importlib.import_module("pytorch3d.renderer.mesh.shader")
+
+    def zfar_ok(zfar):
+        if torch.is_tensor(zfar):
+            return zfar.numel() == 1 and not zfar.requires_grad
+        return isinstance(zfar, (int, float)) and not isinstance(zfar, bool)
+
+    def frags_ok(fragments, with_dists):
+        p2f, zbuf = fragments.pix_to_face, fragments.zbuf
+        ok = (torch.is_tensor(p2f) and p2f.is_cuda and p2f.dtype == torch.int64 and p2f.dim() == 4
+              and 1 <= p2f.shape[3] <= _ours.kMaxPointsPerPixel and _is_hip_f32(zbuf) and zbuf.shape == p2f.shape
+              and zbuf.device == p2f.device)
+        if ok and with_dists:
+            d = fragments.dists
+            ok = _is_hip_f32(d) and d.shape == p2f.shape and d.device == p2f.device
+        return ok
+
+    def make(orig, name, soft):
+        def forward(self, fragments, meshes, **kwargs):
+            if soft and fragments.dists is None:
+                raise ValueError("SoftDepthShader requires Fragments.dists to be present.")
+            cameras = shader.ShaderBase._get_cameras(self, **kwargs)
+            zfar = kwargs.get("zfar", getattr(cameras, "zfar", 100.0))
+            try:
+                ok = zfar_ok(zfar) and frags_ok(fragments, soft) and (not soft or float(self.blend_params.sigma) > 0.0)
+            except Exception:
+                ok = False
+            _count(name + ".forward", ok)
+            if not ok:
+                return orig(self, fragments, meshes, **kwargs)
+            if soft:
+                return our_blend.soft_depth_blend(fragments, self.blend_params, zfar=zfar)
+            return our_blend.hard_depth_blend(fragments, zfar=zfar)
+
+        forward.__wrapped__ = orig
+        return forward
+
+    for cls_name, soft in (("HardDepthShader", False), ("SoftDepthShader", True)):
+        cls = getattr(shader, cls_name, None)
+        if cls is None:
+            continue
+        orig = cls.forward
+        new = make(orig, cls_name, soft)
+        cls.forward = new
+        _PATCHED.append((cls, "forward", orig, new))
 
 
 def _patch_meshes_offset_verts():
