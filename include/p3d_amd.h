@@ -562,6 +562,61 @@ int p3d_splatter_blend_backward(const float* grad_out, const float* colors, cons
                                 int K, float* grad_colors, float* grad_screen_coords, void* workspace, size_t workspace_bytes,
                                 p3d_stream_t stream);
 
+/* ---- deterministic backwards (torch.use_deterministic_algorithms(True)) -----------------------------------------------
+ *
+ * The backwards above end in float atomics: the order of the additions, and with it the last bits of a gradient, changes
+ * from run to run.  The *_ordered entries compute the same sums in an order that only their inputs decide (csrc/ordered_sum.h;
+ * DESIGN.md section 8.8): no float atomic in LDS or in memory, every output row written (zeros for primitives nobody hit),
+ * nothing read from an output or the workspace before it is written.  They are not bit-equal to the atomic entries.
+ *   sorted_samples (num_sorted) i64: the linear indices of the samples that hold a primitive (index >= 0), sorted STABLY by
+ *     that primitive: ascending primitive, ascending sample index inside one primitive.  The linear index counts the logical
+ *     shape of the index tensor: (N, H, W, K) for pix_to_face / idxs, (N, K, H, W) for the compositors' points_idx, (P) for
+ *     interp.  The caller builds it (torch: nonzero + stable sort; one host sync for num_sorted).  An index outside the tensor
+ *     or a primitive outside the output is skipped.  A list that is not sorted as described gives wrong sums, never a write
+ *     outside the outputs.
+ *   sorted_corners (num_corners) i64: the same for the corners c = 3 f + j of faces (F, 3) with a vertex inside [0, V),
+ *     sorted stably by vertex (negative ids wrap once, as torch indexing does).
+ *   workspace: p3d_*_ordered_workspace_bytes(...) bytes, 16-byte aligned; smaller: P3D_ERR_WORKSPACE.  Arguments are checked
+ *     before anything is launched. */
+size_t p3d_rasterize_meshes_backward_ordered_workspace_bytes(int64_t F, int through_faces, int64_t num_sorted);
+/* p3d_rasterize_meshes_backward_ex's two forms: faces null -> grad_out (F,3,3); faces (F,3) -> grad_out (V,3) (the per-face sums go
+ * to the workspace, then the corners of a vertex are summed in the order of sorted_corners). */
+int p3d_rasterize_meshes_backward_ordered(const float* face_verts, const int64_t* faces, const int64_t* pix_to_face,
+                                          const float* grad_zbuf, const float* grad_bary, const float* grad_dists,
+                                          const int64_t* sorted_samples, int64_t num_sorted, const int64_t* sorted_corners,
+                                          int64_t num_corners, int64_t F, int64_t V, int N, int H, int W, int K,
+                                          int perspective_correct, int clip_barycentric_coords, float* grad_out, void* workspace,
+                                          size_t workspace_bytes, p3d_stream_t stream);
+size_t p3d_scatter_face_grads_ordered_workspace_bytes(int64_t F);
+int p3d_scatter_face_grads_ordered(const float* grad_face_verts, const int64_t* faces, const int64_t* sorted_corners,
+                                   int64_t num_corners, int64_t V, int64_t F, float* grad_verts, void* workspace,
+                                   size_t workspace_bytes, p3d_stream_t stream);
+size_t p3d_rasterize_points_backward_ordered_workspace_bytes(int64_t num_sorted);
+int p3d_rasterize_points_backward_ordered(const float* points, const int32_t* idxs, const float* grad_zbuf, const float* grad_dists,
+                                          const int64_t* sorted_samples, int64_t num_sorted, int64_t P, int N, int H, int W, int K,
+                                          float* grad_points, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+/* p3d_rasterize_points_composite_backward; any K <= 150 (the pixel part runs per pixel, grad_alphas and the entries' weights pass
+ * through the workspace). */
+size_t p3d_rasterize_points_composite_backward_ordered_workspace_bytes(int N, int H, int W, int K, int C, int64_t num_sorted);
+int p3d_rasterize_points_composite_backward_ordered(int mode, const float* points, const float* features, const int32_t* idxs,
+                                                    const float* dists, const float* grad_images, const int64_t* sorted_samples,
+                                                    int64_t num_sorted, int64_t P, int C, int N, int H, int W, int points_per_pixel,
+                                                    float inv_r2, float* grad_points, float* grad_features, void* workspace,
+                                                    size_t workspace_bytes, p3d_stream_t stream);
+/* p3d_composite_backward: grad_alphas per pixel as before (no scatter), grad_features ordered; any C, both feature layouts. */
+size_t p3d_composite_backward_ordered_workspace_bytes(int N, int K, int H, int W, int C, int64_t num_sorted);
+int p3d_composite_backward_ordered(int mode, const float* grad_outputs, const float* features, const int64_t feature_strides[2],
+                                   const float* alphas, const int64_t* points_idx, const int64_t* sorted_samples, int64_t num_sorted,
+                                   int N, int C, int64_t P, int K, int H, int W, const int64_t alphas_strides[4],
+                                   const int64_t idx_strides[4], float* grad_features, const int64_t grad_feature_strides[2],
+                                   float* grad_alphas, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+/* p3d_interp_face_attrs_backward for float32 (float64 has no ordered form), any D; image-shaped samples take the same entry. */
+size_t p3d_interp_face_attrs_backward_ordered_workspace_bytes(int64_t D, int64_t num_sorted);
+int p3d_interp_face_attrs_backward_ordered(const int64_t* pix_to_face, const float* barycentric_coords, const float* face_attrs,
+                                           const float* grad_pix_attrs, const int64_t* sorted_samples, int64_t num_sorted, int64_t P,
+                                           int64_t F, int64_t D, float* grad_barycentric_coords, float* grad_face_attrs,
+                                           void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

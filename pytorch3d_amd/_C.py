@@ -88,6 +88,32 @@ def _refuse_when_deterministic(op_name):
         raise RuntimeError(f"{op_name} does not have a deterministic implementation")
 
 
+def _ordered():
+    """torch.use_deterministic_algorithms(True), not warn-only: the backwards take the *_ordered entries (include/p3d_amd.h) --
+    sums in an order that only the inputs decide -- instead of float atomics.  Off or warn-only: the atomic entries, as ever."""
+    return torch.are_deterministic_algorithms_enabled() and not torch.is_deterministic_algorithms_warn_only_enabled()
+
+
+def _sorted_hits(index):
+    """The linear indices (logical shape, row-major) of the entries of `index` that hold a primitive (>= 0), sorted stably by
+    that primitive: what the *_ordered entries take as sorted_samples.  torch.nonzero waits for the device once (the count);
+    the deterministic mode pays that, the atomic path never comes here."""
+    flat = index.reshape(-1)
+    hits = torch.nonzero(flat >= 0).squeeze(1)  # ascending linear index
+    order = torch.sort(flat[hits], stable=True).indices
+    return hits[order].contiguous()
+
+
+def _sorted_corners(faces, V):
+    """The corners 3 f + j of faces (F, 3) whose vertex lies in [0, V) (negative ids wrap once, as torch indexing does), sorted stably
+    by vertex: a vertex's faces in a fixed order."""
+    flat = faces.reshape(-1)
+    flat = torch.where(flat < 0, flat + V, flat)
+    ok = torch.nonzero((flat >= 0) & (flat < V)).squeeze(1)
+    order = torch.sort(flat[ok], stable=True).indices
+    return ok[order].contiguous()
+
+
 def _num_bins(H, W, bin_size, who):
     by, bx = 1 + (H - 1) // bin_size, 1 + (W - 1) // bin_size
     if by >= kMaxItemsPerBin or bx >= kMaxItemsPerBin:
@@ -485,7 +511,6 @@ def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad
                    cover, face_pre=None):
     """grad_face_verts (F,3,3) when faces is None, else grad_verts (V,3) through faces (F,3).  Missing grads count as zeros;
     cover: the row cover of THIS pix_to_face or None; face_pre: the records of p3d_gather_face_verts_pre (faces given) or None."""
-    _refuse_when_deterministic("RasterizeMeshesBackwardCuda")
     dev = pix_to_face.device
     zeros = lambda *tail: torch.zeros(tuple(pix_to_face.shape) + tail, dtype=torch.float32, device=dev)
     gz = _c(grad_zbuf, torch.float32) if grad_zbuf is not None else zeros()
@@ -511,11 +536,45 @@ def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad
                 face_pre = None  # the QUIRK above
         if F == 0:
             return out
+        if _ordered():
+            # the same bits whatever the cover, the records or the caller (the cover only says where NOT to look; the list below
+            # is made from pix_to_face itself)
+            lib = _lib.load()
+            hits = _sorted_hits(p2f)
+            corners = _sorted_corners(faces, V) if faces is not None else None
+            ws = _workspace(lib.p3d_rasterize_meshes_backward_ordered_workspace_bytes(F, int(faces is not None), hits.numel()), dev)
+            rc = lib.p3d_rasterize_meshes_backward_ordered(
+                _ptr(fv), _ptr(faces), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), _ptr(hits), hits.numel(), _ptr(corners),
+                corners.numel() if corners is not None else 0, F, V, N, H, W, K, persp, clip, _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+            _lib.check(rc, "rasterize_meshes_backward")
+            return out
         ws = backward_workspace(cover, N, H, W, dev)
         rc = _lib.load().p3d_rasterize_meshes_backward_ex(
             _ptr(fv), _ptr(faces), _ptr(face_pre), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), cover_ptr(cover, N, H, W), F, V, N, H, W,
             K, persp, clip, flags, _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
         _lib.check(rc, "rasterize_meshes_backward")
+    return out
+
+
+def scatter_face_grads(grad_face_verts, faces, V):
+    """The backward of `verts[faces]` (include/p3d_amd.h: p3d_scatter_face_grads[_ordered]): grad_face_verts (F, 3, 3), faces (F, 3)
+    int64 -> grad_verts (V, 3)."""
+    dev = grad_face_verts.device
+    g, faces = _c(grad_face_verts, torch.float32), _c(faces, torch.int64)
+    F = faces.shape[0]
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        if not V:
+            return out
+        if _ordered():
+            corners = _sorted_corners(faces, V)
+            ws = _workspace(lib.p3d_scatter_face_grads_ordered_workspace_bytes(F), dev)
+            rc = lib.p3d_scatter_face_grads_ordered(_ptr(g), _ptr(faces), _ptr(corners), corners.numel(), V, F, _ptr(out), _ptr(ws),
+                                                    ws.numel(), _stream(dev))
+        else:
+            rc = lib.p3d_scatter_face_grads(_ptr(g), _ptr(faces), V, F, _ptr(out), _stream(dev))
+        _lib.check(rc, "scatter_face_grads")
     return out
 
 
@@ -654,7 +713,6 @@ def _rasterize_points_fine(points, bin_points, image_size, radius, bin_size, poi
 def rasterize_points_backward(points, idxs, grad_zbuf, grad_dists):
     """RasterizePointsBackward, rasterize_points.h:281-305.  Returns grad_points (P,3)."""
     dev = _same_device(("points", points), ("idxs", idxs), ("grad_zbuf", grad_zbuf), ("grad_dists", grad_dists))
-    _refuse_when_deterministic("RasterizePointsBackwardCuda")
     pts = _c(points, torch.float32)
     ix = _c(idxs, torch.int32)
     gz, gd = _c(grad_zbuf, torch.float32), _c(grad_dists, torch.float32)
@@ -665,8 +723,14 @@ def rasterize_points_backward(points, idxs, grad_zbuf, grad_dists):
         out = torch.empty((P, 3), dtype=torch.float32, device=dev)
         if P == 0:
             return out
-        rc = lib.p3d_rasterize_points_backward(_ptr(pts), _ptr(ix), _ptr(gz), _ptr(gd), P, N, H, W, K, _ptr(out),
-                                               _stream(dev))
+        if _ordered():
+            hits = _sorted_hits(ix)
+            ws = _workspace(lib.p3d_rasterize_points_backward_ordered_workspace_bytes(hits.numel()), dev)
+            rc = lib.p3d_rasterize_points_backward_ordered(_ptr(pts), _ptr(ix), _ptr(gz), _ptr(gd), _ptr(hits), hits.numel(), P, N, H, W, K,
+                                                           _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
+        else:
+            rc = lib.p3d_rasterize_points_backward(_ptr(pts), _ptr(ix), _ptr(gz), _ptr(gd), P, N, H, W, K, _ptr(out),
+                                                   _stream(dev))
         _lib.check(rc, "rasterize_points_backward")
     return out
 
@@ -692,7 +756,6 @@ def rasterize_points_composite(points, cloud_to_packed_first_idx, num_points_per
 def rasterize_points_composite_backward(points, features, idxs, dists, grad_images, inv_r2, mode="alpha"):
     """include/p3d_amd.h: p3d_rasterize_points_composite_backward.  Returns (grad_points (P, 3), grad_features (P, C))."""
     dev = _same_device(("points", points), ("features", features), ("idxs", idxs), ("dists", dists), ("grad_images", grad_images))
-    _refuse_when_deterministic("RasterizePointsBackwardCuda")
     pts, feats = _c(points, torch.float32), _c(features, torch.float32)
     ix, ds, gi = _c(idxs, torch.int32), _c(dists, torch.float32), _c(grad_images, torch.float32)
     N, H, W, K = ix.shape
@@ -705,8 +768,15 @@ def rasterize_points_composite_backward(points, features, idxs, dists, grad_imag
         gf = torch.empty((P, C), dtype=torch.float32, device=dev)
         if P == 0:
             return gp, gf
-        rc = lib.p3d_rasterize_points_composite_backward(_SPLAT_MODES[mode], _ptr(pts), _ptr(feats), _ptr(ix), _ptr(ds), _ptr(gi), P, C, N, H, W, K,
-                                                         float(inv_r2), _ptr(gp), _ptr(gf), _stream(dev))
+        if _ordered():
+            hits = _sorted_hits(ix)
+            ws = _workspace(lib.p3d_rasterize_points_composite_backward_ordered_workspace_bytes(N, H, W, K, C, hits.numel()), dev)
+            rc = lib.p3d_rasterize_points_composite_backward_ordered(
+                _SPLAT_MODES[mode], _ptr(pts), _ptr(feats), _ptr(ix), _ptr(ds), _ptr(gi), _ptr(hits), hits.numel(), P, C, N, H, W, K,
+                float(inv_r2), _ptr(gp), _ptr(gf), _ptr(ws), ws.numel(), _stream(dev))
+        else:
+            rc = lib.p3d_rasterize_points_composite_backward(_SPLAT_MODES[mode], _ptr(pts), _ptr(feats), _ptr(ix), _ptr(ds), _ptr(gi), P, C, N, H, W, K,
+                                                             float(inv_r2), _ptr(gp), _ptr(gf), _stream(dev))
         _lib.check(rc, "rasterize_points_composite_backward")
     return gp, gf
 
@@ -781,8 +851,15 @@ def _composite_backward(mode, name, grad_outputs, features, alphas, points_idx):
         else:
             gf = torch.empty((C, P), dtype=torch.float32, device=dev)
         ga = torch.empty((N, K, H, W), dtype=torch.float32, device=dev)
-        rc = lib.p3d_composite_backward(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
-                                        _strides4(alphas), _strides4(points_idx), _ptr(gf), _strides2(fst), _ptr(ga), _stream(dev))
+        if _ordered():
+            hits = _sorted_hits(points_idx)  # in the logical (N, K, H, W) order, whatever the strides
+            ws = _workspace(lib.p3d_composite_backward_ordered_workspace_bytes(N, K, H, W, C, hits.numel()), dev)
+            rc = lib.p3d_composite_backward_ordered(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), _ptr(hits),
+                                                    hits.numel(), N, C, P, K, H, W, _strides4(alphas), _strides4(points_idx), _ptr(gf),
+                                                    _strides2(fst), _ptr(ga), _ptr(ws), ws.numel(), _stream(dev))
+        else:
+            rc = lib.p3d_composite_backward(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
+                                            _strides4(alphas), _strides4(points_idx), _ptr(gf), _strides2(fst), _ptr(ga), _stream(dev))
         _lib.check(rc, name)
     return gf, ga
 
@@ -853,7 +930,8 @@ def interp_face_attrs_backward(pix_to_face, barycentric_coords, face_attrs, grad
                        ("face_attributes", face_attrs), ("pix_attrs", grad_pix_attrs))
     if not (barycentric_coords.dtype == face_attrs.dtype == grad_pix_attrs.dtype) or face_attrs.dtype not in _DTYPES:
         raise RuntimeError("barycentric_coords, face_attributes and pix_attrs must have the same floating dtype")
-    _refuse_when_deterministic("InterpFaceAttrsBackwardCuda")
+    if _ordered() and face_attrs.dtype != torch.float32:
+        raise RuntimeError("InterpFaceAttrsBackwardCuda does not have a deterministic implementation for float64 (float32 has one)")
     P = pix_to_face.size(0)
     if barycentric_coords.dim() != 2 or barycentric_coords.size(0) != P or barycentric_coords.size(1) != 3:
         raise RuntimeError("barycentric_coords must have size (P, 3)")
@@ -868,6 +946,13 @@ def interp_face_attrs_backward(pix_to_face, barycentric_coords, face_attrs, grad
     with torch.cuda.device(dev):
         gb = torch.empty((P, 3), dtype=attrs.dtype, device=dev)
         gf = torch.empty((F, 3, D), dtype=attrs.dtype, device=dev)
+        if _ordered():  # (image-shaped or not: one entry, the same bits)
+            hits = _sorted_hits(p2f)
+            ws = _workspace(lib.p3d_interp_face_attrs_backward_ordered_workspace_bytes(D, hits.numel()), dev)
+            rc = lib.p3d_interp_face_attrs_backward_ordered(_ptr(p2f), _ptr(bary), _ptr(attrs), _ptr(g), _ptr(hits), hits.numel(), P, F, D,
+                                                            _ptr(gb), _ptr(gf), _ptr(ws), ws.numel(), _stream(dev))
+            _lib.check(rc, "interp_face_attrs_backward")
+            return gb, gf
         if (image_shape is not None and attrs.dtype == torch.float32 and 1 <= D <= 4 and F > 0
                 and image_shape[0] * image_shape[1] * image_shape[2] * image_shape[3] == P):
             n_, h_, w_, k_ = (int(x) for x in image_shape)

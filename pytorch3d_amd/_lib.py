@@ -135,6 +135,25 @@ _SIGNATURES = {
                                            c_ptr, c_ptr]),
     "p3d_splatter_blend_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_f32, ctypes.POINTER(c_f32), c_int, c_int, c_int,
                                             c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    # the deterministic backwards (include/p3d_amd.h: *_ordered)
+    "p3d_rasterize_meshes_backward_ordered_workspace_bytes": (c_size, [c_i64, c_int, c_i64]),
+    "p3d_rasterize_meshes_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64,
+                                                      c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_scatter_face_grads_ordered_workspace_bytes": (c_size, [c_i64]),
+    "p3d_scatter_face_grads_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_rasterize_points_backward_ordered_workspace_bytes": (c_size, [c_i64]),
+    "p3d_rasterize_points_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_ptr,
+                                                      c_ptr, c_size, c_ptr]),
+    "p3d_rasterize_points_composite_backward_ordered_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int, c_i64]),
+    "p3d_rasterize_points_composite_backward_ordered": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int,
+                                                                c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_composite_backward_ordered_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int, c_i64]),
+    "p3d_composite_backward_ordered": (c_int, [c_int, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_i64,
+                                               c_int, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr,
+                                               ctypes.POINTER(c_i64), c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_interp_face_attrs_backward_ordered_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "p3d_interp_face_attrs_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr,
+                                                       c_size, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

@@ -43,6 +43,21 @@ Tensor workspace(size_t bytes, const Tensor& like) {
   return at::empty({(int64_t)std::max<size_t>(bytes, 256)}, like.options().dtype(at::kByte));
 }
 
+// torch.use_deterministic_algorithms(True), not warn-only: the backwards take the *_ordered entries (include/p3d_amd.h) in place of
+// the float atomics -- the same switch, the same hit list and therefore the same bits as pytorch3d_amd/_C.py
+bool ordered() {
+  auto& ctx = at::globalContext();
+  return ctx.deterministicAlgorithms() && !ctx.deterministicAlgorithmsWarnOnly();
+}
+
+// linear indices (logical shape) of the entries >= 0, sorted stably by entry: sorted_samples of the *_ordered entries (one host sync)
+Tensor sorted_hits(const Tensor& index) {
+  auto flat = index.reshape({-1});
+  auto hits = at::nonzero(flat.ge(0)).squeeze(1);
+  auto order = std::get<1>(at::sort(flat.index_select(0, hits), /*stable=*/true, /*dim=*/0, /*descending=*/false));
+  return hits.index_select(0, order).contiguous();
+}
+
 void check_bins(int H, int W, int bin_size) {  // rasterize_coarse.cu:244-249
   TORCH_CHECK(bin_size > 0, "bin_size must be positive");
   const int bins = 1 + (std::max(H, W) - 1) / bin_size;
@@ -149,8 +164,9 @@ Tensor rasterize_meshes_backward(const Tensor& face_verts, const Tensor& pix_to_
                                  const Tensor& grad_dists, bool perspective_correct, bool clip_barycentric_coords) {
   check_gpu({{&face_verts, "face_verts"}, {&pix_to_face, "pix_to_face"}, {&grad_zbuf, "grad_zbuf"}, {&grad_bary, "grad_bary"},
              {&grad_dists, "grad_dists"}});
-  // float atomics: the accumulation order is not deterministic (rasterize_meshes.cu:587)
-  at::globalContext().alertNotDeterministic("RasterizeMeshesBackwardCuda");
+  // float atomics: the accumulation order is not deterministic (rasterize_meshes.cu:587); warn-only mode says so, strict mode
+  // takes the ordered entry below
+  if (!ordered()) at::globalContext().alertNotDeterministic("RasterizeMeshesBackwardCuda");
   DeviceGuard guard(face_verts.device());
   auto fv = face_verts.contiguous().to(at::kFloat);
   auto p2f = pix_to_face.contiguous().to(at::kLong);
@@ -159,6 +175,16 @@ Tensor rasterize_meshes_backward(const Tensor& face_verts, const Tensor& pix_to_
   const int64_t F = fv.size(0);
   auto out = at::empty({F, 3, 3}, fv.options());
   if (F == 0) return out;
+  if (ordered()) {
+    auto hits = sorted_hits(p2f);
+    auto ws = workspace(p3d_rasterize_meshes_backward_ordered_workspace_bytes(F, 0, hits.numel()), fv);
+    ok(p3d_rasterize_meshes_backward_ordered(fv.data_ptr<float>(), nullptr, p2f.data_ptr<int64_t>(), gz.data_ptr<float>(), gb.data_ptr<float>(),
+                                             gd.data_ptr<float>(), hits.data_ptr<int64_t>(), hits.numel(), nullptr, 0, F, 0, N, H, W, K,
+                                             perspective_correct, clip_barycentric_coords, out.data_ptr<float>(), ws.data_ptr(),
+                                             (size_t)ws.numel(), stream_of(fv)),
+       "rasterize_meshes_backward");
+    return out;
+  }
   ok(p3d_rasterize_meshes_backward(fv.data_ptr<float>(), p2f.data_ptr<int64_t>(), gz.data_ptr<float>(), gb.data_ptr<float>(),
                                    gd.data_ptr<float>(), F, N, H, W, K, perspective_correct, clip_barycentric_coords, out.data_ptr<float>(),
                                    stream_of(fv)),
@@ -243,7 +269,7 @@ std::tuple<Tensor, Tensor, Tensor> rasterize_points_fine(const Tensor& points, c
 
 Tensor rasterize_points_backward(const Tensor& points, const Tensor& idxs, const Tensor& grad_zbuf, const Tensor& grad_dists) {
   check_gpu({{&points, "points"}, {&idxs, "idxs"}, {&grad_zbuf, "grad_zbuf"}, {&grad_dists, "grad_dists"}});
-  at::globalContext().alertNotDeterministic("RasterizePointsBackwardCuda");
+  if (!ordered()) at::globalContext().alertNotDeterministic("RasterizePointsBackwardCuda");
   DeviceGuard guard(points.device());
   auto pts = points.contiguous().to(at::kFloat);
   auto ix = idxs.contiguous().to(at::kInt);
@@ -252,6 +278,15 @@ Tensor rasterize_points_backward(const Tensor& points, const Tensor& idxs, const
   const int64_t P = pts.size(0);
   auto out = at::empty({P, 3}, pts.options());
   if (P == 0) return out;
+  if (ordered()) {
+    auto hits = sorted_hits(ix);
+    auto ws = workspace(p3d_rasterize_points_backward_ordered_workspace_bytes(hits.numel()), pts);
+    ok(p3d_rasterize_points_backward_ordered(pts.data_ptr<float>(), ix.data_ptr<int32_t>(), gz.data_ptr<float>(), gd.data_ptr<float>(),
+                                             hits.data_ptr<int64_t>(), hits.numel(), P, N, H, W, K, out.data_ptr<float>(), ws.data_ptr(),
+                                             (size_t)ws.numel(), stream_of(pts)),
+       "rasterize_points_backward");
+    return out;
+  }
   ok(p3d_rasterize_points_backward(pts.data_ptr<float>(), ix.data_ptr<int32_t>(), gz.data_ptr<float>(), gd.data_ptr<float>(), P, N, H, W, K,
                                    out.data_ptr<float>(), stream_of(pts)),
      "rasterize_points_backward");
@@ -312,6 +347,15 @@ std::tuple<Tensor, Tensor> composite_backward(int mode, const char* name, const 
   auto ga = at::empty({N, K, H, W}, feats.options());
   const int64_t as[4] = {alphas.stride(0), alphas.stride(1), alphas.stride(2), alphas.stride(3)};
   const int64_t is[4] = {points_idx.stride(0), points_idx.stride(1), points_idx.stride(2), points_idx.stride(3)};
+  if (ordered()) {
+    auto hits = sorted_hits(points_idx);  // in the logical (N, K, H, W) order, whatever the strides
+    auto ws = workspace(p3d_composite_backward_ordered_workspace_bytes(N, K, H, W, C, hits.numel()), feats);
+    ok(p3d_composite_backward_ordered(mode, go.data_ptr<float>(), feats.data_ptr<float>(), fst, alphas.data_ptr<float>(),
+                                      points_idx.data_ptr<int64_t>(), hits.data_ptr<int64_t>(), hits.numel(), N, C, P, K, H, W, as, is,
+                                      gf.data_ptr<float>(), fst, ga.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(feats)),
+       name);
+    return {gf, ga};
+  }
   ok(p3d_composite_backward(mode, go.data_ptr<float>(), feats.data_ptr<float>(), fst, alphas.data_ptr<float>(), points_idx.data_ptr<int64_t>(),
                             N, C, P, K, H, W, as, is, gf.data_ptr<float>(), fst, ga.data_ptr<float>(), stream_of(feats)),
      name);
@@ -349,7 +393,9 @@ std::tuple<Tensor, Tensor> interp_face_attrs_backward(const Tensor& pix_to_face,
   TORCH_CHECK(barycentric_coords.scalar_type() == face_attrs.scalar_type() && grad_pix_attrs.scalar_type() == face_attrs.scalar_type(),
               "barycentric_coords, face_attributes and pix_attrs must have the same floating dtype");
   const int dt = dtype_code(face_attrs);
-  at::globalContext().alertNotDeterministic("InterpFaceAttrsBackwardCuda");
+  TORCH_CHECK(!(ordered() && dt != 0),
+              "InterpFaceAttrsBackwardCuda does not have a deterministic implementation for float64 (float32 has one)");
+  if (!ordered()) at::globalContext().alertNotDeterministic("InterpFaceAttrsBackwardCuda");
   const int64_t P = pix_to_face.size(0);
   TORCH_CHECK(barycentric_coords.dim() == 2 && barycentric_coords.size(0) == P && barycentric_coords.size(1) == 3, "barycentric_coords must have size (P, 3)");
   TORCH_CHECK(face_attrs.dim() == 3 && face_attrs.size(1) == 3, "face_attrs must have size (F, 3, D)");
@@ -359,6 +405,15 @@ std::tuple<Tensor, Tensor> interp_face_attrs_backward(const Tensor& pix_to_face,
   auto p2f = pix_to_face.contiguous().to(at::kLong);
   auto bary = barycentric_coords.contiguous(), attrs = face_attrs.contiguous(), g = grad_pix_attrs.contiguous();
   auto gb = at::empty({P, 3}, attrs.options()), gf = at::empty({F, 3, D}, attrs.options());
+  if (ordered()) {
+    auto hits = sorted_hits(p2f);
+    auto ws = workspace(p3d_interp_face_attrs_backward_ordered_workspace_bytes(D, hits.numel()), attrs);
+    ok(p3d_interp_face_attrs_backward_ordered(p2f.data_ptr<int64_t>(), bary.data_ptr<float>(), attrs.data_ptr<float>(), g.data_ptr<float>(),
+                                              hits.data_ptr<int64_t>(), hits.numel(), P, F, D, gb.data_ptr<float>(), gf.data_ptr<float>(),
+                                              ws.data_ptr(), (size_t)ws.numel(), stream_of(attrs)),
+       "interp_face_attrs_backward");
+    return {gb, gf};
+  }
   ok(p3d_interp_face_attrs_backward(dt, p2f.data_ptr<int64_t>(), bary.data_ptr(), attrs.data_ptr(), g.data_ptr(), P, F, D, gb.data_ptr(),
                                     gf.data_ptr(), stream_of(attrs)),
      "interp_face_attrs_backward");

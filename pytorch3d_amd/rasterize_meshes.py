@@ -149,18 +149,8 @@ class _GatherFaceVerts(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_face_verts):
-        from . import _lib
-
         (faces,) = ctx.saved_tensors
-        lib = _lib.load()
-        g = grad_face_verts.contiguous()
-        V, F = ctx.V, faces.shape[0]
-        with torch.cuda.device(g.device):
-            out = torch.empty((V, 3), dtype=torch.float32, device=g.device)
-            if V:
-                rc = lib.p3d_scatter_face_grads(_C._ptr(g), _C._ptr(faces), V, F, _C._ptr(out), _C._stream(g.device))
-                _lib.check(rc, "scatter_face_grads")
-        return out, None
+        return _C.scatter_face_grads(grad_face_verts, faces, ctx.V), None
 
 
 class _RasterizeFaceVerts(torch.autograd.Function):
