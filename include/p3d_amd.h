@@ -143,7 +143,12 @@ int p3d_rasterize_meshes_cover_check(const int64_t* pix_to_face, const int32_t* 
  * without a pass over the cover and without a workspace: two kernels fewer than with a plain cover (the list builder
  * mesh_backward_areas and the memset of its counter; 0.02 ms of the 2.3 ms bench step).  The words in front are a plain cover:
  * the buffer may be handed to every function that takes `cover`.  The list's order is the order in which the forward's tiles
- * finished. */
+ * finished.
+ * When the forward's tiles are the words of the cover (binned, image sides multiples of 16, at most 512 pixels a side, a full
+ * workspace) the list is filled from the tile plan of the coarse stage instead, without atomics: it then holds the word of EVERY
+ * tile whose bin list holds a face, in the order the forward walks them (longest list first, or image order for small launches),
+ * and the counter is the number of those tiles.  That is a superset of the non-empty words: a tile whose faces reach no pixel
+ * centre is listed with a word that ends up 0 (the backward finds no row there and returns).  No word is listed twice. */
 size_t p3d_rasterize_meshes_cover_list_bytes(int N, int H, int W);
 
 /* flags of p3d_rasterize_meshes_ex (both) and p3d_rasterize_points_ex (P3D_RASTER_CUDA_TIE_ORDER only) */

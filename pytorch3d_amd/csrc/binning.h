@@ -64,7 +64,8 @@ inline BinGeom make_internal_geom(int H, int W, int user_bin_size) {
 //               then the class counts and cursors of the sort
 // The fine rasterizers use it to walk the tiles in a balanced order (raster_mesh.hip: "Which tile") and to let the
 // workgroups of active tiles write the -1 fill of the background tiles ("piggyback fill"): active row number r fills
-// background rows [r * q, (r + 1) * q), q = ceil(B / A).
+// background rows [r * q, (r + 1) * q), q = ceil(B / A).  With a tile order, r is the tile's position in the walk (any bijection
+// of the active workgroups onto 0..A-1 will do, and this one needs no load); without one (small launches) its rank arank[row].
 constexpr int kPlanClasses = 64;  // list-length classes of the tile order
 constexpr int kPlanHdr = 4;       // first class counter in plan_hdr
 constexpr int kPlanTicket = kPlanHdr + 2 * kPlanClasses;  // arrival counter of the row scan's workgroups (bin_scan_rows_tail_kernel)

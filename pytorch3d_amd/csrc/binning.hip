@@ -575,7 +575,9 @@ __global__ __launch_bounds__(1024) void bin_scan_small_kernel(int* __restrict__ 
                                                               int* __restrict__ bg_list, int* __restrict__ plan_hdr,
                                                               int64_t capacity) {
   __shared__ int cs[kSelfPlanMax + 1];
-  if (threadIdx.x == 0) plan_hdr[3] = 0;  // no sorted order from this kernel (small launches run the split kernels)
+  // no sorted order from this kernel: launches of up to 512 tiles run the split kernels, larger ones (up to 4096 rows get here) walk the
+  // tiles in image order and key the piggyback fill by arank[row] (raster_mesh.hip; tests/test_gpu_fine_tile_walk.py cases 1-10)
+  if (threadIdx.x == 0) plan_hdr[3] = 0;
   __shared__ long long wsum[16];
   plan_in_lds(count, N, cs);
   const int tid = threadIdx.x;

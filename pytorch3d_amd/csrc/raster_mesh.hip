@@ -35,6 +35,69 @@
 #include <stdlib.h>
 
 
+// Probe build (-DP3D_PROBE_CHAIN through P3D_EXTRA_FLAGS into a library of its own, never the product): where the life of an active
+// tile's wave goes.  Lane 0 of every wave of one workgroup in eight (single-chunk tiles of the plan walk) notes the shader clock at
+// the points below in LDS; at exit the wave adds the length of each phase to g_chain[phase] and 1 to g_chain[16 + phase] (ordinary
+// atomics, nothing waits for them).  profiles/fine_tile_chain.py reads and prints them.
+#ifdef P3D_PROBE_CHAIN
+__device__ unsigned long long g_chain[32];
+extern "C" __attribute__((visibility("default"))) void p3d_probe_chain_read(unsigned long long* out) {
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chain), sizeof(unsigned long long) * 32);
+  unsigned long long z[32] = {0};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_chain), z, sizeof(z));
+}
+namespace p3d {
+namespace {
+constexpr int kChainStamps = 11;  // 0 entry, 1 head loads, 2 list indices, 3 vertices, 4 staging published, 5 order done, 6 evaluation done,
+                                  // 7 past the trailing barrier, 8 pixel stores issued, 9 background rows known, 10 exit
+__shared__ unsigned long long s_chain[4][kChainStamps + 1];  // [wave][stamp]; [wave][kChainStamps] = armed
+__device__ __forceinline__ void chain_note(int i, unsigned long long t) {
+  if ((threadIdx.x & 63) == 0) s_chain[threadIdx.x >> 6][i] = t;
+}
+__device__ __forceinline__ void chain_stamp(int i) { chain_note(i, __builtin_readcyclecounter()); }
+__device__ __forceinline__ void chain_flush(unsigned long long r0) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (s_chain[w][kChainStamps] == 0ull || lane >= kChainStamps) return;
+  if (lane == 0) {  // the wave's life on the constant 100 MHz clock: what a tick of the shader clock is worth
+    atomicAdd(&g_chain[15], (unsigned long long)__builtin_amdgcn_s_memrealtime() - r0);
+    atomicAdd(&g_chain[31], 1ull);
+    return;
+  }
+  // (same wave, in-order LDS: the notes of lane 0 are visible)
+  const unsigned long long t1 = s_chain[w][lane];
+  int prev = lane - 1;
+  while (prev > 0 && s_chain[w][prev] == 0ull) --prev;  // a point this wave did not pass
+  if (t1 == 0ull) return;
+  atomicAdd(&g_chain[lane], t1 - s_chain[w][prev]);
+  atomicAdd(&g_chain[16 + lane], 1ull);
+}
+}  // namespace
+}  // namespace p3d
+#define P3D_CHAIN_ENTRY()                                                                                        \
+  const unsigned long long chain_t0 = __builtin_readcyclecounter();                                              \
+  const unsigned long long chain_r0 = __builtin_amdgcn_s_memrealtime();                                          \
+  if ((threadIdx.x & 63) < kChainStamps + 1) s_chain[threadIdx.x >> 6][threadIdx.x & 63] = 0ull
+#define P3D_CHAIN_ARM(on)                                                                 \
+  if ((on) && (blockIdx.x & 7u) == 0u) {                                                  \
+    chain_note(kChainStamps, 1ull);                                                       \
+    chain_note(0, chain_t0);                                                              \
+  }
+#define P3D_CHAIN_STAMP(i) chain_stamp(i)
+#define P3D_CHAIN_ARRIVED(i, ...)               \
+  do {                                          \
+    asm volatile("" ::__VA_ARGS__ : "memory");  \
+    chain_stamp(i);                             \
+  } while (0)
+#define P3D_CHAIN_FLUSH() chain_flush(chain_r0)
+#else
+#define P3D_CHAIN_ENTRY() ((void)0)
+#define P3D_CHAIN_ARM(on) ((void)0)
+#define P3D_CHAIN_STAMP(i) ((void)0)
+#define P3D_CHAIN_ARRIVED(i, ...) ((void)0)
+#define P3D_CHAIN_FLUSH() ((void)0)
+#endif
+
 namespace p3d {
 
 namespace {
@@ -253,6 +316,7 @@ __device__ __forceinline__ void write_subtile_fill_patch(const MeshArgs& a, cons
 // 256 threads -- every store instruction of a wave covers one contiguous 1 KiB piece (a lane writing its own pixel's
 // K-row stores 16 bytes at a stride of 4*K..12*K).  Per tile row the outputs hold cols*K floats (zbuf, dists),
 // 3*cols*K floats (bary) and cols*K int64 (pix_to_face) = 7 * cols*K/4 16-byte pieces.
+// `tid` in 0..THREADS-1 names the share to write: a wave may write another wave's share (the piggyback fill hands out quarters).
 template <int THREADS>
 __device__ __forceinline__ void fill_tile_background(const MeshArgs& a, int n, int ty0, int tx0, int y_end, int x_end,
                                                      int tid, int side = kTile) {
@@ -653,11 +717,13 @@ __device__ __forceinline__ int stage_chunk(const MeshArgs& a, const StageLds& l,
   fs.reject = true;
   if (has) {
     fid = BINNED ? a.csr.list[src_base + i] : (int)(src_base + i);
+    P3D_CHAIN_ARRIVED(2, "v"(fid));
     const float* g = a.face_verts + (int64_t)fid * 9;
     nb = (int)a.neighbor[fid];  // requested together with the vertices: one memory round trip, not two
     v0 = mk3(g[0], g[1], g[2]);
     v1 = mk3(g[3], g[4], g[5]);
     v2 = mk3(g[6], g[7], g[8]);
+    P3D_CHAIN_ARRIVED(3, "v"(v0.x), "v"(v1.y), "v"(v2.z), "v"(nb));
     fs = face_setup(v0, v1, v2, a.sqrt_blur, cull);
   }
   // the tile's pixel columns / rows whose centres lie inside the blur-expanded box: the per-pixel bbox test of the
@@ -827,6 +893,7 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
   __shared__ float s_qlow[kStage];                  // lower bound of s_zc over sorted positions >= i
   __shared__ ChunkOrderScratch s_ord;
   __shared__ int s_wcnt[kStage / kWave];
+  __shared__ int s_fill_ticket;  // quarter-tiles of the piggyback fill handed out so far
 
   // Which tile.  With a tile plan (binning.h: the lists came from bin_build and a tile is a bin) the blocks walk the ACTIVE
   // tiles, longest list first, and then the background ones.  Workgroups reach the CUs round robin by index, not by load
@@ -835,22 +902,37 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
   // background, and the few tiles with many hundred faces -- 250-330 us each, profiles/r02_fine_timeline.txt -- start at
   // arbitrary times) some CUs idle while others queue; dealt longest-first every CU draws the same mix and the launch has no
   // tail.  Measured: 1.19 -> 1.04 ms.  Otherwise (naive path, caller's bins, split mode): the XCD-aware tile map.
+  // The head of an active tile is a chain of dependent global round trips with all four waves idle (profiles/fine_tile_chain_mi355x.txt:
+  // ~2.2 us to the first answer of a wave's life and for the list, 0.8 us for the vertex gather, under this kernel's write load), so
+  // everything that does not depend on another load is requested HERE, in one batch of scalar loads waited for once: the overflow
+  // flag, the plan's header and the row at walk position `blk` (order[] is read at an index clamped to its length: which entries
+  // mean something is only known with the header).  The row's list length and offset are the second trip, the list the third.
+  P3D_CHAIN_ENTRY();
+  // ... and the wave runs at raised priority until its tile's first chunk is staged and ordered: a workgroup in this serial phase (a
+  // few hundred instructions between long waits) otherwise queues for issue behind the evaluating waves of the three other
+  // workgroups on its SIMDs.  Measured on the bench launch only (K = 8, perspective + clip, plan walk; -4.3 % on a variant of this
+  // head, profiles/fine_tile_chain_mi355x.txt); the other instantiations (naive, split, tie marks, long queues) and the workgroups
+  // that only fill or return take the same few instructions and were not measured.
+  __builtin_amdgcn_s_setprio(3);
+  unsigned blk = SPLIT ? blockIdx.x >> 2 : blockIdx.x;
+  const bool plan_walk = BINNED && !SPLIT && a.walk_plan != 0;  // uniform (kernel argument)
+  int hdr_a = 0, hdr_b = 0, hdr_order = 0;
+  int walk_row = 0;
+  if (plan_walk) {
+    hdr_a = a.csr.plan.hdr[0];
+    hdr_b = a.csr.plan.hdr[1];
+    hdr_order = a.csr.plan.hdr[3];
+    const unsigned rows = (unsigned)(a.N * a.tm.BH * a.tm.BW);  // (> 0: the launch has tiles)
+    walk_row = a.csr.plan.order[blk < rows ? blk : rows - 1u];  // (meaningful for blk < A, and only with hdr[3] != 0)
+  }
   if (a.overflow != nullptr && (*a.overflow != 0) == BINNED) return;  // uniform (scalar load)
   TileCoord tc;
-  unsigned blk = SPLIT ? blockIdx.x >> 2 : blockIdx.x;
   bool listed = false;
-  if (BINNED && !SPLIT && a.walk_plan && a.csr.plan.hdr[3] != 0) {  // uniform
-    const unsigned A = (unsigned)a.csr.plan.hdr[0], B = (unsigned)a.csr.plan.hdr[1];
+  if (plan_walk && hdr_order != 0) {  // uniform
+    const unsigned A = (unsigned)hdr_a, B = (unsigned)hdr_b;
     int row;
     if (blk < A) {
-      row = a.csr.plan.order[blk];
-      if (a.list_by_plan && threadIdx.x == 0) {
-        // this tile's word of the cover into slot `blk` of the list: the backward then walks the areas longest list first, as this launch does
-        const int per = a.tm.BH * a.tm.BW;
-        const int ln = row / per, lrem = row - ln * per, lby = lrem / a.tm.BW, lbx = lrem - lby * a.tm.BW;
-        a.area_list[blk] = (ln * a.CY + (a.CY - 1 - lby)) * a.CX + (a.CX - 1 - lbx);
-        if (blk == 0) *a.area_count = (int)A;
-      }
+      row = walk_row;
     } else if (blk < A + B) {
       if (EXACT && (KT & 3) == 0 && A > 0) return;  // piggyback fill (below): the active workgroups write this tile
       row = a.csr.plan.bg_list[blk - A];
@@ -863,6 +945,11 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
     tc.by = rem / a.tm.BW;
     tc.bx = rem - tc.by * a.tm.BW;
     tc.ty = tc.tx = 0;
+    if (blk < A && a.list_by_plan && threadIdx.x == 0) {
+      // this tile's word of the cover into slot `blk` of the list: the backward then walks the areas longest list first, as this launch does
+      a.area_list[blk] = (tc.n * a.CY + (a.CY - 1 - tc.by)) * a.CX + (a.CX - 1 - tc.bx);
+      if (blk == 0) *a.area_count = (int)A;
+    }
     listed = true;
   }
   if (!listed && !tile_of_block(a.tm, blk, &tc)) return;
@@ -887,13 +974,18 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
   const bool pix_ok = yi < y_end && xi < x_end;
   const bool wave_ok = sy0 < y_end && sx0 < x_end;
 
+  // Piggyback fill (below): which share of the background tiles this workgroup writes -- its position in the walk, or without a
+  // tile order (small launches) the tile's rank among the active tiles, requested with the CSR row.
+  const bool piggy = BINNED && !SPLIT && EXACT && (KT & 3) == 0 && plan_walk;
   int64_t src_base;
   int count;
+  int fill_slot = (int)blk;
   if (BINNED) {
     // both words of the bin's CSR row are requested at once (offset has rows + 1 entries, so the load is always valid)
     const int64_t row = ((int64_t)n * a.tm.BH + by) * a.tm.BW + bx;
     count = a.csr.total[row];
     src_base = a.csr.offset[row];
+    if (!listed && (piggy || (!SPLIT && a.list_by_plan))) fill_slot = a.csr.plan.arank[row];
   } else {
     src_base = a.mesh_first[n];
     count = (int)a.mesh_count[n];
@@ -903,24 +995,33 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
   // ~5.6 us -- 0.2 ms of a 1.5 ms launch were slots held by background tiles (profiles/r02_ablate_fwd.txt: tiles with
   // faces alone 1.3 ms).  With the tile plan of the offsets scan (binning.h: TilePlan) the ACTIVE workgroups issue those
   // stores instead, at the end of their own work (fire and forget: ~40 instructions per tile, fill_tile_full), and a
-  // background workgroup returns at once.  Active row number r takes background rows [r q, (r + 1) q), q = ceil(B / A).
+  // background workgroup returns at once.  Active workgroup number r (its walk position) takes background rows [r q, (r + 1) q), q = ceil(B / A).
   // Only when a bin is ONE tile (walk_plan: Ty == Tx == 1, images up to 512 pixels a side): with several tiles per bin a
   // background bin's tile (ty, tx) would be dealt to workgroup (ty, tx) of an active bin, and the workgroups of an active
   // bin in the partial last bin row / column whose own tile has no pixel return before they get here -- those tiles of
   // the background bins dealt to them were never written (tests/test_gpu_meshes.py:
   // test_large_images_background_is_written).  Larger images fill their background tiles with their own workgroups.
-  const bool piggy = BINNED && !SPLIT && EXACT && (KT & 3) == 0 && a.walk_plan != 0 && a.csr.plan.hdr != nullptr;
-  int plan_a = 0, plan_b = 0;
-  if (piggy) {
-    plan_a = a.csr.plan.hdr[0];
-    plan_b = a.csr.plan.hdr[1];
+  // The fill runs at the END of the workgroup's own work, and a round trip there holds its slot (LDS, four wave slots) for nothing:
+  // the first two of its background rows (q = 2 at the bench workload) are requested now and wait in SGPRs.
+  const int plan_a = piggy ? hdr_a : 0, plan_b = piggy ? hdr_b : 0;
+  int bg_n = 0, bg_row0 = 0, bg_row1 = 0;
+  long long bg_j0 = 0;
+  if (piggy && plan_b > 0 && count > 0) {  // uniform
+    const int q_bg = (plan_b + plan_a - 1) / plan_a;
+    bg_j0 = (long long)fill_slot * q_bg;
+    const long long left = (long long)plan_b - bg_j0;
+    bg_n = left < 0 ? 0 : (left < q_bg ? (int)left : q_bg);
+    if (bg_n > 0) bg_row0 = a.csr.plan.bg_list[bg_j0];
+    if (bg_n > 1) bg_row1 = a.csr.plan.bg_list[bg_j0 + 1];
   }
+  if (tid == 0) s_fill_ticket = 0;  // (published by the first staging barrier)
   if (BINNED && !SPLIT && a.list_by_plan && !listed && tid == 0) {
     // (a plan without a tile order -- small launches: the slot is the tile's rank among the active tiles)
-    const int64_t row = ((int64_t)n * a.tm.BH + by) * a.tm.BW + bx;
-    if (count > 0) a.area_list[a.csr.plan.arank[row]] = (n * a.CY + (a.CY - 1 - by)) * a.CX + (a.CX - 1 - bx);
-    if (blockIdx.x == 0) *a.area_count = a.csr.plan.hdr[0];
+    if (count > 0) a.area_list[fill_slot] = (n * a.CY + (a.CY - 1 - by)) * a.CX + (a.CX - 1 - bx);
+    if (blockIdx.x == 0) *a.area_count = hdr_a;
   }
+  P3D_CHAIN_ARM(BINNED && listed && count > 0 && count <= kStage);
+  P3D_CHAIN_STAMP(1);
   if (count <= 0) {
     if (piggy && plan_a > 0) return;  // an active workgroup writes this tile (uniform)
     const int Kbg = EXACT ? KT : a.K;  // compile-time where it can be: the row-fill branch is then the only one left
@@ -1009,12 +1110,20 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
   for (; base < count; base += kStage) {
     staged = stage_chunk<BINNED, PC>(a, lds, tile, src_base, count, base, tid, cull, clip, prune, &general);
     if (general) break;  // uniform
+    P3D_CHAIN_STAMP(4);
     chunk_bucket_order(s_zc, staged, s_order, s_qlow, s_ord, tid);
+    P3D_CHAIN_STAMP(5);
+    __builtin_amdgcn_s_setprio(0);
     if (run_waves)
       wave_chunk<false, Queue, PC, TIES>(a, K, q, staged, true, st, p, pix_ok, lane, persp, clip, prune, s_pm, s_rec, s_zc, s_order,
                                          s_qlow, SPLIT ? 0 : (sub & 1) * 8, SPLIT ? 0 : (sub >> 1) * 8, tie_z, tie_drop, SPLIT ? w : -1);
-    __syncthreads();
+    P3D_CHAIN_STAMP(6);
+    // the staging arrays are rewritten by the next chunk only: after the last one (98.9 % of the bench launch's tiles hold one chunk) a
+    // wave goes straight on to its pixel stores instead of waiting for the slowest of the four (uniform)
+    if (base + kStage < count) __syncthreads();
+    P3D_CHAIN_STAMP(7);
   }
+  __builtin_amdgcn_s_setprio(0);  // (a first chunk that went to the general nest left the loop before it was lowered)
   if constexpr (SPLIT && Queue::kPayload > 0) {
     // the queues of waves 1..3 join wave 0's: before the general nest (its neighbour rule must see every entry queued so
     // far, and only wave 0 walks it), or before the pixels are written
@@ -1101,27 +1210,38 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
     const unsigned long long tmask = __ballot(tie);
     if (a.tie_words != nullptr && wave_ok && l2 == 0) a.tie_words[((int64_t)n * a.SY + (sy0 >> 3)) * a.SX + (sx0 >> 3)] = tmask;
   }
+  P3D_CHAIN_STAMP(8);
   if constexpr (BINNED && !SPLIT && EXACT && (KT & 3) == 0) {
-    if (piggy && plan_b > 0) {
-      const int64_t row = ((int64_t)n * a.tm.BH + by) * a.tm.BW + bx;
-      const int q_bg = (plan_b + plan_a - 1) / plan_a;
-      const long long j0 = (long long)a.csr.plan.arank[row] * q_bg;
-      const long long j1 = j0 + q_bg < (long long)plan_b ? j0 + q_bg : (long long)plan_b;
+    // Piggyback fill: the workgroup's bg_n background tiles, a quarter (the share of one wave: `tid` of wave t & 3) at a time.  Whichever
+    // wave has issued its own pixel stores draws the next quarter from the LDS ticket, so the waves that finish first write most of them
+    // and the slowest one, which decides when the workgroup's slot is free again, usually finds none left.  Every quarter is drawn once.
+    if (bg_n > 0) {  // uniform
+      P3D_CHAIN_ARRIVED(9, "s"(bg_row0), "s"(bg_row1));
+      int l2;
+      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l2));
       const int per_image = a.tm.BH * a.tm.BW;
-      for (long long j = j0; j < j1; ++j) {  // uniform: scalar loads and arithmetic
-        const int brow = a.csr.plan.bg_list[j];
+      for (;;) {
+        int t = 0;
+        if (l2 == 0) t = atomicAdd(&s_fill_ticket, 1);
+        t = __builtin_amdgcn_readfirstlane(t);
+        const int j = t >> 2;
+        if (j >= bg_n) break;  // uniform: scalar loads and arithmetic below
+        const int brow = j == 0 ? bg_row0 : (j == 1 ? bg_row1 : a.csr.plan.bg_list[bg_j0 + j]);
+        const int vtid = (t & 3) * kWave + l2;
         const int bn = brow / per_image, brem = brow - bn * per_image;
         const int bby = brem / a.tm.BW, bbx = brem - bby * a.tm.BW;
         const int by_end = min(H, (bby + 1) * a.tm.bin_size), bx_end = min(W, (bbx + 1) * a.tm.bin_size);
         const int bty0 = bby * a.tm.bin_size + ty * kTile, btx0 = bbx * a.tm.bin_size + tx * kTile;  // the same tile of that bin
         if (bty0 >= by_end || btx0 >= bx_end) continue;
         if (bty0 + kTile <= by_end && btx0 + kTile <= bx_end)
-          fill_tile_full<KT>(a, bn, bty0, btx0, tid);
+          fill_tile_full<KT>(a, bn, bty0, btx0, vtid);
         else
-          fill_tile_background<kStage>(a, bn, bty0, btx0, by_end, bx_end, tid);
+          fill_tile_background<kStage>(a, bn, bty0, btx0, by_end, bx_end, vtid);
       }
     }
   }
+  P3D_CHAIN_STAMP(10);
+  P3D_CHAIN_FLUSH();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
