@@ -243,6 +243,17 @@ int p3d_transform_verts_forward(const float* verts_world, const int64_t* mesh_to
 int p3d_transform_verts_backward(const float* verts_world, const int64_t* mesh_to_vert_first_idx, const float* matrices,
                                  const float* grad_verts_ndc, int64_t V, int N, int num_matrices, float* grad_verts_world,
                                  p3d_stream_t stream);
+/* The same backward with the gradient of the CAMERAS: grad_matrices (num_matrices,2,4,4), the layout of `matrices`, fully written:
+ *   grad_matrices[n][0][i][j] = sum_v (x, y, z, 1)_i * dL/d((p, 1) @ A)_j,   grad_matrices[n][1][i][j] = sum_v (view, 1)_i * dL/d((view, 1) @ B)_j
+ * over the vertices that share matrix n (mesh n, or all of them when num_matrices == 1); a mesh without vertices gets zeros, and
+ * column j = 2 of the second matrix is exactly 0 (the depth is taken from view space).  A two-stage segmented sum without float
+ * atomics: the same input gives the same bits on every run and stream.  grad_verts_world (V,3) comes from the same pass, bit-equal
+ * to p3d_transform_verts_backward's, or is skipped when NULL.  workspace: at least p3d_transform_backward_workspace_bytes(...)
+ * bytes, 16-byte aligned (a shorter one: P3D_ERR_INVALID_ARG, nothing is launched); V == 0: zeros, no launch, no workspace. */
+size_t p3d_transform_backward_workspace_bytes(int64_t V, int N, int num_matrices);
+int p3d_transform_backward_cameras(const float* verts_world, const int64_t* mesh_to_vert_first_idx, const float* matrices,
+                                   const float* grad_verts_ndc, int64_t V, int N, int num_matrices, float* grad_verts_world,
+                                   float* grad_matrices, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
 /* ---- point clouds -------------------------------------------------------------------- */
 

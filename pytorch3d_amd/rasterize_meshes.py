@@ -269,17 +269,16 @@ def rasterize_meshes_world(meshes_world, world_to_view, view_to_ndc, image_size=
 
     world_to_view, view_to_ndc: (N, 4, 4) or (1, 4, 4) matrices, `cameras.get_world_to_view_transform().get_matrix()` and
     `cameras.get_projection_transform().compose(cameras.get_ndc_camera_transform()).get_matrix()`.  The transform runs
-    inside the face gather (one launch); the backward delivers the gradient wrt the WORLD vertices.  Matrices that
-    require grad take the torch formulation of the transform (gradients to the cameras through autograd), followed by
-    the fused gather + rasterization."""
+    inside the face gather (one launch); the backward delivers the gradient wrt the WORLD vertices and, for matrices that
+    require grad, wrt both matrix stacks (p3d_transform_backward_cameras; a (1, 4, 4) stack next to an (N, 4, 4) one is
+    reduced by autograd through the broadcast of _pack_matrices).  Inputs the kernels do not take (CPU tensors, other
+    dtypes) go through the torch formulation of the transform."""
     verts = meshes_world.verts_packed()
     faces = meshes_world.faces_packed()
     n = len(meshes_world)
     w2v = torch.as_tensor(world_to_view)
     v2n = torch.as_tensor(view_to_ndc)
-    cams_need_grad = (torch.is_tensor(world_to_view) and world_to_view.requires_grad) or \
-                     (torch.is_tensor(view_to_ndc) and view_to_ndc.requires_grad)
-    if cams_need_grad or not _gatherable(verts, faces):
+    if not _gatherable(verts, faces):
         a = w2v.to(verts.device, torch.float32)
         b = v2n.to(verts.device, torch.float32)
         a = a[None] if a.dim() == 2 else a
@@ -301,7 +300,8 @@ def rasterize_meshes_world(meshes_world, world_to_view, view_to_ndc, image_size=
 
 class _TransformVerts(torch.autograd.Function):
     """world vertices (V,3) -> NDC x, y + view depth (V,3): MeshRasterizer.transform (rasterizer.py:171-216) on the PACKED
-    vertices in one launch (p3d_transform_verts_forward), backward = p3d_transform_verts_backward."""
+    vertices in one launch (p3d_transform_verts_forward), backward = p3d_transform_verts_backward, or
+    p3d_transform_backward_cameras when the matrices need their gradient too."""
 
     @staticmethod
     def forward(ctx, verts, vert_first, mats):
@@ -321,25 +321,48 @@ class _TransformVerts(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
-
         v, vert_first, mats = ctx.saved_tensors
-        lib = _lib.load()
-        dev = v.device
-        g = g.contiguous()
-        with torch.cuda.device(dev):
-            out = torch.empty_like(v)
-            if v.shape[0]:
-                rc = lib.p3d_transform_verts_backward(_C._ptr(v), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g), v.shape[0],
-                                                      vert_first.shape[0], mats.shape[0], _C._ptr(out), _C._stream(dev))
+        g_world, g_mats = _transform_backward(v, vert_first, mats, g.contiguous(), ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        return g_world, None, g_mats
+
+
+def camera_grad_tree_depth(count):
+    """Additions on the longest path of the summation tree of p3d_transform_backward_cameras for `count` vertices that share a
+    matrix (csrc/transform.hip): 6 in the wave scan, ceil(R / 64) in a lane's chain over the segment's R <= ceil(count / 64) + 1
+    partial rows, 6 in the lane tree."""
+    rows = -(-int(count) // 64) + 1
+    return 12 + -(-rows // 64)
+
+
+def _transform_backward(verts, vert_first, mats, g_ndc, want_verts, want_mats):
+    """(grad of the world vertices, grad of the packed matrices or None).  Frozen cameras: p3d_transform_verts_backward, as ever.
+    Cameras that need grad: ONE pass that delivers both (the vertex gradient only when asked for)."""
+    from . import _lib
+
+    lib = _lib.load()
+    dev = verts.device
+    V, N, num = verts.shape[0], vert_first.shape[0], mats.shape[0]
+    with torch.cuda.device(dev):
+        if not want_mats:
+            out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+            if V:
+                rc = lib.p3d_transform_verts_backward(_C._ptr(verts), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g_ndc), V, N, num,
+                                                      _C._ptr(out), _C._stream(dev))
                 _lib.check(rc, "transform_verts_backward")
-        return out, None, None
+            return out, None
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev) if want_verts else None
+        g_mats = torch.empty((num, 2, 4, 4), dtype=torch.float32, device=dev)
+        nbytes = lib.p3d_transform_backward_workspace_bytes(V, N, num)
+        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        rc = lib.p3d_transform_backward_cameras(_C._ptr(verts), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g_ndc), V, N, num,
+                                                _C._ptr(out), _C._ptr(g_mats), _C._ptr(ws), nbytes, _C._stream(dev))
+        _lib.check(rc, "transform_backward_cameras")
+    return out, g_mats
 
 
 def transform_verts_to_ndc(meshes_world, world_to_view, view_to_ndc):
     """Packed world vertices of `meshes_world` -> packed NDC vertices (x, y in NDC, z = view depth), differentiable with
-    respect to the vertices.  Matrices as in rasterize_meshes_world; they must not require grad (callers take the torch
-    formulation then)."""
+    respect to the vertices and to the matrices.  Matrices as in rasterize_meshes_world."""
     verts = meshes_world.verts_packed()
     mats = _pack_matrices(torch.as_tensor(world_to_view), torch.as_tensor(view_to_ndc), len(meshes_world), verts.device)
     return _TransformVerts.apply(verts, meshes_world.mesh_to_verts_packed_first_idx().contiguous(), mats)
@@ -373,7 +396,8 @@ class _PackedVertsView:
 
 class _RasterizeMeshWorld(torch.autograd.Function):
     """world vertices -> fragments as ONE node: p3d_transform_gather_face_verts + the rasterizer; backward =
-    p3d_rasterize_meshes_backward_ex with faces (per-vertex NDC gradient) + p3d_transform_verts_backward."""
+    p3d_rasterize_meshes_backward_ex with faces (per-vertex NDC gradient) + p3d_transform_verts_backward, or
+    p3d_transform_backward_cameras when the matrices need their gradient too."""
 
     @staticmethod
     def forward(ctx, verts, faces, face_first, num_faces, vert_first, mats, nbr, static):
@@ -400,19 +424,11 @@ class _RasterizeMeshWorld(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, _g_idx, grad_zbuf, grad_bary, grad_dists):
-        from . import _lib
-
         verts, faces, vert_first, mats, face_verts, pix_to_face, cover = ctx.saved_tensors
         cover = _C.checked_cover(pix_to_face, cover)  # (P3D_CHECK=1: verified on the device before it is trusted)
         if grad_zbuf is None and grad_bary is None and grad_dists is None:
             return (None,) * 8
         V = verts.shape[0]
         g_ndc = _C._mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad_dists, *ctx.flags, cover)
-        lib = _lib.load()
-        dev = pix_to_face.device
-        with torch.cuda.device(dev):
-            g_world = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            rc = lib.p3d_transform_verts_backward(_C._ptr(verts), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g_ndc), V,
-                                                  vert_first.shape[0], mats.shape[0], _C._ptr(g_world), _C._stream(dev))
-            _lib.check(rc, "transform_verts_backward")
-        return (g_world,) + (None,) * 7
+        g_world, g_mats = _transform_backward(verts, vert_first, mats, g_ndc, ctx.needs_input_grad[0], ctx.needs_input_grad[5])
+        return (g_world,) + (None,) * 4 + (g_mats,) + (None,) * 2

@@ -18,7 +18,9 @@ fused HIP versions of this package, so that `MeshRenderer(MeshRasterizer, SoftPh
 reference classes runs on them end to end:
 
     renderer.mesh.rasterizer.MeshRasterizer.forward           -> camera transform on the PACKED vertices in one launch
-                                                                 (csrc/transform.hip) + the fused rasterize_meshes below
+                                                                 (csrc/transform.hip) + the fused rasterize_meshes below;
+                                                                 gradients to the vertices AND to camera parameters that
+                                                                 require grad (R, T, focal_length, principal_point, ...)
     renderer.mesh.rasterize_meshes.rasterize_meshes           -> fused gather + rasterizer (+ HIP clipping), one autograd node
     renderer.mesh.clip.clip_faces / convert_clipped_...       -> csrc/clip.hip
     renderer.mesh.shader.SoftPhongShader.forward              -> csrc/soft_phong.hip: shading + softmax blend in one kernel
@@ -36,8 +38,9 @@ reference classes runs on them end to end:
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
-the kernels do not).  The names are replaced in every loaded `pytorch3d.*` module that imported them (`from .x import
-f` copies), `uninstall_python_patches()` restores them.
+the kernels do not).  Cameras that require grad are NOT such an input: MeshRasterizer, PointsRasterizer and the fused
+PointsRenderer keep their fused paths and deliver the camera gradients.  The names are replaced in every
+loaded `pytorch3d.*` module that imported them (`from .x import f` copies), `uninstall_python_patches()` restores them.
 """
 import sys
 import types
@@ -355,8 +358,10 @@ def _patch_mesh_rasterizer(our_rm):
     4x4 `transform_points` (homogeneous divides, `cat`, `update_padded` -> a new Meshes): ~4 ms of small launches and
     Python per call on the bench batch, more than the rasterization itself.  Here: both matrices from the cameras, one
     kernel on the packed vertices, then the fused rasterize_meshes (its own z-clipping / culling) on a view of the mesh's
-    topology.  Falls back to the reference's forward when the cameras have no matrix form, need an `eps`, or their
-    matrices require grad (camera optimisation: torch autograd through transform_points)."""
+    topology.  Cameras that are being optimised stay on this path: their matrices are rebuilt on every call (camera_matrices)
+    and the transform's backward sums their gradient in the same pass as the vertices' (p3d_transform_backward_cameras), on
+    the un-clipped path and on the z-clip path alike.  Falls back to the reference's forward when the cameras have no matrix
+    form or need an `eps`."""
     import importlib
 
     import torch
@@ -377,7 +382,7 @@ def _patch_mesh_rasterizer(our_rm):
                     ok = cm is not None
                     if ok:
                         w2v, v2n, cam_persp, znear = cm
-                        ok = not (w2v.requires_grad or v2n.requires_grad) and w2v.device == verts.device
+                        ok = w2v.device == verts.device
             except Exception:
                 ok = False
         _count("MeshRasterizer.forward", ok)
@@ -427,8 +432,9 @@ def _patch_points_rasterizer(our_rm):
     ~1 ms of GPU time and ~50 small copies per call at 1M points) before `rasterize_points`.  Here: both matrices from the
     cameras, ONE kernel on the packed points (csrc/transform.hip: p3d_transform_verts_forward / _backward, the kernel
     MeshRasterizer.forward uses for vertices: x, y to NDC, z = view depth, as rasterizer.py:140-141 keeps it) and the
-    rasterizer's own autograd node.  Falls back to the reference's forward when the cameras have no matrix form, need an
-    `eps`, or their matrices require grad.
+    rasterizer's own autograd node; camera parameters that require grad get their gradient from the transform's backward
+    (p3d_transform_backward_cameras).  Falls back to the reference's forward when the cameras have no matrix form or need
+    an `eps`.
 
     PointsRenderer.forward (renderer/points/renderer.py:56-76) with the plain PointsRasterizer and AlphaCompositor or NormWeightedCompositor, float32
     (P, C <= 4) features, one scalar radius and K <= 16: the whole chain is pytorch3d_amd.render_points' fused node -- the image is
@@ -477,7 +483,7 @@ def _patch_points_rasterizer(our_rm):
             if cm is None:
                 return None
             w2v, v2n = cm[0], cm[1]
-            if w2v.requires_grad or v2n.requires_grad or w2v.device != pts.device:
+            if w2v.device != pts.device:
                 return None
         except Exception:
             return None
