@@ -224,6 +224,40 @@ int p3d_gather_face_verts(const float* verts, const int64_t* faces, int64_t V, i
 int p3d_scatter_face_grads(const float* grad_face_verts, const int64_t* faces, int64_t V, int64_t F, float* grad_verts,
                            p3d_stream_t stream);
 
+/* ---- face areas / normals and vertex normals (csrc/normals.hip) -------------------------------- */
+
+/* `_C.face_areas_normals_forward` (face_areas_normals.cu:14-70): verts (V,3) f32, faces (F,3) i64 -> areas (F), normals (F,3);
+ * c = (v1 - v0) x (v2 - v0), area = |c| / 2, normal = c / max(|c|, 1e-6), IEEE sqrt and division.  Vertex ids as
+ * p3d_gather_face_verts reads them: a negative id wraps once, an id still out of range makes the face NaN and nothing outside
+ * `verts` is read (V == 0: every face NaN, by a fill). */
+int p3d_face_areas_normals_forward(const float* verts, const int64_t* faces, int64_t V, int64_t F, float* areas, float* normals,
+                                   p3d_stream_t stream);
+/* Its backward up to the scatter: grad_face_verts (F,3,3), the gradient per corner, every element written; finish with
+ * p3d_scatter_face_grads or p3d_scatter_face_grads_ordered.  The reference's derivative, its c_x-for-c_y term in d/d(v1.z)
+ * (face_areas_normals.cu:183-184) included. */
+int p3d_face_areas_normals_backward(const float* grad_areas, const float* grad_normals, const float* verts, const int64_t* faces,
+                                    int64_t V, int64_t F, float* grad_face_verts, p3d_stream_t stream);
+
+/* Area-weighted vertex normals (structures/meshes.py:884-926) in gather form: no float atomics, the same bits on every run.
+ * The caller builds the incidence list once per topology: corners (offsets[V] <= 3 F entries) i32, the corners c = 3 f + j whose
+ * vertex lies in [0, V) (negative ids wrap once), sorted STABLY by vertex; offsets (V + 1) i32, vertex v owns
+ * corners[offsets[v] .. offsets[v + 1]).  3 F must fit an int32.  A list that breaks this gives wrong sums, never an access
+ * outside the rows (offsets are clamped to [0, 3 F], corner ids outside [0, 3 F) skipped; `corners` must hold offsets[V] entries).
+ *   forward: face_raw (F,3) workspace (p3d_verts_normals_forward_workspace_bytes) <- (v2 - v1) x (v0 - v1) per face;
+ *     sums (V,3) <- +0 plus face_raw[corner / 3] over the vertex's corners in list order; normals (V,3) <- sums / max(|sums|, 1e-6).
+ *     A vertex without a face gets zeros.  Keep `sums` for the backward.
+ *   backward: face_rows (F,3,3) workspace (p3d_verts_normals_backward_workspace_bytes) <- per face the gradient of its three
+ *     vertices through the normalisation ((g - n (n.g)) / |s| where |s| > 1e-6, g / 1e-6 where it is not) summed in corner order
+ *     and taken through the cross product; grad_verts (V,3) <- the rows of the vertex's corners summed in list order.
+ * Every output row is written; nothing is read before it is written. */
+size_t p3d_verts_normals_forward_workspace_bytes(int64_t F);
+size_t p3d_verts_normals_backward_workspace_bytes(int64_t F);
+int p3d_verts_normals_forward(const float* verts, const int64_t* faces, const int32_t* offsets, const int32_t* corners, int64_t V,
+                              int64_t F, float* face_raw, float* sums, float* normals, p3d_stream_t stream);
+int p3d_verts_normals_backward(const float* grad_normals, const float* verts, const int64_t* faces, const float* sums,
+                               const int32_t* offsets, const int32_t* corners, int64_t V, int64_t F, float* face_rows,
+                               float* grad_verts, p3d_stream_t stream);
+
 /* ---- world -> NDC vertex transform fused into the gather ---------------- */
 
 /* replaces MeshRasterizer.transform (pytorch3d/renderer/mesh/rasterizer.py:171-216: two batched 4x4 transform_points

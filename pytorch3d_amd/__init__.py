@@ -9,6 +9,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     sample_textures_atlas            the neighbouring steps, fused
     splatter_blend, SplatterBlender  SplatterPhongShader's blend, fused
     hard_depth_blend, soft_depth_blend  HardDepthShader's / SoftDepthShader's depth maps, one kernel each way
+    face_areas_normals, verts_normals, vert_incidence  face / vertex normals of a packed batch, fused (vertex normals without atomics)
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -18,6 +19,7 @@ from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_al
                        softmax_rgb_blend)
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
+from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401

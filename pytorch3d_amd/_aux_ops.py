@@ -1,10 +1,14 @@
-"""Four small `pytorch3d._C` operators ABOVE the rasterization boundary, as plain torch formulations.
+"""Four small `pytorch3d._C` operators ABOVE the rasterization boundary.
 
-Not part of the hot path and not HIP kernels: `Meshes.faces_normals_packed()` / `faces_areas_packed()`
-(pytorch3d/structures/meshes.py:868-880 -> ops/mesh_face_areas_normals.py:48,63) and `packed_to_padded` /
-`padded_to_packed` (ops/packed_to_padded.py:52-62,142-152) are what the reference's mesh classes and flat shading call on
-the way to the renderer.  They are F- / V-sized and run once per mesh batch; providing them lets the UNMODIFIED
-`Meshes` + `MeshRenderer(MeshRasterizer, HardFlatShader)` work through the shim without the reference's own extension.
+`Meshes.faces_normals_packed()` / `faces_areas_packed()` (pytorch3d/structures/meshes.py:868-880 ->
+ops/mesh_face_areas_normals.py:48,63) and `packed_to_padded` / `padded_to_packed` (ops/packed_to_padded.py:52-62,142-152) are what
+the reference's mesh classes and flat shading call on the way to the renderer; providing them lets the UNMODIFIED `Meshes` +
+`MeshRenderer(MeshRasterizer, HardFlatShader)` work through the shim without the reference's own extension.
+
+face_areas_normals_forward / _backward: float32 tensors on the GPU go to the HIP kernels of csrc/normals.hip
+(pytorch3d_amd/mesh_normals.py); everything else (CPU tensors, float64, empty inputs) keeps the torch formulation below.  The
+dispatch lives HERE because both shim.make_module and tests/run_reference_suite.py take the operators from this module.
+packed_to_padded / padded_to_packed are torch formulations (F- / V-sized, once per mesh batch).
 Semantics follow the reference's kernels (csrc/face_areas_normals/face_areas_normals.cu:14-70: area = |(v1 - v0) x (v2 -
 v0)| / 2, normal = cross / max(|cross|, 1e-6); csrc/packed_to_padded_tensor/*: zero padding, rows first_idxs[n] ..).
 """
@@ -16,7 +20,18 @@ def _cross(verts, faces):
     return torch.cross(v1 - v0, v2 - v0, dim=1)
 
 
+def fused_face_areas_normals(verts, faces, *grads):
+    """Do these arguments take the HIP kernels?  float32 on one GPU (faces int64), not empty."""
+    return (verts.is_cuda and verts.dtype == torch.float32 and faces.dtype == torch.int64 and faces.device == verts.device
+            and verts.dim() == 2 and faces.dim() == 2 and verts.shape[0] > 0 and faces.shape[0] > 0
+            and all(g.dtype == torch.float32 and g.device == verts.device for g in grads))
+
+
 def face_areas_normals_forward(verts, faces):
+    if fused_face_areas_normals(verts, faces):
+        from . import mesh_normals
+
+        return mesh_normals.face_areas_normals_forward(verts, faces)
     c = _cross(verts, faces)
     norm = c.norm(dim=1)
     return norm / 2.0, c / norm.clamp_min(1e-6)[:, None]
@@ -30,6 +45,10 @@ def face_areas_normals_backward(grad_areas, grad_normals, verts, faces):
     -- the derivative of area and unit normal -- with ONE deviation kept from the reference: in d/d(v1.z) the j = y term
     multiplies by c_x where the derivative has c_y (face_areas_normals.cu:183-184, the same in its CPU kernel).  A
     drop-in has to return what the reference returns."""
+    if fused_face_areas_normals(verts, faces, grad_areas, grad_normals):
+        from . import mesh_normals
+
+        return mesh_normals.face_areas_normals_backward(grad_areas, grad_normals, verts, faces)
     v0, v1, v2 = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
     a, b = v1 - v0, v2 - v0
     c = torch.cross(a, b, dim=1)

@@ -453,6 +453,74 @@ Tensor sigmoid_alpha_blend_backward(const Tensor& grad_alphas, const Tensor& alp
   return out;
 }
 
+// ---- face areas and normals (csrc/normals.hip) ---------------------------------------------------------------------------------
+void check_verts_faces(const Tensor& verts, const Tensor& faces) {
+  TORCH_CHECK(verts.dim() == 2 && verts.size(1) == 3, "verts must have shape (V, 3)");
+  TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3, "faces must have shape (F, 3)");
+  TORCH_CHECK(verts.scalar_type() == at::kFloat, "verts must be float32");
+  TORCH_CHECK(faces.scalar_type() == at::kLong, "faces must be int64");
+}
+
+std::tuple<Tensor, Tensor> face_areas_normals_forward(const Tensor& verts, const Tensor& faces) {
+  check_gpu({{&verts, "verts"}, {&faces, "faces"}});
+  check_verts_faces(verts, faces);
+  DeviceGuard guard(verts.device());
+  auto v = verts.contiguous(), f = faces.contiguous();
+  const int64_t V = v.size(0), F = f.size(0);
+  auto areas = at::empty({F}, v.options()), normals = at::empty({F, 3}, v.options());
+  if (F == 0) return {areas, normals};
+  ok(p3d_face_areas_normals_forward(V ? v.data_ptr<float>() : nullptr, f.data_ptr<int64_t>(), V, F, areas.data_ptr<float>(),
+                                    normals.data_ptr<float>(), stream_of(v)),
+     "face_areas_normals_forward");
+  return {areas, normals};
+}
+
+// the corners 3 f + j with a vertex inside [0, V) (negative ids wrap once), sorted stably by vertex: pytorch3d_amd/_C.py _sorted_corners
+Tensor sorted_corners(const Tensor& faces, int64_t V) {
+  auto flat = faces.reshape({-1});
+  flat = at::where(flat.lt(0), flat + V, flat);
+  auto hits = at::nonzero(flat.ge(0).logical_and(flat.lt(V))).squeeze(1);
+  auto order = std::get<1>(at::sort(flat.index_select(0, hits), /*stable=*/true, /*dim=*/0, /*descending=*/false));
+  return hits.index_select(0, order).contiguous();
+}
+
+// per-corner gradients (F, 3, 3) summed per vertex -> (V, 3), V > 0: pytorch3d_amd/_C.py scatter_face_grads, the one place of this
+// file that restates it (atomic adds; under the strict deterministic flag the ordered kernel over the sorted corners)
+Tensor scatter_face_grads(const Tensor& per_corner, const Tensor& faces, int64_t V, const char* who) {
+  const int64_t F = faces.size(0);
+  auto out = at::empty({V, 3}, per_corner.options());
+  const float* pc = F ? per_corner.data_ptr<float>() : nullptr;
+  const int64_t* fp = F ? faces.data_ptr<int64_t>() : nullptr;
+  if (ordered()) {
+    auto corners = sorted_corners(faces, V);
+    auto ws = workspace(p3d_scatter_face_grads_ordered_workspace_bytes(F), per_corner);
+    ok(p3d_scatter_face_grads_ordered(pc, fp, corners.numel() ? corners.data_ptr<int64_t>() : nullptr, corners.numel(), V, F,
+                                      out.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(per_corner)),
+       who);
+    return out;
+  }
+  ok(p3d_scatter_face_grads(pc, fp, V, F, out.data_ptr<float>(), stream_of(per_corner)), who);
+  return out;
+}
+
+Tensor face_areas_normals_backward(const Tensor& grad_areas, const Tensor& grad_normals, const Tensor& verts, const Tensor& faces) {
+  check_gpu({{&verts, "verts"}, {&faces, "faces"}, {&grad_areas, "grad_areas"}, {&grad_normals, "grad_normals"}});
+  check_verts_faces(verts, faces);
+  DeviceGuard guard(verts.device());
+  auto v = verts.contiguous(), f = faces.contiguous();
+  const int64_t V = v.size(0), F = f.size(0);
+  TORCH_CHECK(grad_areas.dim() == 1 && grad_areas.size(0) == F && grad_normals.dim() == 2 && grad_normals.size(0) == F && grad_normals.size(1) == 3,
+              "grad_areas must have shape (F,) and grad_normals (F, 3)");
+  auto ga = grad_areas.contiguous().to(at::kFloat), gn = grad_normals.contiguous().to(at::kFloat);
+  if (V == 0) return at::empty({0, 3}, v.options());
+  auto per_corner = at::empty({F, 3, 3}, v.options());
+  if (F > 0)
+    ok(p3d_face_areas_normals_backward(ga.data_ptr<float>(), gn.data_ptr<float>(), v.data_ptr<float>(), f.data_ptr<int64_t>(), V, F,
+                                       per_corner.data_ptr<float>(), stream_of(v)),
+       "face_areas_normals_backward");
+  return scatter_face_grads(per_corner, f, V, "face_areas_normals_backward");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -478,6 +546,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("interp_face_attrs_backward", &interp_face_attrs_backward);
   m.def("sigmoid_alpha_blend", &sigmoid_alpha_blend);
   m.def("sigmoid_alpha_blend_backward", &sigmoid_alpha_blend_backward);
+  m.def("face_areas_normals_forward", &face_areas_normals_forward);  // ext.cpp: the mesh classes' operators, float32 GPU tensors only
+  m.def("face_areas_normals_backward", &face_areas_normals_backward);
   m.attr("EPS") = py::float_(1e-6);  // constants pytorch3d/renderer/points/pulsar/renderer.py reads at import time (ext.cpp:180-185)
   m.attr("MAX_FLOAT") = py::float_(3.4e38);
   m.attr("MAX_INT") = py::int_(2147483647);

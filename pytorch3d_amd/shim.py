@@ -35,6 +35,11 @@ reference classes runs on them end to end:
                                                                  each way instead of the cat / cumsum / clamp / diff chain
     structures.meshes.Meshes.offset_verts / offset_verts_     -> one add on the packed vertices, topology shared, no host sync
                                                                  (the reference re-runs Meshes.__init__: ~70 syncs per call)
+    structures.meshes.Meshes._compute_vertex_normals          -> csrc/normals.hip: vertex normals as a gather over an incidence
+                                                                 list kept with the topology (no float atomics, same bits on
+                                                                 every run); offset_verts hands the list on, so a fitting loop
+                                                                 sorts once.  `_C.face_areas_normals_*` (face normals, flat
+                                                                 shading) are HIP kernels of the same file without any patch
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -67,12 +72,26 @@ def make_module(flavour="ctypes"):
         setattr(mod, name, getattr(src, name))
     for name in ("EPS", "MAX_FLOAT", "MAX_INT", "MAX_UINT", "MAX_USHORT", "PULSAR_MAX_GRAD_SPHERES"):
         setattr(mod, name, getattr(_ours, name))
-    # four small operators the reference's mesh classes call on the way to the renderer (face normals / areas, packed <->
-    # padded): torch formulations, not part of the hot path (pytorch3d_amd/_aux_ops.py)
+    # four small operators the reference's mesh classes call on the way to the renderer (pytorch3d_amd/_aux_ops.py): face areas /
+    # normals -- csrc/normals.hip for float32 GPU tensors, a torch formulation for everything else -- and packed <-> padded (torch)
     from . import _aux_ops
 
     for name in ("face_areas_normals_forward", "face_areas_normals_backward", "packed_to_padded", "padded_to_packed"):
         setattr(mod, name, getattr(_aux_ops, name))
+    if flavour == "pybind":
+        # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
+        def compiled(name):
+            theirs, ours = getattr(src, name), getattr(_aux_ops, name)
+
+            def call(*args):
+                return theirs(*args) if _aux_ops.fused_face_areas_normals(*args[-2:], *args[:-2]) else ours(*args)
+
+            call.__name__ = name
+            return call
+
+        for name in ("face_areas_normals_forward", "face_areas_normals_backward"):
+            if hasattr(src, name):
+                setattr(mod, name, compiled(name))
 
     def __getattr__(name):  # PEP 562: anything else is outside the hot path
         if name.startswith("__"):
@@ -301,6 +320,7 @@ def patch_reference_python():
     _patch_soft_phong_shader(our_shade)
     _patch_splatter_phong_shader(importlib.import_module(__package__ + ".splatter"))
     _patch_meshes_offset_verts()
+    _patch_meshes_vertex_normals()
     _patch_hard_and_silhouette_shaders()
     _patch_depth_shaders(our_blend)
 
@@ -920,6 +940,62 @@ def _patch_meshes_offset_verts():
     Meshes.offset_verts_ = offset_verts_
     _PATCHED.append((Meshes, "offset_verts", orig, offset_verts))
     _PATCHED.append((Meshes, "offset_verts_", orig_, offset_verts_))
+
+
+def _patch_meshes_vertex_normals():
+    """Meshes._compute_vertex_normals (structures/meshes.py:884-926), behind verts_normals_packed() and what the patched offset_verts
+    re-runs every step of a fitting loop: gather, cross product, three index_add with float atomics, normalize -- and about twice
+    that in autograd.  Here: pytorch3d_amd.mesh_normals.verts_normals, two launches each way and no atomics.  The incidence list it
+    gathers through depends on the faces alone: it is kept in the object's __dict__ (keyed by the packed faces tensor's address,
+    shape and version) and inherited by the copies the patched offset_verts makes, so a loop sorts once.  Exact Meshes, float32, on
+    the GPU, not empty; anything else goes to the reference's method."""
+    import importlib
+
+    import torch
+
+    from . import mesh_normals
+
+    Meshes = importlib.import_module("pytorch3d.structures.meshes").Meshes
+    orig = Meshes._compute_vertex_normals
+
+    def usable(self):
+        if type(self) is not Meshes or self._N == 0:
+            return False
+        v, f = self.verts_packed(), self.faces_packed()
+        if not (_is_hip_f32(v) and f.is_cuda and f.dtype == torch.int64 and f.device == v.device):
+            return False
+        empty = self.__dict__.get("_p3d_amd_isempty")  # a host sync: asked once per topology (see _patch_meshes_offset_verts)
+        if empty is None:
+            empty = bool(self.isempty())
+            self.__dict__["_p3d_amd_isempty"] = empty
+        return not empty
+
+    def incidence(self, faces, V):
+        key = (faces.data_ptr(), tuple(faces.shape), faces._version, V)
+        kept = self.__dict__.get("_p3d_amd_vert_incidence")
+        if kept is None or kept[0] != key:
+            kept = (key,) + mesh_normals.vert_incidence(faces, V)
+            self.__dict__["_p3d_amd_vert_incidence"] = kept
+        return kept[1], kept[2]
+
+    def _compute_vertex_normals(self, refresh=False):
+        if not (refresh or self._verts_normals_packed is None):
+            return
+        ok = False
+        try:
+            ok = usable(self)
+        except Exception:
+            ok = False
+        _count("Meshes._compute_vertex_normals", ok)
+        if not ok:
+            return orig(self, refresh)
+        v, f = self.verts_packed(), self.faces_packed()
+        self._verts_normals_packed = mesh_normals.verts_normals(v, f, incidence(self, f, v.shape[0]))
+
+    _compute_vertex_normals.__wrapped__ = orig
+    _compute_vertex_normals.__doc__ = orig.__doc__
+    Meshes._compute_vertex_normals = _compute_vertex_normals
+    _PATCHED.append((Meshes, "_compute_vertex_normals", orig, _compute_vertex_normals))
 
 
 def uninstall_python_patches():
