@@ -258,6 +258,51 @@ int p3d_verts_normals_backward(const float* grad_normals, const float* verts, co
                                const int32_t* offsets, const int32_t* corners, int64_t V, int64_t F, float* face_rows,
                                float* grad_verts, p3d_stream_t stream);
 
+/* ---- mesh regularisers: edge loss, uniform Laplacian, normal consistency (pytorch3d/loss/mesh_*.py) --------------
+ *
+ * Gather kernels over int32 tables the caller builds once per topology (pytorch3d_amd/mesh_losses.py: mesh_loss_topology):
+ *   edges (E,2): the unique undirected edges (lo, hi) in packed vertex ids; edge_mesh (E), vert_mesh (V), pair_mesh (P): the mesh of
+ *   each; num_edges / num_verts / num_pairs (N): the counts per mesh (a term's weight is 1.0f / count of its mesh);
+ *   adj_offsets (V + 1), adj (2 E): the vertex adjacency as a CSR, the neighbours of a vertex ascending;
+ *   pairs (P,4): the wing pairs (v0, v1, a, b) of normal consistency -- (v0, v1) an edge, a and b the vertices opposite it on two
+ *   of its faces; offsets (V + 1), slots (4 P): per vertex the slots 4 pair + role that name it, sorted stably by vertex.
+ * 4 P, 2 E and V must fit an int32; N > 0.  loss: ONE float, (sum of the terms) / N.  grad_loss: ONE float on the device.
+ * No float atomics: every sum of n terms is a tree whose shape depends on n alone, of depth
+ *   D(n) = 8 + ceil(ceil(n / 256) / 256) + 8
+ * (csrc/mesh_losses.hip), so a loss and its gradient have the same bits on every run and stream.  Forward workspaces hold one
+ * partial sum per 256 terms; every byte that is read was written by the same call.  A table that breaks its contract gives NaN
+ * or wrong numbers, never an access outside the arrays (ids are range-checked, CSR offsets clamped). */
+size_t p3d_mesh_edge_loss_forward_workspace_bytes(int64_t E);
+size_t p3d_mesh_laplacian_forward_workspace_bytes(int64_t V);
+size_t p3d_mesh_normal_consistency_forward_workspace_bytes(int64_t P);
+size_t p3d_mesh_normal_consistency_backward_workspace_bytes(int64_t P);
+/* term_e = (|x_lo - x_hi| - target_length)^2 * weight (mesh_edge_loss.py:47-52) */
+int p3d_mesh_edge_loss_forward(const float* verts, const int32_t* edges, const int32_t* edge_mesh, const int32_t* num_edges, int64_t V,
+                               int64_t E, int N, float target_length, void* workspace, size_t workspace_bytes, float* loss,
+                               p3d_stream_t stream);
+/* grad_verts (V,3), every row written: one lane per vertex walks its row of adj; 0 from an edge of length 0 (torch's norm backward) */
+int p3d_mesh_edge_loss_backward(const float* grad_loss, const float* verts, const int32_t* adj_offsets, const int32_t* adj,
+                                const int32_t* vert_mesh, const int32_t* num_edges, int64_t V, int64_t E, int N, float target_length,
+                                float* grad_verts, p3d_stream_t stream);
+/* mesh_laplacian_smoothing, method "uniform": r_v = (sum of the neighbours) / deg(v) - x_v (the sum term 0 for deg 0),
+ * term_v = |r_v| * weight; q (V,3) <- r_v weight / |r_v| (0 where the norm is 0), kept for the backward */
+int p3d_mesh_laplacian_forward(const float* verts, const int32_t* adj_offsets, const int32_t* adj, const int32_t* vert_mesh,
+                               const int32_t* num_verts, int64_t V, int64_t E, int N, float* q, void* workspace, size_t workspace_bytes,
+                               float* loss, p3d_stream_t stream);
+/* grad_verts_v = (grad_loss / N) (sum over adj(v) of q_u / deg(u) - q_v) */
+int p3d_mesh_laplacian_backward(const float* grad_loss, const float* q, const int32_t* adj_offsets, const int32_t* adj, int64_t V, int64_t E,
+                                int N, float* grad_verts, p3d_stream_t stream);
+/* term_p = (1 - cos(n0, n1)) * weight with n0 = (x_v1 - x_v0) x (x_a - x_v0), n1 = -(x_v1 - x_v0) x (x_b - x_v0) and the cosine of
+ * torch.cosine_similarity(eps=1e-8): (n0 / max(|n0|, eps)) . (n1 / max(|n1|, eps)) */
+int p3d_mesh_normal_consistency_forward(const float* verts, const int32_t* pairs, const int32_t* pair_mesh, const int32_t* num_pairs,
+                                        int64_t V, int64_t P, int N, void* workspace, size_t workspace_bytes, float* loss,
+                                        p3d_stream_t stream);
+/* workspace: (P,4,3) f32, the gradient of each pair to its four vertices; grad_verts (V,3) <- the rows of the vertex's slots summed
+ * in list order, every row written */
+int p3d_mesh_normal_consistency_backward(const float* grad_loss, const float* verts, const int32_t* pairs, const int32_t* pair_mesh,
+                                         const int32_t* num_pairs, const int32_t* offsets, const int32_t* slots, int64_t V, int64_t P,
+                                         int N, void* workspace, size_t workspace_bytes, float* grad_verts, p3d_stream_t stream);
+
 /* ---- world -> NDC vertex transform fused into the gather ---------------- */
 
 /* replaces MeshRasterizer.transform (pytorch3d/renderer/mesh/rasterizer.py:171-216: two batched 4x4 transform_points

@@ -10,6 +10,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     splatter_blend, SplatterBlender  SplatterPhongShader's blend, fused
     hard_depth_blend, soft_depth_blend  HardDepthShader's / SoftDepthShader's depth maps, one kernel each way
     face_areas_normals, verts_normals, vert_incidence  face / vertex normals of a packed batch, fused (vertex normals without atomics)
+    mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, mesh_loss_topology  the regularisers of a fitting loop, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -19,6 +20,8 @@ from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_al
                        softmax_rgb_blend)
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
+from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
+                          mesh_normal_consistency)
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401

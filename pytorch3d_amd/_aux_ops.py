@@ -1,4 +1,4 @@
-"""Four small `pytorch3d._C` operators ABOVE the rasterization boundary.
+"""Five small `pytorch3d._C` operators ABOVE the rasterization boundary.
 
 `Meshes.faces_normals_packed()` / `faces_areas_packed()` (pytorch3d/structures/meshes.py:868-880 ->
 ops/mesh_face_areas_normals.py:48,63) and `packed_to_padded` / `padded_to_packed` (ops/packed_to_padded.py:52-62,142-152) are what
@@ -9,6 +9,8 @@ face_areas_normals_forward / _backward: float32 tensors on the GPU go to the HIP
 (pytorch3d_amd/mesh_normals.py); everything else (CPU tensors, float64, empty inputs) keeps the torch formulation below.  The
 dispatch lives HERE because both shim.make_module and tests/run_reference_suite.py take the operators from this module.
 packed_to_padded / padded_to_packed are torch formulations (F- / V-sized, once per mesh batch).
+mesh_normal_consistency_find_verts is the host operator behind the reference's `pytorch3d.loss.mesh_normal_consistency`
+(mesh_normal_consistency.py:104): vectorised torch on the CPU.
 Semantics follow the reference's kernels (csrc/face_areas_normals/face_areas_normals.cu:14-70: area = |(v1 - v0) x (v2 -
 v0)| / 2, normal = cross / max(|cross|, 1e-6); csrc/packed_to_padded_tensor/*: zero padding, rows first_idxs[n] ..).
 """
@@ -67,6 +69,21 @@ def face_areas_normals_backward(grad_areas, grad_normals, verts, faces):
     out = torch.zeros_like(verts)
     out.index_add_(0, faces.reshape(-1), g.reshape(-1, 3))
     return out
+
+
+def mesh_normal_consistency_find_verts(edge_num):
+    """`_C.mesh_normal_consistency_find_verts` (mesh_normal_consistency/mesh_normal_consistency_cpu.cpp): edge_num (E,) int64 on the
+    CPU, the number of entries each edge owns in an array sorted by edge -> (P, 2) int64 on the CPU, P = sum e (e - 1) / 2: with
+    o_e = sum of edge_num[:e], every (o_e + i, o_e + j) with i < j < edge_num[e].  The reference names no order; here: edges
+    ascending, then j, then i.  Vectorised torch (pytorch3d_amd/mesh_losses.py: find_pair_positions)."""
+    if edge_num.is_cuda:
+        raise RuntimeError("edge_num must be a CPU tensor: mesh_normal_consistency_find_verts is a host operator (the reference has "
+                           "no GPU version of it either).")
+    if edge_num.dim() != 1 or edge_num.dtype != torch.int64:
+        raise RuntimeError("mesh_normal_consistency_find_verts: edge_num must be an int64 vector")
+    from . import mesh_losses
+
+    return mesh_losses.find_pair_positions(edge_num)
 
 
 def packed_to_padded(inputs_packed, first_idxs, max_size):

@@ -62,6 +62,17 @@ _SIGNATURES = {
     "p3d_verts_normals_backward_workspace_bytes": (c_size, [c_i64]),
     "p3d_verts_normals_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     "p3d_verts_normals_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
+    "p3d_mesh_edge_loss_forward_workspace_bytes": (c_size, [c_i64]),
+    "p3d_mesh_laplacian_forward_workspace_bytes": (c_size, [c_i64]),
+    "p3d_mesh_normal_consistency_forward_workspace_bytes": (c_size, [c_i64]),
+    "p3d_mesh_normal_consistency_backward_workspace_bytes": (c_size, [c_i64]),
+    "p3d_mesh_edge_loss_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_size, c_ptr, c_ptr]),
+    "p3d_mesh_edge_loss_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_ptr]),
+    "p3d_mesh_laplacian_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr, c_ptr]),
+    "p3d_mesh_laplacian_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr]),
+    "p3d_mesh_normal_consistency_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_size, c_ptr, c_ptr]),
+    "p3d_mesh_normal_consistency_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_size,
+                                                     c_ptr, c_ptr]),
     "p3d_transform_gather_face_verts": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
     "p3d_transform_verts_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
     "p3d_transform_verts_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),

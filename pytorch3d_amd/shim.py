@@ -40,6 +40,11 @@ reference classes runs on them end to end:
                                                                  every run); offset_verts hands the list on, so a fitting loop
                                                                  sorts once.  `_C.face_areas_normals_*` (face normals, flat
                                                                  shading) are HIP kernels of the same file without any patch
+    loss.mesh_edge_loss / mesh_laplacian_smoothing ("uniform") / mesh_normal_consistency -> csrc/mesh_losses.hip: one autograd
+                                                                 node each over tables kept with the topology, gathers and
+                                                                 fixed-tree sums (no float atomics, no host round trip);
+                                                                 without patch_python the reference's own normal consistency
+                                                                 runs too (`_C.mesh_normal_consistency_find_verts` on the host)
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -72,11 +77,13 @@ def make_module(flavour="ctypes"):
         setattr(mod, name, getattr(src, name))
     for name in ("EPS", "MAX_FLOAT", "MAX_INT", "MAX_UINT", "MAX_USHORT", "PULSAR_MAX_GRAD_SPHERES"):
         setattr(mod, name, getattr(_ours, name))
-    # four small operators the reference's mesh classes call on the way to the renderer (pytorch3d_amd/_aux_ops.py): face areas /
-    # normals -- csrc/normals.hip for float32 GPU tensors, a torch formulation for everything else -- and packed <-> padded (torch)
+    # five small operators the reference's mesh classes and losses call (pytorch3d_amd/_aux_ops.py): face areas / normals --
+    # csrc/normals.hip for float32 GPU tensors, a torch formulation for everything else --, packed <-> padded (torch) and the host
+    # operator of pytorch3d.loss.mesh_normal_consistency (vectorised torch on the CPU)
     from . import _aux_ops
 
-    for name in ("face_areas_normals_forward", "face_areas_normals_backward", "packed_to_padded", "padded_to_packed"):
+    for name in ("face_areas_normals_forward", "face_areas_normals_backward", "packed_to_padded", "padded_to_packed",
+                 "mesh_normal_consistency_find_verts"):
         setattr(mod, name, getattr(_aux_ops, name))
     if flavour == "pybind":
         # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
@@ -323,6 +330,41 @@ def patch_reference_python():
     _patch_meshes_vertex_normals()
     _patch_hard_and_silhouette_shaders()
     _patch_depth_shaders(our_blend)
+    _patch_mesh_losses(wrap)
+
+
+def _patch_mesh_losses(wrap):
+    """pytorch3d.loss.mesh_edge_loss / mesh_laplacian_smoothing / mesh_normal_consistency (loss/mesh_*.py), what every mesh-fitting
+    tutorial of the reference adds to the rendered loss each step -> pytorch3d_amd.mesh_losses: one autograd node each over tables
+    kept with the topology (csrc/mesh_losses.hip: gathers and fixed-tree sums, no float atomics, no host round trip).  The tables
+    live in the object's __dict__ and are inherited by the copies the patched offset_verts makes, so a loop builds them once.  Exact
+    Meshes, float32, on the GPU, not empty, no face that names one vertex twice and, for the Laplacian, method "uniform"; anything else
+    goes to the reference's function."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".mesh_losses")
+    Meshes = importlib.import_module("pytorch3d.structures.meshes").Meshes
+    try:
+        importlib.import_module("pytorch3d.loss")  # every module that copied the names must be loaded before rebinding
+    except ImportError:  # a reference checkout without its loss package: nothing to patch
+        return
+
+    def usable(meshes, *args, **kwargs):
+        if type(meshes) is not Meshes or meshes._N == 0 or not _is_hip_f32(meshes.verts_packed()):
+            return False
+        empty = meshes.__dict__.get("_p3d_amd_isempty")  # a host sync: asked once per topology (see _patch_meshes_offset_verts)
+        if empty is None:
+            empty = bool(meshes.isempty())
+            meshes.__dict__["_p3d_amd_isempty"] = empty
+        # (the tables are built here on the first call and kept; a face that names one vertex twice goes to the reference)
+        return not empty and not ours.topology_of(meshes).repeated
+
+    def uniform(meshes, method="uniform"):
+        return method == "uniform" and usable(meshes)
+
+    for fname, ok in (("mesh_edge_loss", usable), ("mesh_laplacian_smoothing", uniform), ("mesh_normal_consistency", usable)):
+        orig = getattr(importlib.import_module("pytorch3d.loss." + fname), fname)
+        _replace_everywhere(orig, wrap(fname, orig, getattr(ours, fname), ok))
 
 
 def camera_matrices(cameras, kwargs):

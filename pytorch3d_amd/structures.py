@@ -88,7 +88,8 @@ class PackedMeshes:
         return torch.repeat_interleave(torch.arange(self._N, device=self.device), self._num_verts)
 
     def update_verts_packed(self, new_verts_packed):
-        """Same topology, new vertex positions (like Meshes.update_padded, for camera transforms)."""
+        """Same topology, new vertex positions (like Meshes.update_padded, for camera transforms).  What is kept with the topology
+        (the tables of pytorch3d_amd.mesh_losses) is handed on: the copy shares the __dict__ entries."""
         out = object.__new__(PackedMeshes)
         out.__dict__.update(self.__dict__)
         out._verts_packed = new_verts_packed
