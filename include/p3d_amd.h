@@ -712,6 +712,51 @@ int p3d_interp_face_attrs_backward_ordered(const int64_t* pix_to_face, const flo
                                            int64_t F, int64_t D, float* grad_barycentric_coords, float* grad_face_attrs,
                                            void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 
+/* ---- nearest neighbours and chamfer distance (pytorch3d/ops/knn.py, pytorch3d/loss/chamfer.py) ------------------------
+ *
+ * p1 (N,P1,D), p2 (N,P2,D) contiguous f32; lengths1 / lengths2 (N) i64 or NULL (every cloud full; a length is clamped to
+ * [0, P]); norm 1 (L1) or 2 (squared L2); D in {2, 3} and 1 <= K <= P3D_KNN_MAX_K, otherwise P3D_ERR_UNSUPPORTED (the caller
+ * owns a formulation for the rest: pytorch3d_amd/knn.py).
+ * Forward: for n and i < lengths1[n] the min(K, lengths2[n]) smallest dist(p1[n,i], p2[n,j]), j < lengths2[n], ascending by
+ * (dist, j) -- a tie goes to the smaller index.  dist: per coordinate the difference, then |.| or its square, accumulated in
+ * coordinate order, one float32 operation each, NOT fused (the library is built with -ffp-contract=off; every instantiation the
+ * same).  idx (N,P1,K) i64, dists (N,P1,K) f32: every entry is written, 0 in both for rows i >= lengths1[n] and slots
+ * k >= lengths2[n]; no memset in front.  A NaN distance is never selected (a slot that finds nothing holds idx 0, dist +inf).
+ * One lane per query, p2 staged in LDS tiles of P3D_KNN_TILE points (csrc/knn.hip). */
+#define P3D_KNN_MAX_K 32
+#define P3D_KNN_TILE 512
+int p3d_knn_points_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
+                           int64_t P2, int D, int K, int norm, int64_t* idx, float* dists, p3d_stream_t stream);
+/* One direction of chamfer_distance: the K = 1 forward (idx, dists (N,P1), masked as above) and, in the same launch, the terms
+ * dists[n,i] * weights[n] (weights (N) f32 or NULL) summed per wave; a second small launch sums a cloud's partials:
+ * sums (N) f32 <- the cloud's sum, divided by max(lengths1[n], 1) when point_mean != 0.  No float atomic: the sum of a cloud's P1
+ * terms is a tree whose shape depends on P1 alone (6 butterfly rounds in a wave of 64 queries, lane t of one block of 256 adds the
+ * partials t, t + 256, ... ascending, 8 more rounds), depth D(P1) = 6 + ceil(ceil(P1 / 64) / 256) + 8.
+ * workspace: p3d_chamfer_forward_workspace_bytes(N, P1) bytes, every byte read was written by the same call. */
+size_t p3d_chamfer_forward_workspace_bytes(int64_t N, int64_t P1);
+int p3d_chamfer_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, const float* weights,
+                        int64_t N, int64_t P1, int64_t P2, int D, int norm, int point_mean, int64_t* idx, float* dists, float* sums,
+                        void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+/* Backward (knn_cpu.cpp:101-126).  For i < lengths1[n], k < min(K, lengths2[n]), j = idx[n,i,k] (an entry outside [0, P2) is
+ * skipped) and g = grad_dists[n,i,k] (NULL: 1) * cloud_scale[n] (NULL: 1):
+ *   norm 2: grad_p1[n,i] += 2 g (p1[n,i] - p2[n,j]);  norm 1: grad_p1[n,i] += g s, s = +1 where p1 > p2 and -1 otherwise;
+ *   grad_p2[n,j] gets the negative.
+ * grad_p1 (N,P1,D), NULL to skip: a gather, one lane per (n, i), k ascending, every entry written.  grad_p2 (N,P2,D), NULL to
+ * skip: float atomics, the D values of one hit from adjacent lanes; zero-filled first unless flags has P3D_KNN_ACCUMULATE_P2
+ * (then the hits are added to what grad_p2 holds). */
+#define P3D_KNN_ACCUMULATE_P2 1u
+int p3d_knn_points_backward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, const int64_t* idx,
+                            const float* grad_dists, const float* cloud_scale, int64_t N, int64_t P1, int64_t P2, int D, int K,
+                            int norm, unsigned flags, float* grad_p1, float* grad_p2, p3d_stream_t stream);
+/* The grad_p2 part of p3d_knn_points_backward in a fixed order (see "deterministic backwards" above): sorted_samples holds the
+ * linear indices into (N,P1,K) of the valid hits, sorted stably by n * P2 + idx. */
+size_t p3d_knn_points_ordered_backward_workspace_bytes(int64_t num_sorted);
+int p3d_knn_points_ordered_backward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                                    const int64_t* idx, const float* grad_dists, const float* cloud_scale,
+                                    const int64_t* sorted_samples, int64_t num_sorted, int64_t N, int64_t P1, int64_t P2, int D, int K,
+                                    int norm, unsigned flags, float* grad_p2, void* workspace, size_t workspace_bytes,
+                                    p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

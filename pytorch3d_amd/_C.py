@@ -1004,6 +1004,77 @@ def sigmoid_alpha_blend_backward(grad_alphas, alphas, distances, pix_to_face, si
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# nearest neighbours (csrc/knn.hip).  NOT in HOT_PATH_EXPORTS: the shim module keeps `pytorch3d._C.knn_points_idx` a stub that
+# raises; pytorch3d_amd.knn.knn_points (and, under patch_python, the reference's knn_points) come here.
+def _knn_check(p1, p2, lengths1, lengths2, K, who):
+    dev = _same_device(("p1", p1), ("p2", p2))
+    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != p2.shape[0] or p1.shape[2] != p2.shape[2]:
+        raise RuntimeError(f"{who}: p1 (N, P1, D) and p2 (N, P2, D) must share N and D")
+    if p1.shape[2] not in (2, 3) or not 1 <= K <= _lib.KNN_MAX_K:
+        raise RuntimeError(f"{who}: the kernels take D in (2, 3) and 1 <= K <= {_lib.KNN_MAX_K}; pytorch3d_amd.knn.knn_points has a "
+                           "torch formulation for the rest")
+    out = []
+    for name, t in (("lengths1", lengths1), ("lengths2", lengths2)):
+        if t is not None:
+            _same_device(("p1", p1), (name, t))
+            if t.shape != (p1.shape[0],):
+                raise RuntimeError(f"{who}: {name} must have shape (N,)")
+            t = _c(t, torch.int64)
+        out.append(t)
+    return dev, out[0], out[1]
+
+
+def knn_points_idx(p1, p2, lengths1, lengths2, norm, K, version=-1, _out=None):
+    """KNearestNeighborIdx (knn.h): (idx (N, P1, K) int64, dists (N, P1, K)), sorted ascending by (dist, j); `version` is ignored.
+    lengths1 / lengths2 may be None (every cloud full).  _out (not part of the reference's signature): (idx, dists) buffers to write
+    into -- the kernel writes every entry."""
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    K = int(K)
+    dev, lengths1, lengths2 = _knn_check(p1, p2, lengths1, lengths2, K, "knn_points_idx")
+    p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
+    N, P1, D = p1.shape
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if _out is None:
+            idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+            dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+        else:
+            idx, dists = _out
+            if (idx.shape != (N, P1, K) or dists.shape != (N, P1, K) or idx.dtype != torch.int64 or dists.dtype != torch.float32
+                    or not idx.is_contiguous() or not dists.is_contiguous() or idx.device != dev or dists.device != dev):
+                raise RuntimeError("knn_points_idx: _out must be contiguous (N, P1, K) int64 and float32 tensors on the inputs' GPU")
+        rc = lib.p3d_knn_points_forward(_ptr(p1), _ptr(p2), _ptr(lengths1), _ptr(lengths2), N, P1, p2.shape[1], D, K, int(norm),
+                                        _ptr(idx), _ptr(dists), _stream(dev))
+        _lib.check(rc, "knn_points_idx")
+    return idx, dists
+
+
+def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _needs=(True, True)):
+    """KNearestNeighborBackward (knn.h): (grad_p1 (N, P1, D), grad_p2 (N, P2, D)).  grad_p1 is a gather; grad_p2 a scatter with
+    float atomics or, under torch.use_deterministic_algorithms(True), the ordered sum.  _needs (not part of the reference's
+    signature): which of the two to compute (the other is None)."""
+    from . import knn as _knn
+
+    if norm not in (1, 2):
+        raise ValueError("Support for 1 or 2 norm.")
+    _same_device(("p1", p1), ("idxs", idxs), ("grad_dists", grad_dists))
+    if idxs.dim() != 3 or idxs.shape[:2] != p1.shape[:2] or grad_dists.shape != idxs.shape:
+        raise RuntimeError("knn_points_backward: idxs and grad_dists must have shape (N, P1, K)")
+    K = int(idxs.shape[2])
+    dev, lengths1, lengths2 = _knn_check(p1, p2, lengths1, lengths2, max(1, min(K, _lib.KNN_MAX_K)), "knn_points_backward")
+    p1, p2, idxs = _c(p1, torch.float32), _c(p2, torch.float32), _c(idxs, torch.int64)
+    g = grad_dists.to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        grad_p1 = torch.empty_like(p1) if _needs[0] else None
+        grad_p2 = torch.empty_like(p2) if _needs[1] else None
+        if K == 0:
+            return (None if grad_p1 is None else grad_p1.zero_()), (None if grad_p2 is None else grad_p2.zero_())
+        _knn.backward_kernels(p1, p2, lengths1, lengths2, idxs, K, int(norm), g, None, grad_p1, grad_p2)
+    return grad_p1, grad_p2
+
+
 HOT_PATH_EXPORTS = (
     "rasterize_meshes", "rasterize_meshes_backward", "_rasterize_meshes_naive", "_rasterize_meshes_coarse",
     "_rasterize_meshes_fine", "rasterize_points", "rasterize_points_backward", "_rasterize_points_naive",

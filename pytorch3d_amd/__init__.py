@@ -11,6 +11,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     hard_depth_blend, soft_depth_blend  HardDepthShader's / SoftDepthShader's depth maps, one kernel each way
     face_areas_normals, verts_normals, vert_incidence  face / vertex normals of a packed batch, fused (vertex normals without atomics)
     mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, mesh_loss_topology  the regularisers of a fitting loop, fused
+    knn_points, knn_gather, chamfer_distance  nearest neighbours between point clouds and the chamfer loss on top, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -18,8 +19,10 @@ if it is missing (no CPU / eager fallback exists).
 from . import _C  # noqa: F401
 from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_alpha_blend, soft_depth_blend,  # noqa: F401
                        softmax_rgb_blend)
+from .chamfer import chamfer_distance  # noqa: F401
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
+from .knn import knn_gather, knn_points  # noqa: F401
 from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
                           mesh_normal_consistency)
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401

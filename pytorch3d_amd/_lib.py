@@ -25,6 +25,9 @@ RASTER_COVER_LIST = 1
 RASTER_CUDA_TIE_ORDER = 2
 BWD_COVER_HAS_LIST = 1
 BWD_MAKE_FACE_PRE = 2
+KNN_MAX_K = 32           # P3D_KNN_MAX_K
+KNN_TILE = 512           # P3D_KNN_TILE: p2 points staged per step
+KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
 
 _SIGNATURES = {
     # name: (restype, [argtypes])
@@ -173,6 +176,16 @@ _SIGNATURES = {
     "p3d_interp_face_attrs_backward_ordered_workspace_bytes": (c_size, [c_i64, c_i64]),
     "p3d_interp_face_attrs_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr,
                                                        c_size, c_ptr]),
+    # nearest neighbours and chamfer distance (csrc/knn.hip; the ordered scatter: csrc/ordered_bwd.hip)
+    "p3d_knn_points_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    "p3d_chamfer_forward_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "p3d_chamfer_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
+                                    c_size, c_ptr]),
+    "p3d_knn_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_uint,
+                                        c_ptr, c_ptr, c_ptr]),
+    "p3d_knn_points_ordered_backward_workspace_bytes": (c_size, [c_i64]),
+    "p3d_knn_points_ordered_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int,
+                                                c_int, c_int, c_uint, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

@@ -1,0 +1,253 @@
+"""chamfer_distance on the HIP kernels of csrc/knn.hip (pytorch3d/loss/chamfer.py).
+
+    chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None, batch_reduction="mean",
+                     point_reduction="mean", norm=2, single_directional=False, abs_cosine=True) -> (loss, loss_normals)
+
+The reference's signature, validation and return shapes.  x and y are (N, P, D) tensors or anything with points_padded() /
+num_points_per_cloud() / normals_padded() (the reference's Pointclouds).
+
+Without normals and with point_reduction "sum" or "mean", float32 GPU clouds with D in {2, 3} are ONE autograd node: per direction
+one launch of the K = 1 nearest-neighbour kernel that also applies the length mask and the cloud's weight and sums each wave, one
+small launch that adds a cloud's partial sums in a fixed order (no float atomic in the forward), and in the backward a gather for the
+near side and a scatter for the far side.  The reference's chain for the same loss is two KNN calls, about thirty small torch
+launches and three host syncs; here nothing waits for the device, except the reference's own value checks on `weights` when weights
+are given.  (A length above P is clamped by the kernels; the "A length value was too long" check runs for CPU tensors only, where it
+costs nothing.)
+
+With normals, or point_reduction "max" / None, and for every input the kernels do not take (CPU, float64, other D), the indices and
+distances come from pytorch3d_amd.knn.knn_points -- kernels where they apply, its torch formulation otherwise -- and the rest is
+torch arithmetic differentiated by autograd.
+"""
+import torch
+import torch.nn.functional as F
+
+from . import _C, _lib
+from . import knn as _knn
+
+
+def _validate_reductions(batch_reduction, point_reduction):
+    if batch_reduction is not None and batch_reduction not in ["mean", "sum"]:
+        raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
+    if point_reduction is not None and point_reduction not in ["mean", "sum", "max"]:
+        raise ValueError('point_reduction must be one of ["mean", "sum", "max"] or None')
+    if point_reduction is None and batch_reduction is not None:
+        raise ValueError("Batch reduction must be None if point_reduction is None")
+
+
+def _is_cloud_object(points):
+    return all(callable(getattr(points, a, None)) for a in ("points_padded", "num_points_per_cloud", "normals_padded"))
+
+
+def _cloud_input(points, lengths, normals):
+    """(X (N, P, D), lengths (N,) or None for `every cloud full`, normals or None)."""
+    if _is_cloud_object(points):
+        return points.points_padded(), points.num_points_per_cloud(), points.normals_padded()
+    if not torch.is_tensor(points):
+        raise ValueError("The input pointclouds should be either Pointclouds objects or torch.Tensor of shape "
+                         "(minibatch, num_points, 3).")
+    if points.ndim != 3:
+        raise ValueError("Expected points to be of shape (N, P, D)")
+    if lengths is not None:
+        if lengths.ndim != 1 or lengths.shape[0] != points.shape[0]:
+            raise ValueError("Expected lengths to be of shape (N,)")
+        if not lengths.is_cuda and lengths.numel() and lengths.max() > points.shape[1]:
+            raise ValueError("A length value was too long")
+    if normals is not None and normals.ndim != 3:
+        raise ValueError("Expected normals to be of shape (N, P, 3")
+    return points, lengths, normals
+
+
+def fused_path(x, y, x_normals, y_normals, point_reduction):
+    """Whether chamfer_distance on these (tensor) inputs is the single autograd node over the kernels."""
+    return (x_normals is None and y_normals is None and point_reduction in ("sum", "mean") and _knn.kernel_path(x, y, 1))
+
+
+# ---- the single node ---------------------------------------------------------------------------------------------------------------
+def _direction_forward(lib, a, b, la, lb, weights, norm, point_mean):
+    N, P1, D = a.shape
+    dev = a.device
+    idx = torch.empty((N, P1), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1), dtype=torch.float32, device=dev)
+    sums = torch.empty((N,), dtype=torch.float32, device=dev)
+    nbytes = lib.p3d_chamfer_forward_workspace_bytes(N, P1)
+    ws = _C._workspace(nbytes, dev)
+    rc = lib.p3d_chamfer_forward(_C._ptr(a), _C._ptr(b), _C._ptr(la), _C._ptr(lb), _C._ptr(weights), N, P1, b.shape[1], D, norm,
+                                 1 if point_mean else 0, _C._ptr(idx), _C._ptr(dists), _C._ptr(sums), _C._ptr(ws), nbytes, _C._stream(dev))
+    _lib.check(rc, "chamfer_distance forward")
+    return idx, dists, sums
+
+
+class _ChamferFused(torch.autograd.Function):
+    """x, y float32 on one GPU, D in {2, 3}; lengths int64 on that GPU or None; weights float32 (N,) on that GPU or None.
+    Returns the per-cloud losses (N,) for batch_reduction None, else a 0-dim tensor."""
+
+    @staticmethod
+    def forward(ctx, x, y, x_lengths, y_lengths, weights, norm, point_mean, single_directional, batch_reduction):
+        x, y = _C._c(x, torch.float32), _C._c(y, torch.float32)
+        lib, dev, N = _lib.load(), x.device, x.shape[0]
+        with torch.cuda.device(dev):
+            idx_x, dists_x, per_cloud = _direction_forward(lib, x, y, x_lengths, y_lengths, weights, norm, point_mean)
+            idx_y = None
+            if not single_directional:
+                idx_y, dists_y, sums_y = _direction_forward(lib, y, x, y_lengths, x_lengths, weights, norm, point_mean)
+                per_cloud = per_cloud + sums_y
+            div = None
+            if batch_reduction is None:
+                out = per_cloud
+            else:
+                out = per_cloud.sum()
+                if batch_reduction == "mean":
+                    div = weights.sum() if weights is not None else float(max(N, 1))
+                    out = out / div
+        ctx.save_for_backward(x, y, idx_x, idx_y)
+        ctx.aux = (x_lengths, y_lengths, weights, div)
+        ctx.norm, ctx.point_mean, ctx.single, ctx.reduced = norm, point_mean, single_directional, batch_reduction is not None
+        return out
+
+    @staticmethod
+    def _scale(up, weights, lengths, P, point_mean):
+        """What a point's distance is multiplied with on its way into the loss, per cloud: upstream * weight / length."""
+        s = up if weights is None else up * weights
+        if point_mean:  # the forward's divisor: the length clamped into [1, P]; a cloud without a length tensor is full
+            s = s / (float(max(P, 1)) if lengths is None else lengths.clamp(1, max(P, 1)))
+        return s.to(torch.float32).contiguous()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, y, idx_x, idx_y = ctx.saved_tensors
+        x_lengths, y_lengths, weights, div = ctx.aux
+        N, dev = x.shape[0], x.device
+        need_x, need_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        with torch.cuda.device(dev):
+            up = grad_out.to(device=dev, dtype=torch.float32)
+            if ctx.reduced:
+                up = up.reshape(1).expand(N)
+                if div is not None:
+                    up = up / div
+            sx = _ChamferFused._scale(up, weights, x_lengths, x.shape[1], ctx.point_mean)
+            sy = _ChamferFused._scale(up, weights, y_lengths, y.shape[1], ctx.point_mean)
+            gx = torch.empty_like(x) if need_x else None
+            gy = torch.empty_like(y) if need_y else None
+            run = _knn.backward_kernels
+            # x -> y: x is the near side (gather), y the far side (scatter); y -> x the other way round.  The gathers write every
+            # entry, the scatters then add to them.
+            if need_x:
+                run(x, y, x_lengths, y_lengths, idx_x, 1, ctx.norm, None, sx, gx, None)
+            if ctx.single:
+                if need_y:
+                    run(x, y, x_lengths, y_lengths, idx_x, 1, ctx.norm, None, sx, None, gy)
+            else:
+                if need_y or need_x:
+                    run(y, x, y_lengths, x_lengths, idx_y, 1, ctx.norm, None, sy, gy, gx, accumulate_p2=True)
+                if need_y:
+                    run(x, y, x_lengths, y_lengths, idx_x, 1, ctx.norm, None, sx, None, gy, accumulate_p2=True)
+        return gx, gy, None, None, None, None, None, None, None
+
+
+# ---- the general form ------------------------------------------------------------------------------------------------------------
+def _rows_outside(lengths, N, P, device):
+    return None if lengths is None else torch.arange(P, device=device)[None, :] >= lengths.to(device)[:, None]
+
+
+def _one_direction(x, y, x_lengths, y_lengths, x_normals, y_normals, weights, zero_weights, point_reduction, norm, abs_cosine):
+    """The terms of x against y: (distances, normal terms or None), reduced over the points as asked."""
+    N, P1, _ = x.shape
+    if zero_weights:
+        # the reference's own value for weights that are all zero, for both results and whatever the reductions: zeros that still
+        # hang on x, shaped by its broadcast of (N,) against (N, 1)
+        zeros = (x.sum((1, 2)) * weights.view(N, 1)) * 0.0
+        return zeros, zeros
+    with_normals = x_normals is not None and y_normals is not None
+    nn = _knn.knn_points(x, y, lengths1=x_lengths, lengths2=y_lengths, norm=norm, K=1)
+    cham = nn.dists[..., 0]  # (N, P1); rows past a cloud's length are 0 already
+    outside = _rows_outside(x_lengths, N, P1, x.device)
+    if weights is not None:
+        cham = cham * weights.view(N, 1)
+    cham_normals = None
+    if with_normals:
+        near = _knn.knn_gather(y_normals, nn.idx, y_lengths)[..., 0, :]
+        cosine = F.cosine_similarity(x_normals, near, dim=2, eps=1e-6)
+        cham_normals = 1 - (cosine.abs() if abs_cosine else cosine)
+        if outside is not None:
+            cham_normals = cham_normals.masked_fill(outside, 0.0)
+        if weights is not None:
+            cham_normals = cham_normals * weights.view(N, 1)
+    if point_reduction == "max":
+        cham = cham.max(1).values
+    elif point_reduction is not None:
+        cham = cham.sum(1)
+        if with_normals:
+            cham_normals = cham_normals.sum(1)
+        if point_reduction == "mean":
+            count = float(max(P1, 1)) if x_lengths is None else x_lengths.clamp(min=1)
+            cham = cham / count
+            if with_normals:
+                cham_normals = cham_normals / count
+    return cham, cham_normals
+
+
+def _reduce_batch(loss, loss_normals, weights, zero_weights, batch_reduction):
+    if batch_reduction is None:
+        return loss, loss_normals
+    N = loss.shape[0]
+    loss = loss.sum()
+    if loss_normals is not None:
+        loss_normals = loss_normals.sum()
+    if batch_reduction == "mean":
+        if weights is None:
+            div = max(N, 1)
+        else:
+            div = 1 if zero_weights else weights.sum()
+        loss = loss / div
+        if loss_normals is not None:
+            loss_normals = loss_normals / div
+    return loss, loss_normals
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
+                     batch_reduction="mean", point_reduction="mean", norm: int = 2, single_directional: bool = False,
+                     abs_cosine: bool = True):
+    """Chamfer distance between the clouds x and y; see the module docstring.  Returns (loss, loss_normals): reduced tensors, or for
+    point_reduction None the per-point terms -- (N, P1) for single_directional, else the pair ((N, P1), (N, P2)); loss_normals is None
+    without normals (and for "max")."""
+    _validate_reductions(batch_reduction, point_reduction)
+    if not ((norm == 1) or (norm == 2)):
+        raise ValueError("Support for 1 or 2 norm.")
+    if point_reduction == "max" and (x_normals is not None or y_normals is not None):
+        raise ValueError('Normals must be None if point_reduction is "max"')
+    x, x_lengths, x_normals = _cloud_input(x, x_lengths, x_normals)
+    y, y_lengths, y_normals = _cloud_input(y, y_lengths, y_normals)
+    N, _, D = x.shape
+    if y.shape[0] != N or y.shape[2] != D:
+        raise ValueError("y does not have the correct shape.")
+    zero_weights = False
+    if weights is not None:
+        if weights.size(0) != N:
+            raise ValueError("weights must be of shape (N,).")
+        if not (weights >= 0).all():
+            raise ValueError("weights cannot be negative.")
+        zero_weights = bool(weights.sum() == 0.0)
+
+    if not zero_weights and fused_path(x, y, x_normals, y_normals, point_reduction):
+        dev = x.device
+        xl = None if x_lengths is None else x_lengths.to(device=dev, dtype=torch.int64).contiguous()
+        yl = None if y_lengths is None else y_lengths.to(device=dev, dtype=torch.int64).contiguous()
+        w = None if weights is None else weights.to(device=dev, dtype=torch.float32).contiguous()
+        loss = _ChamferFused.apply(x, y, xl, yl, w, int(norm), point_reduction == "mean", bool(single_directional), batch_reduction)
+        return loss, None
+
+    cham_x, normals_x = _one_direction(x, y, x_lengths, y_lengths, x_normals, y_normals, weights, zero_weights, point_reduction, norm, abs_cosine)
+    if single_directional:
+        loss, loss_normals = cham_x, normals_x
+    else:
+        cham_y, normals_y = _one_direction(y, x, y_lengths, x_lengths, y_normals, x_normals, weights, zero_weights, point_reduction, norm, abs_cosine)
+        if point_reduction == "max":
+            loss, loss_normals = torch.maximum(cham_x, cham_y), None
+        elif point_reduction is not None:
+            loss = cham_x + cham_y
+            loss_normals = normals_x + normals_y if normals_x is not None else None
+        else:
+            loss = (cham_x, cham_y)
+            loss_normals = (normals_x, normals_y) if normals_x is not None else None
+    return _reduce_batch(loss, loss_normals, weights, zero_weights, batch_reduction)

@@ -2,6 +2,7 @@
 // rasterizers, the face-vertex gather, the compositors and interpolate_face_attributes as ordered segmented sums
 // (ordered_sum.h) instead of float atomics.  The caller hands over the samples that hold a primitive, sorted by primitive
 // (stable), and a workspace; every gradient is then a pure function of the inputs, bit for bit.  DESIGN.md section 8.8.
+#include "knn_grad.h"
 #include "ordered_sum.h"
 #include "p3d_geom.h"
 
@@ -55,6 +56,24 @@ struct CornerOp {
   }
   __device__ void store(int v, int, const float (&r)[R]) const {
     out[(int64_t)v * 3] = r[0], out[(int64_t)v * 3 + 1] = r[1], out[(int64_t)v * 3 + 2] = r[2];
+  }
+};
+
+// ---- nearest neighbours: hit e of idx (N, P1, K) adds minus its row of knn_grad.h to p2 point n * P2 + idx[e] ----------------------
+struct KnnOp {
+  static constexpr int R = 3;  // D is 2 or 3; a row's third float stays 0 for D = 2
+  int64_t nsamples, nkeys;     // N P1 K hits, N P2 points
+  knn::Hits h;
+  int accumulate;              // add to what out holds (every key is stored once, so the order of the sum stays fixed)
+  float* out;                  // (N P2, D)
+  __device__ int64_t key(int64_t e) const { return h.target(e); }
+  __device__ void row(int64_t e, int t, int, float (&r)[R]) const {
+    const float g = h.upstream(e);
+    for (int c = 0; c < h.D; ++c) r[c] = -h.term(e, t, c, g);
+  }
+  __device__ void store(int t, int, const float (&r)[R]) const {
+    float* o = out + (int64_t)t * h.D;
+    for (int c = 0; c < h.D; ++c) o[c] = accumulate ? o[c] + r[c] : r[c];
   }
 };
 
@@ -392,6 +411,41 @@ P3D_API int p3d_scatter_face_grads_ordered(const float* grad_face_verts, const i
   co.nsamples = F * 3, co.nkeys = V;
   co.src = grad_face_verts, co.faces = faces, co.out = grad_verts;
   return ordered::run(co, sorted_corners, num_corners, 1, workspace, s, "scatter_face_grads_ordered");
+}
+
+// ---- nearest neighbours --------------------------------------------------------------------------------------------------------------
+P3D_API size_t p3d_knn_points_ordered_backward_workspace_bytes(int64_t num_sorted) {
+  return num_sorted < 0 ? 0 : partial_bytes(num_sorted, 3, 1);
+}
+
+P3D_API int p3d_knn_points_ordered_backward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2,
+                                            const int64_t* idx, const float* grad_dists, const float* cloud_scale,
+                                            const int64_t* sorted_samples, int64_t num_sorted, int64_t N, int64_t P1, int64_t P2, int D,
+                                            int K, int norm, unsigned flags, float* grad_p2, void* workspace, size_t workspace_bytes,
+                                            p3d_stream_t stream) {
+  if (N < 0 || P1 < 0 || P2 < 0 || K < 1 || D < 1 || num_sorted < 0 || (norm != 1 && norm != 2)) return P3D_ERR_INVALID_ARG;
+  if (D != 2 && D != 3) return P3D_ERR_UNSUPPORTED;
+  // a key n * P2 + j is an int (ordered_sum.h)
+  if (P2 > 0 && N > INT32_MAX / P2) return P3D_ERR_INVALID_ARG;
+  if (P1 > 0 && N > 0 && (int64_t)K > INT64_MAX / 8 / P1 / N) return P3D_ERR_INVALID_ARG;
+  const int64_t hits = N * P1 * K;
+  if (num_sorted > hits) return P3D_ERR_INVALID_ARG;
+  if (N * P2 == 0) return P3D_OK;
+  if (!grad_p2) return P3D_ERR_INVALID_ARG;
+  if (num_sorted > 0 && (!p1 || !p2 || !idx || !sorted_samples)) return P3D_ERR_INVALID_ARG;
+  if (workspace_bytes < p3d_knn_points_ordered_backward_workspace_bytes(num_sorted) || (!workspace && num_sorted > 0)) return P3D_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int accumulate = (flags & P3D_KNN_ACCUMULATE_P2) != 0;
+  if (!accumulate) {
+    const int st = ordered::fill_zero(grad_p2, N * P2 * D, s);
+    if (st != P3D_OK) return st;
+  }
+  KnnOp op;
+  op.nsamples = hits, op.nkeys = N * P2;
+  op.h.p1 = p1, op.h.p2 = p2, op.h.lengths1 = lengths1, op.h.lengths2 = lengths2, op.h.idx = idx, op.h.grad_dists = grad_dists;
+  op.h.cloud_scale = cloud_scale, op.h.N = N, op.h.P1 = P1, op.h.P2 = P2, op.h.D = D, op.h.K = K, op.h.norm = norm;
+  op.accumulate = accumulate, op.out = grad_p2;
+  return ordered::run(op, sorted_samples, num_sorted, 1, workspace, s, "knn_backward_ordered");
 }
 
 // ---- points ------------------------------------------------------------------------------------------------------------------------

@@ -45,6 +45,10 @@ reference classes runs on them end to end:
                                                                  fixed-tree sums (no float atomics, no host round trip);
                                                                  without patch_python the reference's own normal consistency
                                                                  runs too (`_C.mesh_normal_consistency_find_verts` on the host)
+    ops.knn.knn_points / loss.chamfer.chamfer_distance        -> csrc/knn.hip: brute-force nearest neighbours, one lane per query;
+                                                                 chamfer without normals is one autograd node with no host
+                                                                 sync; inputs the kernels do not take go to this package's torch
+                                                                 formulation (`_C.knn_points_idx` itself stays a stub that raises)
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -331,6 +335,45 @@ def patch_reference_python():
     _patch_hard_and_silhouette_shaders()
     _patch_depth_shaders(our_blend)
     _patch_mesh_losses(wrap)
+    _patch_point_losses()
+
+
+def _patch_point_losses():
+    """pytorch3d.ops.knn.knn_points and pytorch3d.loss.chamfer.chamfer_distance -> pytorch3d_amd.knn / pytorch3d_amd.chamfer
+    (csrc/knn.hip).  float32 GPU clouds with D in {2, 3} (and K <= 32) take the kernels; everything else takes OUR torch formulation of
+    the same contract, not the reference's function: that one ends in `_C.knn_points_idx`, which stays a stub that raises.
+    PATCH_CALLS counts the kernel calls as fused and the torch formulation as fallbacks."""
+    import importlib
+
+    import torch
+
+    ours_knn = importlib.import_module(__package__ + ".knn")
+    ours_chamfer = importlib.import_module(__package__ + ".chamfer")
+    try:  # every module that copied the names must be loaded before rebinding
+        ref_knn = importlib.import_module("pytorch3d.ops.knn")
+        importlib.import_module("pytorch3d.ops")
+        ref_chamfer = importlib.import_module("pytorch3d.loss.chamfer")
+        importlib.import_module("pytorch3d.loss")
+    except ImportError:  # a reference checkout without these packages: nothing to patch
+        return
+
+    def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False, return_sorted=True):
+        _count("knn_points", ours_knn.kernel_path(p1, p2, K))
+        return ours_knn.knn_points(p1, p2, lengths1, lengths2, norm, K, version, return_nn, return_sorted)
+
+    def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None, batch_reduction="mean",
+                         point_reduction="mean", norm=2, single_directional=False, abs_cosine=True):
+        px = x.points_padded() if ours_chamfer._is_cloud_object(x) else x
+        py = y.points_padded() if ours_chamfer._is_cloud_object(y) else y
+        _count("chamfer_distance", torch.is_tensor(px) and torch.is_tensor(py) and ours_knn.kernel_path(px, py, 1))
+        return ours_chamfer.chamfer_distance(x, y, x_lengths, y_lengths, x_normals, y_normals, weights, batch_reduction,
+                                             point_reduction, norm, single_directional, abs_cosine)
+
+    for orig, new in ((ref_knn.knn_points, knn_points), (ref_chamfer.chamfer_distance, chamfer_distance)):
+        new.__doc__ = getattr(orig, "__doc__", None)
+        new.__wrapped__ = orig
+        new.__p3d_amd__ = True
+        _replace_everywhere(orig, new)
 
 
 def _patch_mesh_losses(wrap):
