@@ -757,6 +757,52 @@ int p3d_knn_points_ordered_backward(const float* p1, const float* p2, const int6
                                     int norm, unsigned flags, float* grad_p2, void* workspace, size_t workspace_bytes,
                                     p3d_stream_t stream);
 
+/* ---- point-mesh distances (pytorch3d/loss/point_mesh_distance.py; csrc/point_mesh.hip, csrc/point_mesh_geom.h) ------------
+ *
+ * Brute force between the points of a cloud and the faces or edges of its mesh, per batch element.  A direction is a (query kind,
+ * target kind) pair: (POINT, TRIANGLE) point_face, (TRIANGLE, POINT) face_point, (POINT, SEGMENT) point_edge, (SEGMENT, POINT)
+ * edge_point; anything else is P3D_ERR_INVALID_ARG.  Packed layouts, as the reference's operators take them: points (P,3), tris
+ * (T,3,3), segms (S,2,3) contiguous f32; query_first_idx / target_first_idx (N) i64, element n owning [first[n], first[n+1]) (the
+ * last one up to the total; values are clamped into the arrays).  Q / T: the number of query / target objects.
+ * Forward: dists (Q) f32 <- the smallest squared distance from query q to a target of its element, idxs (Q) i64 <- that target's
+ * PACKED index.  Among equal distances the LARGEST target index wins (the reference's CPU loop: ascending with <=); a NaN distance
+ * is never selected.  An element without targets: dists FLT_MAX, idxs 0.  max_queries: a host-side upper bound of the elements'
+ * query counts (the grid is sized from it, rows past an element's count exit; a bound that is too small leaves rows unwritten).
+ * Every entry of dists / idxs is written, no memset.  The pair functions are those of point_mesh_geom.h: float32, one operation
+ * each, NOT fused; min_triangle_area is compared with the face's area in double (segment directions ignore it).
+ * One lane per query, a wave = 64 consecutive queries of one element, targets staged in LDS tiles of P3D_POINT_MESH_TILE records.
+ * split: waves per workgroup that share the 64 queries and take every split-th tile, 1 / 2 / 4 / 8, or 0 = chosen from the workgroup
+ * count and the device's CU count.  The result is bit-equal for every split.
+ * sums != NULL fuses one direction of the loss: dists[q] * weights[n] (weights (N) f32 or NULL = 1) summed per wave (6 butterfly
+ * rounds), then per element by a second launch (lane t of one block of 256 adds the partials t, t + 256, ... ascending, 8 more
+ * rounds): sums (N) f32.  No float atomic.  workspace: p3d_point_mesh_forward_workspace_bytes(N, max_queries) bytes (sums only). */
+#define P3D_POINT_MESH_POINT 0
+#define P3D_POINT_MESH_SEGMENT 1
+#define P3D_POINT_MESH_TRIANGLE 2
+#define P3D_POINT_MESH_TILE 64
+size_t p3d_point_mesh_forward_workspace_bytes(int64_t N, int64_t max_queries);
+int p3d_point_mesh_forward(int query_kind, int target_kind, const float* queries, const float* targets,
+                           const int64_t* query_first_idx, const int64_t* target_first_idx, int64_t N, int64_t Q, int64_t T,
+                           int64_t max_queries, double min_triangle_area, int split, const float* weights, float* dists,
+                           int64_t* idxs, float* sums, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+/* Backward: the hit of query q is (q, idxs[q]); an idxs entry outside [0, T) is no hit.  Its upstream gradient is grad_dists[q]
+ * (NULL: 1) * elem_scale[n] (NULL: 1).  With the first-index arrays (both or neither; elem_scale needs them) a query of an element
+ * WITHOUT targets is no hit either and nothing of `targets` is read for it.
+ * grad_queries (Q, 3 / 6 / 9), NULL to skip: one lane per query, a plain store to every row (zeros for no hit), or an add to what
+ * the row holds under P3D_POINT_MESH_ACCUMULATE_QUERIES.
+ * grad_targets (T, 3 / 6 / 9), NULL to skip: zero-filled first unless P3D_POINT_MESH_ACCUMULATE_TARGETS; then the hits are added
+ * with float atomics, the 3 / 6 / 9 values of one hit from adjacent lanes -- or, with sorted_hits != NULL (the Q query indices sorted
+ * stably by idxs), by the ordered segmented sum of the deterministic backwards: the same bits on every run.
+ * workspace: p3d_point_mesh_backward_workspace_bytes(target_kind, Q) bytes, needed with sorted_hits only. */
+#define P3D_POINT_MESH_ACCUMULATE_QUERIES 1u
+#define P3D_POINT_MESH_ACCUMULATE_TARGETS 2u
+size_t p3d_point_mesh_backward_workspace_bytes(int target_kind, int64_t Q);
+int p3d_point_mesh_backward(int query_kind, int target_kind, const float* queries, const float* targets, const int64_t* idxs,
+                            const float* grad_dists, const float* elem_scale, const int64_t* query_first_idx,
+                            const int64_t* target_first_idx, int64_t N, int64_t Q, int64_t T, double min_triangle_area,
+                            unsigned flags, const int64_t* sorted_hits, float* grad_queries, float* grad_targets, void* workspace,
+                            size_t workspace_bytes, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

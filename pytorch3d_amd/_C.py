@@ -1075,6 +1075,149 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _nee
     return grad_p1, grad_p2
 
 
+# ----------------------------------------------------------------------------------------------
+# point-mesh distances (csrc/point_mesh.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the eight names to
+# pytorch3d_amd.point_mesh, which comes here for float32 GPU tensors and owns a torch formulation for everything else.
+_PM_KINDS = {"point_face": (_lib.POINT_MESH_POINT, _lib.POINT_MESH_TRIANGLE), "face_point": (_lib.POINT_MESH_TRIANGLE, _lib.POINT_MESH_POINT),
+             "point_edge": (_lib.POINT_MESH_POINT, _lib.POINT_MESH_SEGMENT), "edge_point": (_lib.POINT_MESH_SEGMENT, _lib.POINT_MESH_POINT)}
+
+
+def _pm_check(direction, points, prims, who, **others):
+    corners = 3 if "face" in direction else 2
+    dev = _same_device(("points", points), ("tris" if corners == 3 else "segms", prims), *others.items())
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError(f"{who}: points must have shape (P, 3)")
+    if prims.dim() != 3 or tuple(prims.shape[1:]) != (corners, 3):
+        raise RuntimeError(f"{who}: {'tris' if corners == 3 else 'segms'} must have shape (T, {corners}, 3)")
+    return dev, _c(points, torch.float32), _c(prims, torch.float32)
+
+
+def _pm_first(points_first_idx, prims_first_idx, who):
+    a, b = _c(points_first_idx, torch.int64), _c(prims_first_idx, torch.int64)
+    if a.dim() != 1 or a.shape != b.shape:
+        raise RuntimeError(f"{who}: the two first-index tensors must have the same shape (N,)")
+    return a, b
+
+
+def point_mesh_forward(direction, points, points_first_idx, prims, prims_first_idx, max_queries, min_triangle_area=5e-3, split=0,
+                       weights=None, with_sums=False):
+    """One direction ("point_face", "face_point", "point_edge", "edge_point") of include/p3d_amd.h: p3d_point_mesh_forward ->
+    (dists, idxs) over the QUERY objects -- points for point_*, tris / segms for face_point / edge_point --, idxs packed target
+    indices; with_sums: also sums (N,), the element sums of dists * weights[n]."""
+    who = direction + "_dist_forward"
+    dev, points, prims = _pm_check(direction, points, prims, who, points_first_idx=points_first_idx, prims_first_idx=prims_first_idx)
+    pfirst, sfirst = _pm_first(points_first_idx, prims_first_idx, who)
+    qk, tk = _PM_KINDS[direction]
+    point_query = qk == _lib.POINT_MESH_POINT
+    q, t, qf, tf = (points, prims, pfirst, sfirst) if point_query else (prims, points, sfirst, pfirst)
+    N, Q, T = int(qf.shape[0]), int(q.shape[0]), int(t.shape[0])
+    max_queries = min(int(max_queries), Q)
+    if weights is not None:
+        _same_device(("points", points), ("weights", weights))
+        weights = _c(weights, torch.float32)
+        if weights.shape != (N,):
+            raise RuntimeError(f"{who}: weights must have shape (N,)")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        dists = torch.empty((Q,), dtype=torch.float32, device=dev)
+        idxs = torch.empty((Q,), dtype=torch.int64, device=dev)
+        sums, ws, nbytes = None, None, 0
+        if with_sums:
+            sums = torch.empty((N,), dtype=torch.float32, device=dev)
+            nbytes = lib.p3d_point_mesh_forward_workspace_bytes(N, max_queries)
+            ws = _workspace(nbytes, dev)
+        rc = lib.p3d_point_mesh_forward(qk, tk, _ptr(q), _ptr(t), _ptr(qf), _ptr(tf), N, Q, T, max_queries, float(min_triangle_area),
+                                        int(split), _ptr(weights), _ptr(dists), _ptr(idxs), _ptr(sums), _ptr(ws), nbytes, _stream(dev))
+        _lib.check(rc, who)
+    return (dists, idxs, sums) if with_sums else (dists, idxs)
+
+
+def point_mesh_backward(direction, points, prims, idxs, grad_dists, min_triangle_area=5e-3, points_first_idx=None, prims_first_idx=None,
+                        elem_scale=None, grad_points=None, grad_prims=None, accumulate=False):
+    """p3d_point_mesh_backward -> (grad_points (P, 3), grad_prims like prims).  The query side is a store, the target side float
+    atomics or, under torch.use_deterministic_algorithms(True), the ordered sum over the hits sorted by target on the device (a sort
+    of Q entries: no nonzero, no host sync).  grad_dists may be None (1).  With the first-index tensors a query of an element without
+    targets contributes nothing, and elem_scale (N,) multiplies the upstream gradient per element.  grad_points / grad_prims:
+    buffers to use; accumulate: ADD to what both hold (the second direction of a loss)."""
+    who = direction + "_dist_backward"
+    others = {"idxs": idxs}
+    if grad_dists is not None:
+        others["grad_dists"] = grad_dists
+    dev, points, prims = _pm_check(direction, points, prims, who, **others)
+    qk, tk = _PM_KINDS[direction]
+    point_query = qk == _lib.POINT_MESH_POINT
+    idxs = _c(idxs, torch.int64)
+    pfirst = sfirst = None
+    if points_first_idx is not None:
+        pfirst, sfirst = _pm_first(points_first_idx, prims_first_idx, who)
+    q, t, qf, tf = (points, prims, pfirst, sfirst) if point_query else (prims, points, sfirst, pfirst)
+    N, Q, T = (0 if qf is None else int(qf.shape[0])), int(q.shape[0]), int(t.shape[0])
+    if idxs.shape != (Q,) or (grad_dists is not None and grad_dists.shape != (Q,)):
+        raise RuntimeError(f"{who}: idxs and grad_dists must have one entry per query object")
+    g = None if grad_dists is None else grad_dists.to(torch.float32).contiguous()
+    scale = None if elem_scale is None else _c(elem_scale, torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        for name, buf, like in (("grad_points", grad_points, points), ("grad_prims", grad_prims, prims)):
+            if buf is not None and (buf.shape != like.shape or buf.dtype != torch.float32 or buf.device != dev or not buf.is_contiguous()):
+                raise RuntimeError(f"{who}: {name} must be a contiguous float32 tensor shaped like its input, on the inputs' GPU")
+        if accumulate and (grad_points is None or grad_prims is None):
+            raise RuntimeError(f"{who}: accumulate needs both gradient buffers")
+        grad_points = torch.empty_like(points) if grad_points is None else grad_points
+        grad_prims = torch.empty_like(prims) if grad_prims is None else grad_prims
+        gq, gt = (grad_points, grad_prims) if point_query else (grad_prims, grad_points)
+        flags = (_lib.POINT_MESH_ACCUMULATE_QUERIES | _lib.POINT_MESH_ACCUMULATE_TARGETS) if accumulate else 0
+        hits, ws, nbytes = None, None, 0
+        if _ordered() and Q > 0 and T > 0:
+            hits = torch.sort(idxs, stable=True).indices.contiguous()
+            nbytes = lib.p3d_point_mesh_backward_workspace_bytes(tk, Q)
+            ws = _workspace(nbytes, dev)
+        rc = lib.p3d_point_mesh_backward(qk, tk, _ptr(q), _ptr(t), _ptr(idxs), _ptr(g), _ptr(scale), _ptr(qf), _ptr(tf), N, Q, T,
+                                         float(min_triangle_area), flags, _ptr(hits), _ptr(gq), _ptr(gt), _ptr(ws), nbytes, _stream(dev))
+        _lib.check(rc, who)
+    return grad_points, grad_prims
+
+
+def point_face_dist_forward(points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area=5e-3):
+    """PointFaceDistanceForward (point_mesh_cuda.h): (dists (P,), idxs (P,) packed face indices)."""
+    return point_mesh_forward("point_face", points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area)
+
+
+def point_face_dist_backward(points, tris, idxs, grad_dists, min_triangle_area=5e-3):
+    return point_mesh_backward("point_face", points, tris, idxs, grad_dists, min_triangle_area)
+
+
+def face_point_dist_forward(points, points_first_idx, tris, tris_first_idx, max_tris, min_triangle_area=5e-3):
+    """FacePointDistanceForward: (dists (T,), idxs (T,) packed point indices)."""
+    return point_mesh_forward("face_point", points, points_first_idx, tris, tris_first_idx, max_tris, min_triangle_area)
+
+
+def face_point_dist_backward(points, tris, idxs, grad_dists, min_triangle_area=5e-3):
+    return point_mesh_backward("face_point", points, tris, idxs, grad_dists, min_triangle_area)
+
+
+def point_edge_dist_forward(points, points_first_idx, segms, segms_first_idx, max_points):
+    """PointEdgeDistanceForward: (dists (P,), idxs (P,) packed edge indices)."""
+    return point_mesh_forward("point_edge", points, points_first_idx, segms, segms_first_idx, max_points)
+
+
+def point_edge_dist_backward(points, segms, idxs, grad_dists):
+    return point_mesh_backward("point_edge", points, segms, idxs, grad_dists)
+
+
+def edge_point_dist_forward(points, points_first_idx, segms, segms_first_idx, max_segms):
+    """EdgePointDistanceForward: (dists (S,), idxs (S,) packed point indices)."""
+    return point_mesh_forward("edge_point", points, points_first_idx, segms, segms_first_idx, max_segms)
+
+
+def edge_point_dist_backward(points, segms, idxs, grad_dists):
+    return point_mesh_backward("edge_point", points, segms, idxs, grad_dists)
+
+
+POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
+                      "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
+
+
 HOT_PATH_EXPORTS = (
     "rasterize_meshes", "rasterize_meshes_backward", "_rasterize_meshes_naive", "_rasterize_meshes_coarse",
     "_rasterize_meshes_fine", "rasterize_points", "rasterize_points_backward", "_rasterize_points_naive",

@@ -12,6 +12,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     face_areas_normals, verts_normals, vert_incidence  face / vertex normals of a packed batch, fused (vertex normals without atomics)
     mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency, mesh_loss_topology  the regularisers of a fitting loop, fused
     knn_points, knn_gather, chamfer_distance  nearest neighbours between point clouds and the chamfer loss on top, fused
+    point_mesh_face_distance, point_mesh_edge_distance, point_face_distance, face_point_distance, point_edge_distance,
+    edge_point_distance              distances between a point cloud and the faces / edges of a mesh, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -26,6 +28,8 @@ from .knn import knn_gather, knn_points  # noqa: F401
 from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
                           mesh_normal_consistency)
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
+from .point_mesh import (edge_point_distance, face_point_distance, point_edge_distance, point_face_distance,  # noqa: F401
+                         point_mesh_edge_distance, point_mesh_face_distance)
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401

@@ -15,6 +15,7 @@ c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_uint = ctypes.c_uint
 c_f32 = ctypes.c_float
+c_f64 = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
@@ -28,6 +29,10 @@ BWD_MAKE_FACE_PRE = 2
 KNN_MAX_K = 32           # P3D_KNN_MAX_K
 KNN_TILE = 512           # P3D_KNN_TILE: p2 points staged per step
 KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
+POINT_MESH_POINT, POINT_MESH_SEGMENT, POINT_MESH_TRIANGLE = 0, 1, 2  # P3D_POINT_MESH_*: the kind of a query / target object
+POINT_MESH_TILE = 64                # P3D_POINT_MESH_TILE: target records staged per wave and step
+POINT_MESH_ACCUMULATE_QUERIES = 1   # P3D_POINT_MESH_ACCUMULATE_QUERIES
+POINT_MESH_ACCUMULATE_TARGETS = 2   # P3D_POINT_MESH_ACCUMULATE_TARGETS
 
 _SIGNATURES = {
     # name: (restype, [argtypes])
@@ -186,6 +191,13 @@ _SIGNATURES = {
     "p3d_knn_points_ordered_backward_workspace_bytes": (c_size, [c_i64]),
     "p3d_knn_points_ordered_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int,
                                                 c_int, c_int, c_uint, c_ptr, c_ptr, c_size, c_ptr]),
+    # point-mesh distances (csrc/point_mesh.hip; the ordered scatter: csrc/ordered_bwd.hip)
+    "p3d_point_mesh_forward_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "p3d_point_mesh_forward": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_f64, c_int, c_ptr, c_ptr,
+                                       c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_point_mesh_backward_workspace_bytes": (c_size, [c_int, c_i64]),
+    "p3d_point_mesh_backward": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_f64, c_uint,
+                                        c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

@@ -5,6 +5,7 @@
 #include "knn_grad.h"
 #include "ordered_sum.h"
 #include "p3d_geom.h"
+#include "point_mesh_geom.h"
 
 namespace p3d {
 namespace {
@@ -74,6 +75,30 @@ struct KnnOp {
   __device__ void store(int t, int, const float (&r)[R]) const {
     float* o = out + (int64_t)t * h.D;
     for (int c = 0; c < h.D; ++c) o[c] = accumulate ? o[c] + r[c] : r[c];
+  }
+};
+
+// ---- point-mesh distances: query q adds the target part of its pair's gradient (point_mesh_geom.h) to target idxs[q] -----------------
+template <int QK, int TK>
+struct PointMeshOp {
+  static constexpr int R = pm::kind_floats(TK);
+  int64_t nsamples, nkeys;  // Q queries, T targets
+  pm::Hits h;
+  int accumulate;
+  float* out;  // (T, R)
+  // the recorded index also for a query whose element has no targets (its row is zero): it must not cut a segment in two
+  __device__ int64_t key(int64_t q) const { return h.idxs[q]; }
+  __device__ void row(int64_t q, int, int, float (&r)[R]) const {
+    float g = 0.0f;
+    const int64_t t = h.target(q, &g);
+    if (t < 0) return;
+    float gq[pm::kind_floats(QK)];
+    h.grads<QK, TK>(q, t, g, gq, r);
+  }
+  __device__ void store(int t, int, const float (&r)[R]) const {
+    float* o = out + (int64_t)t * R;
+#pragma unroll
+    for (int c = 0; c < R; ++c) o[c] = accumulate ? o[c] + r[c] : r[c];
   }
 };
 
@@ -348,6 +373,29 @@ bool strides_planar_or_rows(const int64_t* st, int C, int64_t P, int64_t out[2])
 }
 
 }  // namespace
+
+// ---- point-mesh distances (point_mesh.hip calls these) ---------------------------------------------------------------------------------
+size_t point_mesh_ordered_bytes(int target_kind, int64_t Q) { return partial_bytes(Q, pm::kind_floats(target_kind), 1); }
+
+template <int QK, int TK>
+static int point_mesh_ordered_run(const pm::Hits& h, const int64_t* sorted, int accumulate, float* grad_targets, void* workspace,
+                                  hipStream_t s) {
+  PointMeshOp<QK, TK> op;
+  op.nsamples = h.Q, op.nkeys = h.T, op.h = h, op.accumulate = accumulate, op.out = grad_targets;
+  return ordered::run(op, sorted, h.Q, 1, workspace, s, "point_mesh_backward_ordered");
+}
+
+// the rows of grad_targets hold what the sum is added to (accumulate) or anything (then rows nobody hits must be zero already)
+int point_mesh_ordered_scatter(const pm::Hits& h, const int64_t* sorted, int accumulate, float* grad_targets, void* workspace,
+                               hipStream_t s) {
+  if (h.query_kind == pm::kPoint) {
+    return h.target_kind == pm::kTri ? point_mesh_ordered_run<pm::kPoint, pm::kTri>(h, sorted, accumulate, grad_targets, workspace, s)
+                                     : point_mesh_ordered_run<pm::kPoint, pm::kSeg>(h, sorted, accumulate, grad_targets, workspace, s);
+  }
+  return h.query_kind == pm::kTri ? point_mesh_ordered_run<pm::kTri, pm::kPoint>(h, sorted, accumulate, grad_targets, workspace, s)
+                                  : point_mesh_ordered_run<pm::kSeg, pm::kPoint>(h, sorted, accumulate, grad_targets, workspace, s);
+}
+
 }  // namespace p3d
 
 using namespace p3d;

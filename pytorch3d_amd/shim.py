@@ -9,7 +9,9 @@ interpolate_face_attributes, ...) runs on the MI355X kernels.
 
 `pytorch3d/__init__.py` does not import `_C`; the sub-packages do (`from pytorch3d import _C`),
 so the module must be in sys.modules before they are imported.  Operators outside the hot path
-(knn, point_mesh, pulsar, ...) raise NotImplementedError when called.
+(knn, the point_mesh *_array_dist_* operators, pulsar, ...) raise NotImplementedError when called.  The eight point_mesh operators
+under `pytorch3d.loss.point_mesh_face_distance` / `point_mesh_edge_distance` ARE served (csrc/point_mesh.hip), so the unmodified
+reference losses run under plain `shim.install()`.
 
     shim.install(patch_python=True)
 
@@ -49,6 +51,10 @@ reference classes runs on them end to end:
                                                                  chamfer without normals is one autograd node with no host
                                                                  sync; inputs the kernels do not take go to this package's torch
                                                                  formulation (`_C.knn_points_idx` itself stays a stub that raises)
+    loss.point_mesh_distance.point_mesh_face_distance / point_mesh_edge_distance -> csrc/point_mesh.hip: one autograd node each (face /
+                                                                 edge gather, two fused brute-force forwards with fixed-tree sums,
+                                                                 two backward kernels, the vertex scatter) and no host sync; other
+                                                                 inputs go to this package's torch formulation
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -89,6 +95,12 @@ def make_module(flavour="ctypes"):
     for name in ("face_areas_normals_forward", "face_areas_normals_backward", "packed_to_padded", "padded_to_packed",
                  "mesh_normal_consistency_find_verts"):
         setattr(mod, name, getattr(_aux_ops, name))
+    # the eight operators under pytorch3d.loss.point_mesh_distance (pytorch3d_amd/point_mesh.py): csrc/point_mesh.hip for float32 GPU
+    # tensors, a torch formulation of the same contract for everything else.  Both flavours serve these Python wrappers.
+    from . import point_mesh
+
+    for name in _ours.POINT_MESH_EXPORTS:
+        setattr(mod, name, getattr(point_mesh, name))
     if flavour == "pybind":
         # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
         def compiled(name):
@@ -336,6 +348,35 @@ def patch_reference_python():
     _patch_depth_shaders(our_blend)
     _patch_mesh_losses(wrap)
     _patch_point_losses()
+    _patch_point_mesh_losses()
+
+
+def _patch_point_mesh_losses():
+    """pytorch3d.loss.point_mesh_distance.point_mesh_face_distance / point_mesh_edge_distance -> pytorch3d_amd.point_mesh, in every
+    module that copied the names (pytorch3d.loss among them).  float32 GPU batches are one autograd node over csrc/point_mesh.hip;
+    everything else takes OUR torch formulation.  PATCH_CALLS counts the kernel calls as fused and the formulation as fallbacks."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".point_mesh")
+    try:  # every module that copied the names must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.loss.point_mesh_distance")
+        importlib.import_module("pytorch3d.loss")
+    except ImportError:  # a reference checkout without its loss package: nothing to patch
+        return
+
+    def point_mesh_face_distance(meshes, pcls, min_triangle_area=ours.DEFAULT_MIN_TRIANGLE_AREA):
+        _count("point_mesh_face_distance", len(meshes) == len(pcls) and ours.fused_path(meshes, pcls))
+        return ours.point_mesh_face_distance(meshes, pcls, min_triangle_area)
+
+    def point_mesh_edge_distance(meshes, pcls):
+        _count("point_mesh_edge_distance", len(meshes) == len(pcls) and ours.fused_path(meshes, pcls))
+        return ours.point_mesh_edge_distance(meshes, pcls)
+
+    for orig, new in ((ref.point_mesh_face_distance, point_mesh_face_distance), (ref.point_mesh_edge_distance, point_mesh_edge_distance)):
+        new.__doc__ = getattr(orig, "__doc__", None)
+        new.__wrapped__ = orig
+        new.__p3d_amd__ = True
+        _replace_everywhere(orig, new)
 
 
 def _patch_point_losses():
