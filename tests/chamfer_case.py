@@ -3,7 +3,8 @@ results into tests/golden/chamfer_ref.npz), tests/test_cpu_chamfer.py, tests/tes
 
 The fixture holds the inputs too, so nothing depends on a random generator staying the same.  Independent of the package: a float64
 brute force in (dist, j) order, a float64 restatement of the distances / the chamfer loss on GIVEN indices (differentiated by
-autograd) and the gates built from them.
+autograd) and the gates built from them.  At the end: the generated shapes of tests/test_cpu_loss_kernel_edges.py and
+tests/test_gpu_loss_kernel_edges.py (seeded generators, no fixture).
 """
 import math
 import os
@@ -254,3 +255,283 @@ def star_clouds():
     """P2 = 1, P1 = 300: every query hits the one point (the worst case of the scatter)."""
     gen = torch.Generator().manual_seed(5)
     return torch.randn(1, 300, 3, generator=gen), torch.randn(1, 1, 3, generator=gen)
+
+
+# ---- generated shapes: every queue rung, ragged clouds over tile and wave edges, the second round of the sums and loops --------------
+# (tests/test_cpu_loss_kernel_edges.py, tests/test_gpu_loss_kernel_edges.py)
+EDGE_SEED = 31
+# name -> (N, P1, P2, lengths1, lengths2)
+EDGE_SHAPES = {
+    "rungs": (4, 130, 2 * TILE + 6, [130, 64, 65, 1], [2 * TILE + 6, TILE, TILE + 1, TILE - 1]),  # clouds that scan 3, 1, 2 and 1 tiles
+    "short": (3, 70, 40, [70, 1, 33], [40, 17, 5]),                                                  # K > lengths2 on the rungs 8, 16, 32
+}
+EDGE_KS = (1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 31, 32)  # both ends and the inside of every queue capacity 1, 2, 4, 8, 16, 32
+EDGE_BACKWARD = [("rungs", K) for K in (2, 5, 9, 16, 17, 32)] + [("short", K) for K in (8, 16)]
+EDGE_DN = ((3, 2), (2, 1))  # (D, norm) of the backward cases
+MAX_LEFT_OUT = 0.05  # of a case's live queries may fall outside the admission (point_mesh_case.MAX_DROPPED)
+STREAM_CAP = 256 * 16 * 256  # items one pass of a grid-stride loop covers (stream_blocks: 4 096 blocks of 256 threads)
+BIG_P1 = STREAM_CAP + 300
+
+_EDGE = {}
+
+
+def edge_clouds(shape, D):
+    """(p1, p2, lengths1, lengths2) of a generated shape: uniform in the unit cube, drawn p1 then p2 per (shape, D), D = 3 first, from
+    ONE generator.  p2 beyond lengths2[n] holds copies of that cloud's own live p1 points -- decoys at distance 0: a scan that reads
+    past the length finds them nearer than anything -- and p1 beyond lengths1[n] holds NaN."""
+    if not _EDGE:
+        gen = torch.Generator().manual_seed(EDGE_SEED)
+        for name, (N, P1, P2, l1, l2) in EDGE_SHAPES.items():
+            for d in (3, 2):
+                p1, p2 = torch.rand(N, P1, d, generator=gen), torch.rand(N, P2, d, generator=gen)
+                for n in range(N):
+                    if l2[n] < P2:
+                        p2[n, l2[n]:] = p1[n, torch.arange(P2 - l2[n]) % l1[n]]
+                    p1[n, l1[n]:] = float("nan")
+                _EDGE[(name, d)] = (p1.contiguous(), p2.contiguous(), l1, l2)
+    return _EDGE[(shape, D)]
+
+
+def live_rows(lengths1, N, P1):
+    l1 = torch.full((N,), P1) if lengths1 is None else torch.as_tensor(lengths1).cpu()
+    return torch.arange(P1)[None, :] < l1[:, None]
+
+
+def admitted_queries(sorted_dists, lengths1, lengths2, K):
+    """(N, P1) bool from the ascending float64 distances (N, P1, >= min(K + 1, P2)) of every query, +inf past lengths2: the live
+    queries whose consecutive distances among the first min(K, len2) + 1 neighbours all differ by at least MIN_GAP relative (the rule
+    smallest_gap states for a whole case, here per query)."""
+    N, P1, M = sorted_dists.shape
+    l2 = torch.full((N,), M, device=sorted_dists.device) if lengths2 is None else torch.as_tensor(lengths2).to(sorted_dists.device)
+    k = torch.minimum(torch.clamp(l2, max=K) + 1, l2).clamp(max=M)  # neighbours looked at, per cloud
+    sd = sorted_dists[:, :, :min(K + 1, M)]
+    gap = (sd[:, :, 1:] - sd[:, :, :-1]) / sd[:, :, 1:]
+    looked_at = torch.arange(gap.shape[2], device=sd.device)[None, None, :] < (k - 1)[:, None, None]
+    ok = (gap >= MIN_GAP) | ~looked_at
+    return ok.all(2) & live_rows(lengths1, N, P1).to(sd.device)
+
+
+def sorted_dists64(p1, p2, lengths1, lengths2, norm, keep):
+    """(idx, dists) of the first `keep` neighbours of every query in ascending (dist, j), float64, as ONE vectorised pass on the
+    device of p1 (the brute force for shapes where brute64's loop over the clouds on the CPU would do, restated for the large ones):
+    +inf / an arbitrary index past lengths2, whatever the row holds past lengths1."""
+    N, P1, D = p1.shape
+    P2 = p2.shape[1]
+    a, b = p1.double(), p2.double()
+    total = None
+    for c in range(D):  # (N, P1, P2) without the (N, P1, P2, D) intermediate
+        d = a[:, :, c, None] - b[:, None, :, c]
+        d = d * d if norm == 2 else d.abs()
+        total = d if total is None else total + d
+    if lengths2 is not None:
+        l2 = torch.as_tensor(lengths2).to(p1.device)
+        total = total.masked_fill(torch.arange(P2, device=p1.device)[None, None, :] >= l2[:, None, None], float("inf"))
+    sd, sj = torch.sort(total, dim=2, stable=True)
+    return sj[:, :, :keep], sd[:, :, :keep]
+
+
+def brute64_device(p1, p2, lengths1, lengths2, K, norm):
+    """brute64 from sorted_dists64: (idx, dists float64, admitted (N, P1)) on the device of p1, zeros in the padding."""
+    N, P1, _ = p1.shape
+    P2 = p2.shape[1]
+    sj, sd = sorted_dists64(p1, p2, lengths1, lengths2, norm, min(K + 1, P2))
+    ok = admitted_queries(sd, lengths1, lengths2, K)
+    valid = valid_mask(lengths1, lengths2, N, P1, P2, K).to(p1.device)
+    idx = torch.zeros((N, P1, K), dtype=torch.int64, device=p1.device)
+    dists = torch.zeros((N, P1, K), dtype=torch.float64, device=p1.device)
+    k = min(K, P2)
+    idx[:, :, :k], dists[:, :, :k] = sj[:, :, :k], sd[:, :, :k]
+    return idx.masked_fill(~valid, 0), dists.masked_fill(~valid, 0.0), ok
+
+
+_EDGE_TRUTH = {}
+
+
+def edge_truth(shape, D, norm, K):
+    """(idx, dists float64, admitted (N, P1), live (N, P1)) of a generated knn case by brute64 -- computed once, never modified."""
+    key = (shape, D, norm, K)
+    if key not in _EDGE_TRUTH:
+        p1, p2, l1, l2 = edge_clouds(shape, D)
+        N, P1, P2 = p1.shape[0], p1.shape[1], p2.shape[1]
+        idx, dists = brute64(p1, p2, l1, l2, K, norm)
+        sd = torch.full((N, P1, min(K + 1, P2)), float("inf"), dtype=torch.float64)
+        for n in range(N):
+            m = min(K + 1, l2[n])
+            sd[n, :l1[n], :m] = torch.sort(pair_dists64(p1[n, :l1[n]], p2[n, :l2[n]], norm), dim=1).values[:, :m]
+        _EDGE_TRUTH[key] = (idx, dists, admitted_queries(sd, l1, l2, K), live_rows(l1, N, P1))
+    return _EDGE_TRUTH[key]
+
+
+def check_knn_forward(who, got_idx, got_dists, want_idx, want_dists, ok, live, valid):
+    """The contract of the fixture test on a generated case: idx bit-equal on admitted queries, dists within 2e-6 relative on every
+    valid slot, padding rows and slots exactly 0 in both, at most MAX_LEFT_OUT of the live queries outside the admission."""
+    got_idx, got_dists = got_idx.to(want_idx.device), got_dists.to(want_idx.device).double()
+    left_out = 1.0 - float(ok.sum()) / max(int(live.sum()), 1)
+    wrong = int((got_idx != want_idx)[ok].sum())
+    rel = ((got_dists - want_dists).abs() / want_dists.abs().clamp_min(1e-300))[valid]
+    err = float(rel.max()) if rel.numel() else 0.0
+    print("%s: %d of %d live queries admitted (left out %.2f %%, cap %.0f %%), %d wrong indices among them, dists %.3g relative (gate 2e-6)"
+          % (who, int(ok.sum()), int(live.sum()), 100 * left_out, 100 * MAX_LEFT_OUT, wrong, err))
+    assert left_out <= MAX_LEFT_OUT, "too many queries outside the admission"
+    assert wrong == 0, "idx differs on admitted queries"
+    assert float(((got_dists - want_dists).abs() - 2e-6 * want_dists.abs())[valid].max()) <= 0.0 if rel.numel() else True
+    assert not bool(got_idx[~valid].any()) and not bool(got_dists[~valid].any()), "padding rows and slots are exactly 0"
+    assert bool((got_idx >= 0).all()) and not bool(torch.isnan(got_dists).any())
+
+
+def edge_backward_truth(p1, p2, lengths1, lengths2, idx, norm, grad_dists):
+    """knn_grad_truth with the NaN of p1's padding rows taken out first (0 x NaN is NaN under autograd), and the float32 torch
+    formulation's errors against it on the CPU with the SAME indices: (truth (grad_p1, grad_p2), [e_p1, e_p2])."""
+    from pytorch3d_amd import knn as knn_mod
+
+    a, b, idx, g = p1.cpu(), p2.cpu(), idx.cpu(), grad_dists.cpu()
+    truth = knn_grad_truth(torch.nan_to_num(a, nan=0.0), b, lengths1, lengths2, idx, norm, g)
+    f32 = knn_mod.torch_knn_backward(a, b, lengths_tensor(lengths1), lengths_tensor(lengths2), idx, norm, g)
+    return truth, [float((f.double() - t).abs().max()) for f, t in zip(f32, truth)]
+
+
+def check_knn_backward(who, grads, truth, e32, lengths1, lengths2):
+    """Each gradient within 4 x the float32 formulation's error; the padding rows of grad_p1 and the padding points of grad_p2
+    exactly 0."""
+    bad = []
+    for which, got, t, e in zip(("grad_p1", "grad_p2"), grads, truth, e32):
+        err = float((got.cpu().double() - t).abs().max())
+        print(who, which, "error %.3g" % err, "float32 formulation %.3g (gate 4 x)" % e)
+        if not err <= 4 * e:
+            bad.append((which, err, 4 * e))
+    assert not bad, bad
+    N, P1, P2 = grads[0].shape[0], grads[0].shape[1], grads[1].shape[1]
+    assert not bool(grads[0].cpu()[~live_rows(lengths1, N, P1)].any()), "the gradient of a padding row is not exactly 0"
+    assert not bool(grads[1].cpu()[~live_rows(lengths2, N, P2)].any()), "the gradient of a padding point is not exactly 0"
+
+
+# ---- runs in the scatter ----------------------------------------------------------------------------------------------------------------
+RUN_BLOCKS = (40, 1, 27, 1, 1, 50, 3, 1, 33, 1, 42)  # consecutive queries around one target: 200 in all, the target changes per block
+
+
+def star_clouds_d2():
+    """The star in the plane: 300 queries, one target -- ten waves of 32 hits, each one run."""
+    gen = torch.Generator().manual_seed(6)
+    return torch.randn(1, 300, 2, generator=gen), torch.randn(1, 1, 2, generator=gen)
+
+
+def few_targets_clouds(D):
+    """P1 = 200 against P2 = 3: the queries come in blocks of RUN_BLOCKS around one target each, so with K = 1 the hits in their
+    order are runs of 40, 1, 27, 1, 1, 50, ... -- longer than a wave's 32 (D = 2) or 21 (D = 3) hits, across its boundary, with runs of
+    one in between; with K = 2 a hit's neighbour in the order is the same query's OTHER target: runs of one and two."""
+    gen = torch.Generator().manual_seed(8)
+    targets = torch.tensor([[0.1, 0.2, 0.3], [0.9, 0.3, 0.6], [0.4, 0.9, 0.1]])[:, :D]
+    owner = torch.cat([torch.full((n,), b % 3, dtype=torch.int64) for b, n in enumerate(RUN_BLOCKS)])
+    p1 = targets[owner] + 0.1 * (torch.rand(owner.shape[0], D, generator=gen) - 0.5)
+    return p1[None].contiguous(), targets[None].contiguous(), owner
+
+
+def run_lengths(idx_flat):
+    """The lengths of the runs of equal consecutive entries."""
+    change = torch.nonzero(idx_flat[1:] != idx_flat[:-1]).squeeze(1) + 1
+    edges = torch.cat([torch.zeros(1, dtype=torch.int64), change, torch.tensor([idx_flat.numel()])])
+    return (edges[1:] - edges[:-1]).tolist()
+
+
+def scatter_truth(p1, p2, idx, g):
+    """(truth (P2, D) float64, bound): the float64 sum of what each hit adds to its target (norm 2: -2 g (x - y)) and the star's bound,
+    the largest in-degree x 2^-23 x the largest term.  One cloud; idx, g (P1, K)."""
+    x, y = p1[0].double(), p2[0].double()
+    terms = -2.0 * g.double()[..., None] * (x[:, None, :] - y[idx])  # (P1, K, D)
+    truth = torch.zeros_like(y).index_add(0, idx.reshape(-1), terms.reshape(-1, x.shape[1]))
+    degree = int(torch.bincount(idx.reshape(-1), minlength=y.shape[0]).max())
+    return truth, degree * 2.0 ** -23 * float(terms.abs().max()), terms
+
+
+# ---- the second round of the chamfer sum ---------------------------------------------------------------------------------------------
+SUM_SHAPE = (2, 16500, 40, [16500, 16385], [40, 3])  # 16 385 queries: 257 wave partials per cloud; the reverse direction scans 33 tiles
+SUM_WEIGHTS = [0.5, 2.0]
+SUM_CASES = [dict(point_reduction=p, batch_reduction=b, weights=w) for p in ("mean", "sum") for w in (None, SUM_WEIGHTS) for b in ("mean", None)]
+
+
+def sum_case_name(D, kw):
+    return "d%d_%s_%s_%s" % (D, kw["point_reduction"], kw["batch_reduction"], "weights" if kw["weights"] else "plain")
+
+
+def sum_clouds(D):
+    """(x, y) of SUM_SHAPE, uniform in the unit cube; the padding of each holds copies of the OTHER's live points of that cloud."""
+    N, P1, P2, lx, ly = SUM_SHAPE
+    gen = torch.Generator().manual_seed(EDGE_SEED + D)
+    x, y = torch.rand(N, P1, D, generator=gen), torch.rand(N, P2, D, generator=gen)
+    for n in range(N):
+        if ly[n] < P2:
+            y[n, ly[n]:] = x[n, torch.arange(P2 - ly[n]) % lx[n]]
+        if lx[n] < P1:
+            x[n, lx[n]:] = y[n, torch.arange(P1 - lx[n]) % ly[n]]
+    return x.contiguous(), y.contiguous()
+
+
+def sum_inputs(D, kw, device="cpu"):
+    """(x, y leaves, keyword arguments) for chamfer_distance(x, y, **kwargs) on a device."""
+    N, P1, P2, lx, ly = SUM_SHAPE
+    x, y = sum_clouds(D)
+    x, y = x.to(device).requires_grad_(True), y.to(device).requires_grad_(True)
+    out = dict(x_lengths=lengths_tensor(lx).to(device), y_lengths=lengths_tensor(ly).to(device), point_reduction=kw["point_reduction"],
+               batch_reduction=kw["batch_reduction"])
+    if kw["weights"] is not None:
+        out["weights"] = torch.tensor(kw["weights"], dtype=torch.float32, device=device)
+    return x, y, out
+
+
+_SUM_IDX, _SUM_TRUTH = {}, {}
+
+
+def sum_truth(D, kw):
+    name = sum_case_name(D, kw)
+    if name not in _SUM_TRUTH:
+        _SUM_TRUTH[name] = _sum_truth(D, kw)
+    return _SUM_TRUTH[name]
+
+
+def _sum_truth(D, kw):
+    """As test_gpu_chamfer.chamfer_truths for one case of SUM_CASES: float64 loss and gradients on the float64 neighbours, S, n, the
+    float32 CPU formulation's errors against them, and the per-cloud float64 terms of the x -> y direction (N, P1) with their
+    weights and divisors (for the deliberately wrong sum of the CPU leg), and that formulation's own results under "f32".  Computed
+    once per case, never modified."""
+    import pytorch3d_amd as p3d
+
+    N, P1, P2, lx, ly = SUM_SHAPE
+    x, y, ckw = sum_inputs(D, kw)
+    if D not in _SUM_IDX:
+        _SUM_IDX[D] = (brute64(x.detach(), y.detach(), lx, ly, 1, 2)[0][..., 0], brute64(y.detach(), x.detach(), ly, lx, 1, 2)[0][..., 0])
+    idx_x, idx_y = _SUM_IDX[D]
+    xd, yd = x.detach().double().requires_grad_(True), y.detach().double().requires_grad_(True)
+    w = None if kw["weights"] is None else torch.tensor(kw["weights"], dtype=torch.float64)
+    restate = dict(weights=w, point_reduction=kw["point_reduction"], batch_reduction=kw["batch_reduction"])
+    loss = chamfer_restated(xd, yd, lx, ly, idx_x, idx_y, **restate)
+    gx, gy = torch.autograd.grad(scalarise((loss, None)), (xd, yd))
+    per = chamfer_restated(xd.detach(), yd.detach(), lx, ly, idx_x, idx_y, **dict(restate, batch_reduction=None))
+    scale = 1.0
+    if kw["batch_reduction"] == "mean":
+        scale = 1.0 / (float(w.sum()) if w is not None else N)
+    S = float(per.abs().sum()) * scale if kw["batch_reduction"] is not None else float(per.abs().max())
+    f32 = p3d.chamfer_distance(x, y, **ckw)
+    fx, fy = torch.autograd.grad(scalarise(f32), (x, y))
+    terms_x = dists_on_indices(xd.detach(), yd.detach(), idx_x[..., None], valid_mask(lx, ly, N, P1, P2, 1), 2)[..., 0]
+    return dict(loss=loss.detach(), gx=gx, gy=gy, S=S, n=max(P1, P2), scale=scale, per=per, terms_x=terms_x,
+                f32=(f32[0].detach(), fx, fy),
+                e_loss=float((f32[0].detach().double() - loss.detach()).abs().max()),
+                e_gx=float((fx.double() - gx).abs().max()), e_gy=float((fy.double() - gy).abs().max()))
+
+
+def check_sum_case(who, t, loss, gx, gy):
+    """The gates of test_fused_chamfer_loss_and_gradients_within_the_gates; returns whether all three hold (and prints them)."""
+    err = float((loss.detach().cpu().double() - t["loss"]).abs().max())
+    gate = 4 * t["e_loss"] + tree_depth(t["n"]) * 2.0 ** -24 * t["S"]
+    e_gx, e_gy = float((gx.cpu().double() - t["gx"]).abs().max()), float((gy.cpu().double() - t["gy"]).abs().max())
+    print(who, "loss error %.3g gate %.3g = 4 x %.3g + %d x 2^-24 x %.3g" % (err, gate, t["e_loss"], tree_depth(t["n"]), t["S"]),
+          "grad_x %.3g (float32 formulation %.3g)" % (e_gx, t["e_gx"]), "grad_y %.3g (%.3g)" % (e_gy, t["e_gy"]))
+    return err <= gate, e_gx <= 4 * t["e_gx"], e_gy <= 4 * t["e_gy"]
+
+
+# ---- the second pass of the grid-stride loops ------------------------------------------------------------------------------------------
+def big_clouds(D):
+    """N = 1, P1 = STREAM_CAP + 300 queries against 8 targets: the gather (one lane per query) and the scatter (one lane per hit and
+    coordinate) both go round their loops a second time."""
+    gen = torch.Generator().manual_seed(EDGE_SEED + 10 + D)
+    return torch.rand(1, BIG_P1, D, generator=gen), torch.rand(1, 8, D, generator=gen)

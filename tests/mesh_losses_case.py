@@ -129,12 +129,12 @@ def truth(name, verts, tables, grad_output=1.0):
     return float(loss.detach()), g, float(t.detach().abs().sum()) / tables["N"], int(t.numel())
 
 
-def package_formulation(verts_list, faces_list, dtype=torch.float32):
+def package_formulation(verts_list, faces_list, dtype=torch.float32, names=LOSSES + ("cot", "cotcurv")):
     """{loss name: (loss, grad)} of the package's torch formulation on the CPU (pytorch3d_amd/mesh_losses.py below its kernels)."""
     import pytorch3d_amd as p3d
 
     out = {}
-    for name in LOSSES + ("cot", "cotcurv"):
+    for name in names:
         v = [x.to(dtype).clone().requires_grad_(True) for x in verts_list]
         m = p3d.PackedMeshes(v, faces_list)
         if name in ("edge", "edge_target"):
@@ -181,6 +181,119 @@ def gates(name, verts_list, faces_list, tables, grad_output=1.0, f32=None):
     verts = torch.cat(verts_list, 0)
     t_loss, t_grad, S, n = truth(name, verts, tables, grad_output)
     f_loss, f_grad = (f32 if f32 is not None else float32_formulation(verts_list, faces_list))[name]
+    e32_loss = abs(f_loss - t_loss)
+    e32_grad = float((f_grad.double() * grad_output - t_grad).abs().max())
+    rec = {"E32_loss": e32_loss, "E32_grad": e32_grad, "S": S, "n": n, "D": depth(n)}
+    return t_loss, t_grad, 4 * e32_loss + depth(n) * 2.0 ** -24 * S, 4 * e32_grad, rec
+
+
+# ---- larger generated meshes and the vectorised restatements they need (tests/test_*_loss_kernel_edges.py) --------------------------------
+SUM_CAP = 256 * 256          # terms the first round of sum_partials_kernel covers: one partial per 256 terms, 256 lanes
+STREAM_CAP = 256 * 16 * 256  # items one pass of a grid-stride loop covers (stream_blocks: 4 096 blocks of 256 threads)
+
+
+def jittered_grid(n, gen, spacing=0.1, jitter=0.2):
+    """An open n x n vertex grid in the plane z = 0, `spacing` apart, every coordinate moved by up to jitter / 2 of the spacing:
+    (verts (n n, 3) float32, faces (2 (n - 1)^2, 3) int64).  n^2 vertices, 2 (n - 1)^2 faces, 3 (n - 1)^2 + 2 (n - 1) edges,
+    3 (n - 1)^2 - 2 (n - 1) wing pairs."""
+    g = torch.arange(n, dtype=torch.float32)
+    verts = torch.stack([g.repeat_interleave(n), g.repeat(n), torch.zeros(n * n)], 1)
+    verts = (verts + jitter * (torch.rand(n * n, 3, generator=gen) - 0.5)) * spacing
+    i, j = torch.arange(n - 1).repeat_interleave(n - 1), torch.arange(n - 1).repeat(n - 1)
+    a = i * n + j
+    b, c, d = a + 1, a + n, a + n + 1
+    faces = torch.stack([torch.stack([a, b, c], 1), torch.stack([b, d, c], 1)], 1).reshape(-1, 3)
+    return verts.float().contiguous(), faces.contiguous()
+
+
+def second_round_batch():
+    """ico_sphere(1) and a 257 x 257 grid: 66 049 + 42 vertices, 197 120 + 120 edges, 196 096 + 120 pairs -- each count beyond the
+    65 536 terms of the first round of the partial sums."""
+    gen = torch.Generator().manual_seed(79)
+    v, f = U.ico_sphere(1)
+    gv, gf = jittered_grid(257, gen)
+    return [(v + 0.03 * torch.randn(v.shape, generator=gen)).float().contiguous(), gv], [f.contiguous(), gf]
+
+
+def second_pass_mesh(n=1025):
+    """One n x n grid; at 1025: 1 050 625 vertices, 2 097 152 faces, 3 147 776 edges, 3 143 680 pairs -- the smallest at which the loops
+    over faces, vertices, edges and pairs all take a second pass."""
+    return jittered_grid(n, torch.Generator().manual_seed(80))
+
+
+def tensor_tables(verts_list, faces_list, device="cpu"):
+    """brute_tables as int64 tensors on `device`, by sorting instead of Python loops: edges (E, 2), edge_mesh, pairs (P, 4), pair_mesh,
+    vert_mesh, the adjacency as (adj_row, adj_col) ascending by (vertex, neighbour), N, V."""
+    nv = torch.tensor([v.shape[0] for v in verts_list], dtype=torch.int64)
+    base = torch.cumsum(nv, 0) - nv
+    faces = torch.cat([f.to(torch.int64) + int(b) for f, b in zip(faces_list, base)], 0).to(device)
+    V, N = int(nv.sum()), len(verts_list)
+    vert_mesh = torch.repeat_interleave(torch.arange(N), nv).to(device)
+    # corner 3 f + k: the edge opposite vertex k of face f and that vertex as its wing
+    lo = torch.minimum(faces[:, [1, 2, 0]], faces[:, [2, 0, 1]]).reshape(-1)
+    hi = torch.maximum(faces[:, [1, 2, 0]], faces[:, [2, 0, 1]]).reshape(-1)
+    wing = faces.reshape(-1)
+    order = torch.sort(lo * V + hi, stable=True).indices  # the corners by edge, 3 f + k ascending inside an edge
+    lo, hi, wing = lo[order], hi[order], wing[order]
+    first = torch.ones_like(lo, dtype=torch.bool)
+    first[1:] = (lo[1:] != lo[:-1]) | (hi[1:] != hi[:-1])
+    start = torch.nonzero(first).squeeze(1)               # where each edge's corners begin
+    count = torch.cat([start[1:], start.new_tensor([lo.numel()])]) - start
+    edges = torch.stack([lo[start], hi[start]], 1)
+    edge_mesh = vert_mesh[edges[:, 0]]
+    # pairs (i < j) of an edge's corners: edges ascending, then j, then i
+    rows = []
+    for j in range(1, int(count.max()) if count.numel() else 0):
+        has = torch.nonzero(count > j).squeeze(1)
+        for i in range(j):
+            rows.append(torch.stack([has, torch.full_like(has, j), torch.full_like(has, i)], 1))
+    if rows:
+        r = torch.cat(rows, 0)
+        r = r[torch.sort((r[:, 0] * 64 + r[:, 1]) * 64 + r[:, 2]).indices]
+        e = r[:, 0]
+        pairs = torch.stack([edges[e, 0], edges[e, 1], wing[start[e] + r[:, 2]], wing[start[e] + r[:, 1]]], 1)
+    else:
+        e, pairs = start.new_zeros((0,)), start.new_zeros((0, 4))
+    src, dst = torch.cat([edges[:, 0], edges[:, 1]]), torch.cat([edges[:, 1], edges[:, 0]])
+    by_vertex = torch.sort(src * V + dst).indices
+    return {"edges": edges, "edge_mesh": edge_mesh, "pairs": pairs, "pair_mesh": edge_mesh[e], "vert_mesh": vert_mesh,
+            "adj_row": src[by_vertex], "adj_col": dst[by_vertex], "N": N, "V": V}
+
+
+def terms_vectorised(name, verts, tt):
+    """terms() from tensor_tables, on the device of verts: the same formulas, the same order of the operations."""
+    N, V = tt["N"], tt["V"]
+    count = lambda mesh: torch.bincount(mesh, minlength=N)[mesh].to(verts.dtype)  # noqa: E731
+    if name in ("edge", "edge_target"):
+        e = tt["edges"]
+        d = verts[e[:, 0]] - verts[e[:, 1]]
+        return ((d * d).sum(1).sqrt() - (TARGET if name == "edge_target" else 0.0)) ** 2 / count(tt["edge_mesh"])
+    if name == "laplacian":
+        deg = torch.bincount(tt["adj_row"], minlength=V).clamp_min(1).to(verts.dtype)
+        r = torch.zeros_like(verts).index_add(0, tt["adj_row"], verts[tt["adj_col"]]) / deg[:, None] - verts
+        return r.norm(dim=1) / count(tt["vert_mesh"])
+    p = tt["pairs"]
+    x0 = verts[p[:, 0]]
+    e = verts[p[:, 1]] - x0
+    n0 = torch.cross(e, verts[p[:, 2]] - x0, dim=1)
+    n1 = -torch.cross(e, verts[p[:, 3]] - x0, dim=1)
+    cos = ((n0 / n0.norm(dim=1, keepdim=True).clamp_min(1e-8)) * (n1 / n1.norm(dim=1, keepdim=True).clamp_min(1e-8))).sum(1)
+    return (1 - cos) / count(tt["pair_mesh"])
+
+
+def truth_vectorised(name, verts, tt, grad_output=1.0):
+    """truth() from tensor_tables, float64 on the device of the tables."""
+    v = verts.to(tt["edges"].device).double().clone().requires_grad_(True)
+    t = terms_vectorised(name, v, tt)
+    loss = t.sum() / tt["N"]
+    (g,) = torch.autograd.grad(loss * grad_output, v)
+    return float(loss.detach()), g.cpu(), float(t.detach().abs().sum()) / tt["N"], int(t.numel())
+
+
+def gates_vectorised(name, verts_list, tt, f32, grad_output=1.0):
+    """gates() with truth_vectorised; f32: package_formulation(verts_list, faces_list) of the batch."""
+    t_loss, t_grad, S, n = truth_vectorised(name, torch.cat(verts_list, 0), tt, grad_output)
+    f_loss, f_grad = f32[name]
     e32_loss = abs(f_loss - t_loss)
     e32_grad = float((f_grad.double() * grad_output - t_grad).abs().max())
     rec = {"E32_loss": e32_loss, "E32_grad": e32_grad, "S": S, "n": n, "D": depth(n)}

@@ -118,3 +118,54 @@ def autograd_truth(verts, faces, grad_normals):
     n = reference_verts_normals(v, faces)
     (g,) = torch.autograd.grad(n, v, grad_normals.double())
     return n.detach(), g
+
+
+# ---- vectorised restatements for meshes too large for the Python loops above (tests/test_*_loss_kernel_edges.py) -------------------------
+def restated_forward_vectorised(verts, faces):
+    """restated_forward without the loops, on the device of verts: the rows raw[c // 3] added per vertex by one index_add over the
+    corners c = 3 f + j ascending (on the CPU that IS the list order, bit for bit; on the GPU the order is open, in float64)."""
+    fv = verts[faces]
+    raw = torch.cross(fv[:, 2] - fv[:, 1], fv[:, 0] - fv[:, 1], dim=1)
+    sums = torch.zeros_like(verts).index_add(0, faces.reshape(-1), raw.repeat_interleave(3, 0))
+    norm = sums.norm(dim=1, keepdim=True)
+    return sums / norm.clamp_min(EPS), sums
+
+
+def restated_backward_vectorised(grad_normals, verts, faces, sums):
+    """restated_backward without the loops (the same remark on the order)."""
+    norm = sums.norm(dim=1, keepdim=True)
+    n = sums / norm.clamp_min(EPS)
+    g_s = torch.where(norm > EPS, (grad_normals - n * (n * grad_normals).sum(1, keepdim=True)) / norm.clamp_min(EPS), grad_normals / EPS)
+    G = g_s[faces[:, 0]] + g_s[faces[:, 1]] + g_s[faces[:, 2]]
+    fv = verts[faces]
+    a, b = fv[:, 2] - fv[:, 1], fv[:, 0] - fv[:, 1]
+    g2, g0 = torch.cross(b, G, dim=1), torch.cross(G, a, dim=1)
+    rows = torch.stack([g0, -(g0 + g2), g2], 1).reshape(-1, 3)
+    return torch.zeros_like(verts).index_add(0, faces.reshape(-1), rows)
+
+
+def face_areas_normals_restated(verts, faces):
+    """(areas, normals) of the faces in the dtype of verts: c = (v1 - v0) x (v2 - v0), |c| / 2 and c / max(|c|, 1e-6)."""
+    fv = verts[faces]
+    c = torch.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0], dim=1)
+    norm = c.norm(dim=1)
+    return norm / 2.0, c / norm.clamp_min(EPS)[:, None]
+
+
+def face_areas_normals_backward_restated(grad_areas, grad_normals, verts, faces):
+    """What the reference's backward returns on faces with |c| > 1e-6, in the dtype of verts: the derivative of
+    face_areas_normals_restated by autograd, plus the ONE deviation the reference has (and a drop-in keeps): in d / d(v1.z) the term of
+    grad_normal_y is multiplied by c_x where the derivative has c_y.  With s = d(c)/d(v1.z) . c = (e_z x b) . c, b = v2 - v0, that
+    adds -grad_normal_y (c_x - c_y) s / |c|^3 to the z entry of the face's vertex 1."""
+    v = verts.detach().clone().requires_grad_(True)
+    areas, normals = face_areas_normals_restated(v, faces)
+    (g,) = torch.autograd.grad([areas, normals], v, [grad_areas.to(v.dtype), grad_normals.to(v.dtype)])
+    fv = verts[faces]
+    b = fv[:, 2] - fv[:, 0]
+    c = torch.cross(fv[:, 1] - fv[:, 0], b, dim=1)
+    norm = c.norm(dim=1)
+    ez = torch.zeros_like(b)
+    ez[:, 2] = 1.0
+    s = (torch.cross(ez, b, dim=1) * c).sum(1)
+    extra = -grad_normals[:, 1].to(v.dtype) * (c[:, 0] - c[:, 1]) * s / norm ** 3
+    return g.index_add(0, faces[:, 1], torch.stack([torch.zeros_like(extra), torch.zeros_like(extra), extra], 1))

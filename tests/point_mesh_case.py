@@ -1,5 +1,6 @@
 """The cases of the point-mesh distance tests, shared by tests/golden/make_golden_point_mesh.py (which records the reference's results
-into tests/golden/point_mesh_ref.npz), tests/test_cpu_point_mesh.py, tests/test_gpu_point_mesh.py and tests/shim_point_mesh_case.py.
+into tests/golden/point_mesh_ref.npz), tests/test_cpu_point_mesh.py, tests/test_gpu_point_mesh.py and tests/shim_point_mesh_case.py;
+at the end the generated batch of tests/test_cpu_loss_kernel_edges.py / tests/test_gpu_loss_kernel_edges.py.
 
 The fixture holds the inputs too.  Independent of the package: a float64 restatement of the pair distances (differentiated by
 autograd), the rule that admits a query to the index comparison, exact-tie soups and the star.
@@ -295,3 +296,109 @@ def check_mesh_loss(z, name, tag, loss, grad_verts, grad_points, who=""):
           "per-entry bound %.3g" % (who, name, tag, float(loss), want, tol, gerr, 4 * Eg, excess))
     assert abs(float(loss) - want) <= tol
     assert excess <= 0.0
+
+
+# ---- the second round of the element sums (tests/test_*_loss_kernel_edges.py) ---------------------------------------------------------------
+def sum_depth(n):
+    """Additions a term passes through in a fused loss whose largest element has n queries: 6 butterfly rounds in the wave, lane t of
+    one block adding the wave partials t, t + 256, ..., 8 more rounds (include/p3d_amd.h: p3d_point_mesh_forward), then the
+    elements and the two directions added."""
+    import math
+
+    return 6 + math.ceil(math.ceil(n / 64) / 256) + 8 + 2
+
+
+def second_round_batch():
+    """(verts list, faces list, points list, edges (E, 2) packed) of two elements, each direction with one element beyond the 16 384
+    queries = 256 wave partials of the first round while every distance matrix stays 16.5 k x a few dozen:
+      0. a jittered 92 x 92 vertex grid, 0.1 apart (16 562 faces of 5e-3 area and more on average -- both branches of the triangle
+         distance --, 25 025 edges), under a cloud of 30 points;
+      1. ico_sphere(0) around a cloud of 16 500 points INSIDE it (radius 0.3 .. 0.7 of the unit sphere's, the inscribed sphere has
+         0.79): a point inside a convex body is nearest to the interior of a face, so the nearest face is not a tie of the two faces
+         on an edge."""
+    import _util as U
+    import mesh_losses_case as ML
+
+    gen = torch.Generator().manual_seed(41)
+    gv, gf = ML.jittered_grid(92, gen)
+    above = torch.rand(30, 3, generator=gen) * torch.tensor([9.1, 9.1, 0.4]) + torch.tensor([0.0, 0.0, 0.05])
+    iv, iface = U.ico_sphere(0)
+    d = torch.randn(16500, 3, generator=gen)
+    inside = d / d.norm(dim=1, keepdim=True) * (0.3 + 0.4 * torch.rand(16500, 1, generator=gen))
+    verts, faces, points = [gv, iv.contiguous()], [gf, iface.contiguous()], [above.contiguous(), inside.float().contiguous()]
+    return verts, faces, points, ML.tensor_tables(verts, faces)["edges"]
+
+
+_SECOND = {}
+
+
+def second_round_truth(tag):
+    """Everything tests judge the fused loss `tag` ("face" / "edge") on second_round_batch() by, computed once and never modified:
+    per direction the float64 minima and gaps (minima64), the package's float32 torch formulation's distances and indices on the
+    CPU, its error E and the admission; the float64 loss on the minima, S (the same sum: every term is >= 0), the float64 gradients on
+    the formulation's indices, and the formulation's own loss and gradients through the package's loss on CPU tensors with their
+    largest error."""
+    if tag in _SECOND:
+        return _SECOND[tag]
+    import pytorch3d_amd as p3d
+    from pytorch3d_amd import point_mesh as pm
+
+    verts, faces, points, edges = second_round_batch()
+    N = len(verts)
+    nv = [v.shape[0] for v in verts]
+    packed_v, packed_p = torch.cat(verts, 0), torch.cat(points, 0)
+    if tag == "face":
+        index = torch.cat([f + b for f, b in zip(faces, first_idx(nv).tolist())], 0)
+        num_prims = [f.shape[0] for f in faces]
+    else:
+        index = edges
+        num_prims = torch.bincount(torch.searchsorted(first_idx(nv), edges[:, 0].contiguous(), right=True) - 1, minlength=N).tolist()
+    num_points = [p.shape[0] for p in points]
+    prims = packed_v[index]
+    pfirst, sfirst = first_idx(num_points), first_idx(num_prims)
+    out = {"index": index, "num_points": num_points, "num_prims": num_prims, "pfirst": pfirst, "sfirst": sfirst, "points": packed_p,
+           "prims": prims, "directions": {}}
+    loss64, e_minima = 0.0, 0.0
+    gp64, gs64 = torch.zeros(packed_p.shape, dtype=torch.float64), torch.zeros(prims.shape, dtype=torch.float64)
+    for direction in DIRECTIONS["tri" if tag == "face" else "seg"]:
+        point_query = direction.startswith("point")
+        best64, gap = minima64(packed_p, prims, num_points, num_prims, point_query)
+        want_d, want_i = pm.torch_forward(direction, packed_p, pfirst, prims, sfirst)
+        E = float((want_d.double() - best64).abs().max())
+        counts = num_points if point_query else num_prims
+        w = torch.cat([torch.full((c,), 1.0 / (c * N), dtype=torch.float64) for c in counts])
+        loss64 += float((best64 * w).sum())
+        e_minima += E
+        a, b = grads64(packed_p, prims, want_i, w, torch.ones_like(gap, dtype=torch.bool), point_query)
+        gp64, gs64 = gp64 + a, gs64 + b
+        out["directions"][direction] = dict(best64=best64, gap=gap, want_i=want_i, E=E, ok=admitted(gap, E), max_queries=max(counts))
+    gv64 = torch.zeros(packed_v.shape, dtype=torch.float64).index_add(0, index.reshape(-1), gs64.reshape(-1, 3))
+    v32, p32 = [v.clone().requires_grad_(True) for v in verts], [p.clone().requires_grad_(True) for p in points]
+    meshes, pcls = p3d.PackedMeshes(v32, faces), p3d.PackedPointclouds(p32)
+    f_loss = p3d.point_mesh_face_distance(meshes, pcls) if tag == "face" else p3d.point_mesh_edge_distance(meshes, pcls)
+    f_grads = torch.autograd.grad(f_loss, v32 + p32)
+    f_gv, f_gp = torch.cat(f_grads[:N], 0), torch.cat(f_grads[N:], 0)
+    out.update(loss64=loss64, S=loss64, E_minima=e_minima, grad_verts64=gv64, grad_points64=gp64, f32_loss=float(f_loss.detach()),
+               f32_grad_verts=f_gv, f32_grad_points=f_gp,
+               E_grad=max(float((f_gv.double() - gv64).abs().max()), float((f_gp.double() - gp64).abs().max())),
+               n=max(max(num_points), max(num_prims)))
+    _SECOND[tag] = out
+    return out
+
+
+def check_second_round_loss(who, t, loss, grad_verts, grad_points):
+    """The loss within 4 E + sum_depth(n) 2^-24 S (E: the two directions' largest errors of the minima, added -- the loss is two
+    weighted means of them); the gradients per entry within 4 x the formulation's largest error + 4 x 2^-24 of the entry
+    (check_mesh_loss).  Returns (loss ok, gradients ok)."""
+    tol = 4 * t["E_minima"] + sum_depth(t["n"]) * 2.0 ** -24 * t["S"]
+    loss = float(loss.detach()) if torch.is_tensor(loss) else float(loss)
+    err = abs(loss - t["loss64"])
+    gerr, excess = 0.0, -1.0
+    for got, ref in ((grad_verts, t["grad_verts64"]), (grad_points, t["grad_points64"])):
+        e = (got.detach().cpu().double() - ref).abs()
+        gerr = max(gerr, float(e.max()))
+        excess = max(excess, float((e - (4 * t["E_grad"] + 4 * 2.0 ** -24 * ref.abs())).max()))
+    print("%s: loss %.9g, float64 %.9g, error %.3g (tolerance %.3g = 4 x %.3g + %d x 2^-24 x %.3g); gradient error %.3g (4 E_grad = %.3g), "
+          "largest excess over the per-entry bound %.3g" % (who, float(loss), t["loss64"], err, tol, t["E_minima"], sum_depth(t["n"]), t["S"],
+                                                           gerr, 4 * t["E_grad"], excess))
+    return err <= tol, excess <= 0.0
