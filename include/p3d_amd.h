@@ -267,9 +267,9 @@ int p3d_verts_normals_backward(const float* grad_normals, const float* verts, co
  *   pairs (P,4): the wing pairs (v0, v1, a, b) of normal consistency -- (v0, v1) an edge, a and b the vertices opposite it on two
  *   of its faces; offsets (V + 1), slots (4 P): per vertex the slots 4 pair + role that name it, sorted stably by vertex.
  * 4 P, 2 E and V must fit an int32; N > 0.  loss: ONE float, (sum of the terms) / N.  grad_loss: ONE float on the device.
- * No float atomics: every sum of n terms is a tree whose shape depends on n alone, of depth
- *   D(n) = 8 + ceil(ceil(n / 256) / 256) + 8
- * (csrc/mesh_losses.hip), so a loss and its gradient have the same bits on every run and stream.  Forward workspaces hold one
+ * No float atomics: every sum of n terms is the fixed tree of csrc/fixed_sum.h over blocks of 256 terms, of depth
+ *   D(n) = 8 + ceil(ceil(n / 256) / 256) + 8,
+ * so a loss and its gradient have the same bits on every run and stream.  Forward workspaces hold one
  * partial sum per 256 terms; every byte that is read was written by the same call.  A table that breaks its contract gives NaN
  * or wrong numbers, never an access outside the arrays (ids are range-checked, CSR offsets clamped). */
 size_t p3d_mesh_edge_loss_forward_workspace_bytes(int64_t E);
@@ -730,8 +730,7 @@ int p3d_knn_points_forward(const float* p1, const float* p2, const int64_t* leng
 /* One direction of chamfer_distance: the K = 1 forward (idx, dists (N,P1), masked as above) and, in the same launch, the terms
  * dists[n,i] * weights[n] (weights (N) f32 or NULL) summed per wave; a second small launch sums a cloud's partials:
  * sums (N) f32 <- the cloud's sum, divided by max(lengths1[n], 1) when point_mean != 0.  No float atomic: the sum of a cloud's P1
- * terms is a tree whose shape depends on P1 alone (6 butterfly rounds in a wave of 64 queries, lane t of one block of 256 adds the
- * partials t, t + 256, ... ascending, 8 more rounds), depth D(P1) = 6 + ceil(ceil(P1 / 64) / 256) + 8.
+ * terms is the fixed tree of csrc/fixed_sum.h over waves of 64 queries, depth D(P1) = 6 + ceil(ceil(P1 / 64) / 256) + 8.
  * workspace: p3d_chamfer_forward_workspace_bytes(N, P1) bytes, every byte read was written by the same call. */
 size_t p3d_chamfer_forward_workspace_bytes(int64_t N, int64_t P1);
 int p3d_chamfer_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, const float* weights,
@@ -773,9 +772,8 @@ int p3d_knn_points_ordered_backward(const float* p1, const float* p2, const int6
  * One lane per query, a wave = 64 consecutive queries of one element, targets staged in LDS tiles of P3D_POINT_MESH_TILE records.
  * split: waves per workgroup that share the 64 queries and take every split-th tile, 1 / 2 / 4 / 8, or 0 = chosen from the workgroup
  * count and the device's CU count.  The result is bit-equal for every split.
- * sums != NULL fuses one direction of the loss: dists[q] * weights[n] (weights (N) f32 or NULL = 1) summed per wave (6 butterfly
- * rounds), then per element by a second launch (lane t of one block of 256 adds the partials t, t + 256, ... ascending, 8 more
- * rounds): sums (N) f32.  No float atomic.  workspace: p3d_point_mesh_forward_workspace_bytes(N, max_queries) bytes (sums only). */
+ * sums != NULL fuses one direction of the loss: dists[q] * weights[n] (weights (N) f32 or NULL = 1) summed per wave of 64 queries,
+ * then per element by a second launch -- the fixed tree of csrc/fixed_sum.h: sums (N) f32.  No float atomic.  workspace: p3d_point_mesh_forward_workspace_bytes(N, max_queries) bytes (sums only). */
 #define P3D_POINT_MESH_POINT 0
 #define P3D_POINT_MESH_SEGMENT 1
 #define P3D_POINT_MESH_TRIANGLE 2

@@ -16,14 +16,17 @@
 // One wave per workgroup keeps 1 x 5000 x 5000 at 79 workgroups instead of 20 and needs no workgroup barrier beyond the wave's own;
 // the tile is re-staged per wave from L2 (D * 2 KiB per 512 x 64 pairs).
 //
-// Chamfer: the K = 1 kernel also multiplies a query's distance by its cloud's weight and sums the wave with six butterfly rounds;
-// a second launch (one block per cloud) adds a cloud's wave partials in a fixed order.  No float atomic in the forward.
+// Chamfer: the K = 1 kernel also multiplies a query's distance by its cloud's weight and sums the wave; a second launch (one block
+// per cloud) adds a cloud's wave partials: the fixed tree of fixed_sum.h with a wave of 64 queries at level 1.  No float atomic in
+// the forward.
 //
 // Backward: grad_p1 is a gather (one lane per (n, i), k ascending).  grad_p2 is a scatter with float atomics, lane = hit * D +
 // coordinate so that the D values of one hit leave from adjacent lanes (profiles/microbench/global_atomic_mi355x.txt), after
 // consecutive hits of one point have been summed inside the wave; its ordered form is in ordered_bwd.hip.  All three take a hit's
 // terms from knn_grad.h.
+#include "fixed_sum.h"
 #include "knn_grad.h"
+#include "vec3.h"
 
 namespace p3d {
 namespace {
@@ -31,7 +34,6 @@ namespace {
 constexpr int kTile = P3D_KNN_TILE;
 static_assert(kTile % 4 == 0, "a tile is read four points at a time");
 
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
 __device__ __forceinline__ float pos_inf() { return __int_as_float(0x7f800000); }
 
 template <int NORM>
@@ -143,35 +145,23 @@ __global__ __launch_bounds__(64) void knn_kernel(const float* __restrict__ p1, c
   if constexpr (KQ == 1) {
     if (partials) {  // wave-uniform
       const float w = weights ? weights[n] : 1.0f;
-      float term = live && found > 0 ? best.d[0] * w : 0.0f;
-#pragma unroll
-      for (int d = 1; d < kWave; d <<= 1) term += __shfl_xor(term, d);
+      const float term = wave_sum(live && found > 0 ? best.d[0] * w : 0.0f);
       if (lane == 0) partials[blockIdx.x] = term;
     }
   }
 }
 
-// One block per cloud: lane t adds the wave partials t, t + 256, ... ascending, then eight butterfly rounds.
-__global__ __launch_bounds__(256) void chamfer_cloud_sum_kernel(const float* __restrict__ partials, const int64_t* __restrict__ lengths1,
-                                                                int64_t P1, int64_t blocks_per_cloud, int point_mean,
-                                                                float* __restrict__ sums) {
-  __shared__ float part[4];
-  const int64_t n = blockIdx.x;
-  float acc = 0.0f;
-  for (int64_t b = threadIdx.x; b < blocks_per_cloud; b += 256) acc += partials[n * blocks_per_cloud + b];
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) acc += __shfl_xor(acc, d);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = (part[0] + part[1]) + (part[2] + part[3]);
-    if (point_mean) {
-      const int64_t len1 = knn::cloud_length(lengths1, n, P1);
-      s = s / (float)(len1 < 1 ? 1 : len1);  // cham_x /= x_lengths.clamp(min=1)
-    }
-    sums[n] = s;
+// the last step of segment_sum_kernel over a cloud's wave partials: for point_mean, cham_x /= x_lengths.clamp(min=1)
+struct CloudMean {
+  const int64_t* lengths1;
+  int64_t P1;
+  int point_mean;
+  __device__ __forceinline__ float operator()(int64_t n, float s) const {
+    if (!point_mean) return s;
+    const int64_t len1 = knn::cloud_length(lengths1, n, P1);
+    return s / (float)(len1 < 1 ? 1 : len1);
   }
-}
+};
 
 // grad_p1: one lane per (n, i); every entry written
 template <int D>
@@ -196,7 +186,8 @@ __global__ __launch_bounds__(256) void knn_bwd_gather_kernel(knn::Hits h, float*
 // grad_p2: lane = hit * D + coordinate, a wave owns kWave / D consecutive hits (the last 64 % D lanes idle).  Consecutive hits of
 // one p2 point -- a cloud that many queries share one neighbour of -- are first summed inside the wave by a segmented scan over the
 // run (ordered_sum.h's), and the last hit of a run issues the atomics: its D adjacent lanes.  Runs of one hit, the common case, go
-// through unchanged.
+// through unchanged.  The scan is written out here, in ordered_sum.h (pass1_kernel) and in transform.hip on purpose: hoisted into a
+// shared helper it compiled ordered::pass1_kernel<Op> to 2-3 % more instructions (ordered_sum.h has the figures).
 template <int D>
 __global__ __launch_bounds__(256) void knn_bwd_scatter_kernel(knn::Hits h, int64_t nwaves, float* __restrict__ grad_p2) {
   constexpr int kHits = kWave / D;  // hits per wave
@@ -222,12 +213,6 @@ __global__ __launch_bounds__(256) void knn_bwd_scatter_kernel(knn::Hits h, int64
     const bool tail = hw + 1 >= kHits || after != t;
     if (t >= 0 && tail) atomicAdd(grad_p2 + t * D + c, v);
   }
-}
-
-unsigned stream_blocks(int64_t items) {
-  int64_t blocks = ceil_div(items, 256);
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  return (unsigned)blocks;
 }
 
 // every index the kernels form must fit an int64 comfortably and a hit's j an int32
@@ -306,7 +291,7 @@ P3D_API int p3d_chamfer_forward(const float* p1, const float* p2, const int64_t*
     if (rc != P3D_OK) return rc;
   }
   LaunchScope ls("chamfer_cloud_sum", s);
-  chamfer_cloud_sum_kernel<<<(unsigned)N, 256, 0, s>>>(partials, lengths1, P1, ceil_div(P1, kWave), point_mean, sums);
+  segment_sum_kernel<<<(unsigned)N, 256, 0, s>>>(partials, ceil_div(P1, kWave), CloudMean{lengths1, P1, point_mean}, sums);
   return launch_status();
 }
 

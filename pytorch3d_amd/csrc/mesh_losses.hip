@@ -4,49 +4,29 @@
 // The reference redoes the topology's work every step (sort + bincount + a host round trip for the wing pairs, a sparse V x V matrix
 // for the Laplacian, gathers whose autograd ends in index_put / sparse mm with float atomics).  Here the topology is a set of int32
 // tables built once (pytorch3d_amd/mesh_losses.py: mesh_loss_topology) and every step is a GATHER:
-//   * forward: one lane per edge / vertex / wing pair computes its term, the terms are summed by a fixed tree (below);
+//   * forward: one lane per edge / vertex / wing pair computes its term, the terms are summed by the fixed tree of fixed_sum.h;
 //   * backward of the edge loss and of the Laplacian: one lane per vertex walks its row of the adjacency CSR;
 //   * backward of normal consistency: one lane per pair stores the gradients of its four vertices as rows (P, 4, 3), a second launch
-//     sums, per vertex, the rows of its incidence list in list order (the shape of normals.hip).
-// No float atomic anywhere.  THE SUM OF n TERMS is a tree whose shape depends on n alone:
-//   level 1  block b of 256 lanes owns terms 256 b .. 256 b + 255 (a lane past n holds +0): six xor-butterfly rounds inside each of
-//            its four waves, then (w0 + w1) + (w2 + w3) -> partial[b];
-//   level 2  ONE block of 256 lanes: lane t adds partial[t], partial[t + 256], ... in ascending order, then the same eight rounds;
-//            the result is divided by the number of meshes and stored.
-// A term passes through at most  D(n) = 8 + ceil(ceil(n / 256) / 256) + 8  additions; the loss and the gradient have the same bits
-// on every run, stream and process.
+//     sums, per vertex, the rows of its incidence list in list order (csr_gather.h, shared with normals.hip).
+// No float atomic anywhere.  The sum of n terms is the tree of fixed_sum.h with a block of 256 terms at level 1 and the whole batch
+// as the one segment of level 2, finished by the division by the number of meshes: a term passes through at most
+// D(n) = 8 + ceil(ceil(n / 256) / 256) + 8  additions; the loss and the gradient have the same bits on every run, stream and process.
 // Forward values follow the reference's Python one float32 operation per torch operation (the library is built with
 // -ffp-contract=off; IEEE sqrt and division); arithmetic that only a gradient sees may contract.
 // The tables are the caller's: a vertex id outside [0, V) or a mesh id outside [0, N) makes its term NaN, CSR offsets are clamped
 // to the list and list entries out of range skipped -- a table that breaks its contract gives wrong numbers, never an access
 // outside the arrays.
-#include "p3d_common.h"
+#include "csr_gather.h"
+#include "fixed_sum.h"
 
 namespace p3d {
 namespace {
 
-struct v3 {
-  float x, y, z;
-};
-__device__ __forceinline__ v3 mkv(float x, float y, float z) {
-  v3 r;
-  r.x = x, r.y = y, r.z = z;
-  return r;
-}
-__device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mkv(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return mkv(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ v3 operator*(v3 a, float s) { return mkv(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ v3 neg(v3 a) { return mkv(-a.x, -a.y, -a.z); }
-__device__ __forceinline__ v3 cross(v3 a, v3 b) { return mkv(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ v3 load3(const float* p) { return mkv(p[0], p[1], p[2]); }
-__device__ __forceinline__ void store3(float* p, v3 a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
-
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+struct MeshLosses;  // this translation unit's instance of vert_gather_sum_kernel
 
 // A vertex by a table's id: nothing outside `verts` is read, an id out of range gives NaN coordinates.
-__device__ __forceinline__ v3 vertex(const float* __restrict__ verts, int64_t id, int64_t V) {
-  if (id < 0 || id >= V) return mkv(quiet_nan(), quiet_nan(), quiet_nan());
+__device__ __forceinline__ V3 vertex(const float* __restrict__ verts, int64_t id, int64_t V) {
+  if (id < 0 || id >= V) return mk(quiet_nan(), quiet_nan(), quiet_nan());
   return load3(verts + id * 3);
 }
 
@@ -56,29 +36,11 @@ __device__ __forceinline__ float mesh_weight(const int32_t* __restrict__ counts,
   return 1.0f / (float)counts[mesh];
 }
 
-// ---- the fixed tree ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) x += __shfl_xor(x, d);
-  return x;
-}
-
-// every lane of the block calls it (no early return in front); lane 0 of the block holds the sum
-__device__ __forceinline__ float block_sum_256(float x) {
-  __shared__ float part[4];
-  x = wave_sum(x);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-__global__ __launch_bounds__(256) void sum_partials_kernel(const float* __restrict__ partials, int64_t nparts, int N,
-                                                           float* __restrict__ loss) {
-  float acc = 0.0f;
-  for (int64_t i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
-  const float s = block_sum_256(acc);
-  if (threadIdx.x == 0) loss[0] = s / (float)N;  // loss.sum() / N
-}
+// the last step of segment_sum_kernel: loss.sum() / N
+struct DivideByMeshes {
+  int N;
+  __device__ __forceinline__ float operator()(int64_t, float s) const { return s / (float)N; }
+};
 
 // ---- mesh_edge_loss ------------------------------------------------------------------------------------------------------------
 // mesh_edge_loss.py:47-52: ((v0 - v1).norm(dim=1, p=2) - target) ** 2.0 * weights
@@ -88,8 +50,8 @@ __global__ __launch_bounds__(256) void edge_loss_fwd_kernel(const float* __restr
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   float term = 0.0f;
   if (e < E) {
-    const v3 d = vertex(verts, edges[e * 2], V) - vertex(verts, edges[e * 2 + 1], V);
-    const float len = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+    const V3 d = vertex(verts, edges[e * 2], V) - vertex(verts, edges[e * 2 + 1], V);
+    const float len = norm3(d);
     const float t = len - target;
     term = (t * t) * mesh_weight(num_edges, edge_mesh[e], N);
   }
@@ -107,15 +69,14 @@ __global__ __launch_bounds__(256) void edge_loss_bwd_kernel(const float* __restr
 #pragma clang fp contract(fast)
   const float g = grad_loss[0] / (float)N;
   for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
-    int64_t begin = adj_offsets[v], end = adj_offsets[v + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > n_adj ? n_adj : end;
-    const v3 x = load3(verts + v * 3);
-    v3 s = mkv(0.f, 0.f, 0.f);
+    int64_t begin, end;
+    csr_row(adj_offsets, v, n_adj, begin, end);
+    const V3 x = load3(verts + v * 3);
+    V3 s = mk(0.f, 0.f, 0.f);
     for (int64_t i = begin; i < end; ++i) {
       const int64_t u = adj[i];
       if (u < 0 || u >= V) continue;
-      const v3 d = x - load3(verts + u * 3);
+      const V3 d = x - load3(verts + u * 3);
       const float len = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
       const float k = len == 0.0f ? 0.0f : 2.0f * (len - target) / len;
       s = s + d * k;
@@ -136,15 +97,14 @@ __global__ __launch_bounds__(256) void laplacian_fwd_kernel(const float* __restr
   const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
   float term = 0.0f;
   if (v < V) {
-    int64_t begin = adj_offsets[v], end = adj_offsets[v + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > n_adj ? n_adj : end;
-    v3 s = mkv(0.f, 0.f, 0.f);
+    int64_t begin, end;
+    csr_row(adj_offsets, v, n_adj, begin, end);
+    V3 s = mk(0.f, 0.f, 0.f);
     for (int64_t i = begin; i < end; ++i) s = s + vertex(verts, adj[i], V);
     const float deg = (float)(end - begin);
-    if (end > begin) s = mkv(s.x / deg, s.y / deg, s.z / deg);
-    const v3 r = s - load3(verts + v * 3);
-    const float norm = sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
+    if (end > begin) s = s / deg;
+    const V3 r = s - load3(verts + v * 3);
+    const float norm = norm3(r);
     const float w = mesh_weight(num_verts, vert_mesh[v], N);
     term = norm * w;
     const float k = norm == 0.0f ? 0.0f : w / norm;
@@ -161,16 +121,14 @@ __global__ __launch_bounds__(256) void laplacian_bwd_kernel(const float* __restr
 #pragma clang fp contract(fast)
   const float g = grad_loss[0] / (float)N;
   for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
-    int64_t begin = adj_offsets[v], end = adj_offsets[v + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > n_adj ? n_adj : end;
-    v3 s = mkv(0.f, 0.f, 0.f);
+    int64_t begin, end;
+    csr_row(adj_offsets, v, n_adj, begin, end);
+    V3 s = mk(0.f, 0.f, 0.f);
     for (int64_t i = begin; i < end; ++i) {
       const int64_t u = adj[i];
       if (u < 0 || u >= V) continue;
-      int64_t ub = adj_offsets[u], ue = adj_offsets[u + 1];
-      ub = ub < 0 ? 0 : ub;
-      ue = ue > n_adj ? n_adj : ue;
+      int64_t ub, ue;
+      csr_row(adj_offsets, u, n_adj, ub, ue);
       if (ue > ub) s = s + load3(q + u * 3) * (1.0f / (float)(ue - ub));
     }
     store3(grad_verts + v * 3, (s - load3(q + v * 3)) * g);
@@ -180,22 +138,20 @@ __global__ __launch_bounds__(256) void laplacian_bwd_kernel(const float* __restr
 // ---- mesh_normal_consistency ---------------------------------------------------------------------------------------------------
 // A wing pair (v0, v1, a, b): n0 = (x_v1 - x_v0) x (x_a - x_v0), n1 = -((x_v1 - x_v0) x (x_b - x_v0)) (mesh_normal_consistency.py:113-125).
 struct Wing {
-  v3 e, p, q, n0, n1;
+  V3 e, p, q, n0, n1;
 };
 __device__ __forceinline__ Wing wing(const float* __restrict__ verts, const int32_t* __restrict__ pairs, int64_t i, int64_t V) {
-  const v3 x0 = vertex(verts, pairs[i * 4 + 0], V);
+  const V3 x0 = vertex(verts, pairs[i * 4 + 0], V);
   Wing w;
   w.e = vertex(verts, pairs[i * 4 + 1], V) - x0;
   w.p = vertex(verts, pairs[i * 4 + 2], V) - x0;
   w.q = vertex(verts, pairs[i * 4 + 3], V) - x0;
   w.n0 = cross(w.e, w.p);
-  w.n1 = neg(cross(w.e, w.q));
+  w.n1 = -cross(w.e, w.q);
   return w;
 }
 
 constexpr float kCosEps = 1e-8f;  // cosine_similarity's default eps
-
-__device__ __forceinline__ float norm3(v3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
 
 // torch.cosine_similarity(n0, n1, dim=1) of torch 2.x (ATen/native/Distance.cpp): each vector is divided by its own norm,
 // clamped from below at eps, and the quotients are multiplied and summed: ((x1 / max(|x1|, eps)) * (x2 / max(|x2|, eps))).sum().
@@ -208,7 +164,7 @@ __global__ __launch_bounds__(256) void normal_consistency_fwd_kernel(const float
   if (i < P) {
     const Wing w = wing(verts, pairs, i, V);
     const float c0 = fmaxf(norm3(w.n0), kCosEps), c1 = fmaxf(norm3(w.n1), kCosEps);
-    const v3 a = mkv(w.n0.x / c0, w.n0.y / c0, w.n0.z / c0), b = mkv(w.n1.x / c1, w.n1.y / c1, w.n1.z / c1);
+    const V3 a = w.n0 / c0, b = w.n1 / c1;
     const float cosine = a.x * b.x + a.y * b.y + a.z * b.z;
     term = (1.0f - cosine) * mesh_weight(num_pairs, pair_mesh[i], N);
   }
@@ -219,11 +175,11 @@ __global__ __launch_bounds__(256) void normal_consistency_fwd_kernel(const float
 // The gradient of a = x / c, c = max(|x|, eps), as autograd takes it through cosine_similarity: the clamp is applied to the VALUE of
 // the norm under no_grad, so d a = d x / c - x (x . d x) / (|x| c^2), and the second term is absent where |x| == 0 (the norm's
 // backward is masked there).  Where |x| >= eps this is the derivative of x / |x|.
-__device__ __forceinline__ v3 unit_grad(v3 x, v3 up) {
+__device__ __forceinline__ V3 unit_grad(V3 x, V3 up) {
 #pragma clang fp contract(fast)
   const float n = norm3(x);
   const float c = fmaxf(n, kCosEps);
-  const v3 direct = up * (1.0f / c);
+  const V3 direct = up * (1.0f / c);
   if (n == 0.0f) return direct;
   return direct - x * (dot(up, x) / (c * c * n));
 }
@@ -241,39 +197,15 @@ __global__ __launch_bounds__(256) void normal_consistency_bwd_rows_kernel(const 
     const Wing w = wing(verts, pairs, i, V);
     const float c0 = fmaxf(norm3(w.n0), kCosEps), c1 = fmaxf(norm3(w.n1), kCosEps);
     const float gc = -(g * mesh_weight(num_pairs, pair_mesh[i], N));  // d loss / d cosine
-    const v3 a = w.n0 * (1.0f / c0), b = w.n1 * (1.0f / c1);
-    const v3 G0 = unit_grad(w.n0, b * gc), H = neg(unit_grad(w.n1, a * gc));
-    const v3 de = cross(w.p, G0) + cross(w.q, H), dp = cross(G0, w.e), dq = cross(H, w.e);
+    const V3 a = w.n0 * (1.0f / c0), b = w.n1 * (1.0f / c1);
+    const V3 G0 = unit_grad(w.n0, b * gc), H = -unit_grad(w.n1, a * gc);
+    const V3 de = cross(w.p, G0) + cross(w.q, H), dp = cross(G0, w.e), dq = cross(H, w.e);
     float* out = rows + i * 12;
-    store3(out + 0, neg(de + dp + dq));
+    store3(out + 0, -(de + dp + dq));
     store3(out + 3, de);
     store3(out + 6, dp);
     store3(out + 9, dq);
   }
-}
-
-// One lane per vertex: +0 plus the rows of its slots (4 pair + role) in list order (normals.hip: vert_gather_sum_kernel).
-__global__ __launch_bounds__(256) void vert_slot_sum_kernel(const float* __restrict__ rows, const int32_t* __restrict__ offsets,
-                                                            const int32_t* __restrict__ slots, int64_t V, int64_t n_slots,
-                                                            float* __restrict__ grad_verts) {
-  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
-    int64_t begin = offsets[v], end = offsets[v + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > n_slots ? n_slots : end;
-    v3 s = mkv(0.f, 0.f, 0.f);
-    for (int64_t i = begin; i < end; ++i) {
-      const int64_t c = slots[i];
-      if (c < 0 || c >= n_slots) continue;
-      s = s + load3(rows + c * 3);
-    }
-    store3(grad_verts + v * 3, s);
-  }
-}
-
-unsigned stream_blocks(int64_t items) {
-  int64_t blocks = ceil_div(items, 256);
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  return (unsigned)blocks;
 }
 
 size_t partial_bytes(int64_t n) { return n <= 0 ? 0 : (size_t)ceil_div(n, 256) * sizeof(float); }
@@ -306,7 +238,7 @@ P3D_API int p3d_mesh_edge_loss_forward(const float* verts, const int32_t* edges,
   LaunchScope ls("mesh_edge_loss_forward", s);
   if (E > 0)
     edge_loss_fwd_kernel<<<(unsigned)ceil_div(E, 256), 256, 0, s>>>(verts, edges, edge_mesh, num_edges, V, E, N, target_length, partials);
-  sum_partials_kernel<<<1, 256, 0, s>>>(partials, ceil_div(E, 256), N, loss);
+  segment_sum_kernel<<<1, 256, 0, s>>>(partials, ceil_div(E, 256), DivideByMeshes{N}, loss);
   return launch_status();
 }
 
@@ -336,7 +268,7 @@ P3D_API int p3d_mesh_laplacian_forward(const float* verts, const int32_t* adj_of
   LaunchScope ls("mesh_laplacian_forward", s);
   if (V > 0)
     laplacian_fwd_kernel<<<(unsigned)ceil_div(V, 256), 256, 0, s>>>(verts, adj_offsets, adj, vert_mesh, num_verts, V, E * 2, N, q, partials);
-  sum_partials_kernel<<<1, 256, 0, s>>>(partials, ceil_div(V, 256), N, loss);
+  segment_sum_kernel<<<1, 256, 0, s>>>(partials, ceil_div(V, 256), DivideByMeshes{N}, loss);
   return launch_status();
 }
 
@@ -362,7 +294,7 @@ P3D_API int p3d_mesh_normal_consistency_forward(const float* verts, const int32_
   LaunchScope ls("mesh_normal_consistency_forward", s);
   if (P > 0)
     normal_consistency_fwd_kernel<<<(unsigned)ceil_div(P, 256), 256, 0, s>>>(verts, pairs, pair_mesh, num_pairs, V, P, N, partials);
-  sum_partials_kernel<<<1, 256, 0, s>>>(partials, ceil_div(P, 256), N, loss);
+  segment_sum_kernel<<<1, 256, 0, s>>>(partials, ceil_div(P, 256), DivideByMeshes{N}, loss);
   return launch_status();
 }
 
@@ -379,6 +311,7 @@ P3D_API int p3d_mesh_normal_consistency_backward(const float* grad_loss, const f
   float* rows = static_cast<float*>(workspace);
   LaunchScope ls("mesh_normal_consistency_backward", s);
   normal_consistency_bwd_rows_kernel<<<stream_blocks(P), 256, 0, s>>>(grad_loss, verts, pairs, pair_mesh, num_pairs, V, P, N, rows);
-  vert_slot_sum_kernel<<<stream_blocks(V), 256, 0, s>>>(rows, offsets, slots, V, P * 4, grad_verts);
+  // one lane per vertex: +0 plus the rows of its slots (4 pair + role) in list order
+  vert_gather_sum_kernel<MeshLosses, false, false><<<stream_blocks(V), 256, 0, s>>>(rows, offsets, slots, V, P * 4, grad_verts, nullptr);
   return launch_status();
 }

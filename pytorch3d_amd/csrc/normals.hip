@@ -11,28 +11,14 @@
 //     of its list in list order.  No float atomic anywhere: the result is a pure function of verts, faces and the list, with the
 //     same bits on every run, stream and process.  The backward has the same two-kernel shape.
 // IEEE sqrt and division throughout (no rsqrt, no rcp): the forwards are compared with the reference at 1e-6 and below.
-#include "p3d_common.h"
+#include "csr_gather.h"
 
 namespace p3d {
 namespace {
 
-struct v3 {
-  float x, y, z;
-};
-__device__ __forceinline__ v3 mkv(float x, float y, float z) {
-  v3 r;
-  r.x = x, r.y = y, r.z = z;
-  return r;
-}
-__device__ __forceinline__ v3 operator-(v3 a, v3 b) { return mkv(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ v3 operator+(v3 a, v3 b) { return mkv(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ v3 cross(v3 a, v3 b) { return mkv(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ v3 unit(int d) { return mkv(d == 0 ? 1.f : 0.f, d == 1 ? 1.f : 0.f, d == 2 ? 1.f : 0.f); }
-__device__ __forceinline__ v3 load3(const float* p) { return mkv(p[0], p[1], p[2]); }
-__device__ __forceinline__ void store3(float* p, v3 a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
+struct Normals;  // this translation unit's instances of vert_gather_sum_kernel
 
-constexpr float kNormEps = 1e-6f;  // face_areas_normals.cu:58 and F.normalize(eps=1e-6)
+__device__ __forceinline__ V3 unit(int d) { return mk(d == 0 ? 1.f : 0.f, d == 1 ? 1.f : 0.f, d == 2 ? 1.f : 0.f); }
 
 // A vertex id as torch indexing reads it (a negative id wraps once); -1 when it is still outside [0, V).
 __device__ __forceinline__ int64_t vertex_id(const int64_t* __restrict__ faces, int64_t corner, int64_t V) {
@@ -43,9 +29,8 @@ __device__ __forceinline__ int64_t vertex_id(const int64_t* __restrict__ faces, 
 
 // The vertex of a corner, as gather_faces_kernel (gather.hip) returns it: nothing outside `verts` is read, an id out of range
 // gives NaN coordinates (visible downstream, never silent garbage).
-__device__ __forceinline__ v3 corner_vertex(const float* __restrict__ verts, int64_t v) {
-  const float nan = __int_as_float(0x7fc00000);
-  if (v < 0) return mkv(nan, nan, nan);
+__device__ __forceinline__ V3 corner_vertex(const float* __restrict__ verts, int64_t v) {
+  if (v < 0) return mk(quiet_nan(), quiet_nan(), quiet_nan());
   return load3(verts + v * 3);
 }
 
@@ -55,14 +40,14 @@ __global__ __launch_bounds__(256) void face_areas_normals_fwd_kernel(const float
                                                                      int64_t V, int64_t F, float* __restrict__ areas,
                                                                      float* __restrict__ normals) {
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += (int64_t)gridDim.x * 256) {
-    const v3 v0 = corner_vertex(verts, vertex_id(faces, f * 3 + 0, V));
-    const v3 v1 = corner_vertex(verts, vertex_id(faces, f * 3 + 1, V));
-    const v3 v2 = corner_vertex(verts, vertex_id(faces, f * 3 + 2, V));
-    const v3 c = cross(v1 - v0, v2 - v0);
-    float norm = sqrtf(c.x * c.x + c.y * c.y + c.z * c.z);
+    const V3 v0 = corner_vertex(verts, vertex_id(faces, f * 3 + 0, V));
+    const V3 v1 = corner_vertex(verts, vertex_id(faces, f * 3 + 1, V));
+    const V3 v2 = corner_vertex(verts, vertex_id(faces, f * 3 + 2, V));
+    const V3 c = cross(v1 - v0, v2 - v0);
+    float norm = norm3(c);
     areas[f] = norm / 2.0f;
     norm = norm < kNormEps ? kNormEps : norm;
-    store3(normals + f * 3, mkv(c.x / norm, c.y / norm, c.z / norm));
+    store3(normals + f * 3, c / norm);
   }
 }
 
@@ -75,29 +60,29 @@ __global__ __launch_bounds__(256) void face_areas_normals_bwd_kernel(const float
                                                                      const float* __restrict__ verts, const int64_t* __restrict__ faces,
                                                                      int64_t V, int64_t F, float* __restrict__ grad_face_verts) {
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += (int64_t)gridDim.x * 256) {
-    const v3 v0 = corner_vertex(verts, vertex_id(faces, f * 3 + 0, V));
-    const v3 v1 = corner_vertex(verts, vertex_id(faces, f * 3 + 1, V));
-    const v3 v2 = corner_vertex(verts, vertex_id(faces, f * 3 + 2, V));
-    const v3 a = v1 - v0, b = v2 - v0;
-    const v3 c = cross(a, b);
-    float norm = sqrtf(c.x * c.x + c.y * c.y + c.z * c.z);
+    const V3 v0 = corner_vertex(verts, vertex_id(faces, f * 3 + 0, V));
+    const V3 v1 = corner_vertex(verts, vertex_id(faces, f * 3 + 1, V));
+    const V3 v2 = corner_vertex(verts, vertex_id(faces, f * 3 + 2, V));
+    const V3 a = v1 - v0, b = v2 - v0;
+    const V3 c = cross(a, b);
+    float norm = norm3(c);
     norm = norm < kNormEps ? kNormEps : norm;
     const float inv = 1.0f / norm;
     const float inv2 = inv * inv;
     const float ga_half_inv = grad_areas[f] * (0.5f * inv);
-    const v3 gn = load3(grad_normals + f * 3);
+    const V3 gn = load3(grad_normals + f * 3);
     float* out = grad_face_verts + f * 9;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-      const v3 t1 = cross(unit(d), b), t2 = cross(a, unit(d));
-      const v3 t0 = mkv(-(t1.x + t2.x), -(t1.y + t2.y), -(t1.z + t2.z));
+      const V3 t1 = cross(unit(d), b), t2 = cross(a, unit(d));
+      const V3 t0 = -(t1 + t2);
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
-        const v3 t = p == 0 ? t0 : p == 1 ? t1 : t2;
+        const V3 t = p == 0 ? t0 : p == 1 ? t1 : t2;
         const float s = dot(t, c);
         const float k = s * inv2;
         const float cy = (p == 1 && d == 2) ? c.x : c.y;  // the reference's c_x in place of c_y
-        const v3 dn = mkv((t.x - c.x * k) * inv, (t.y - cy * k) * inv, (t.z - c.z * k) * inv);
+        const V3 dn = mk((t.x - c.x * k) * inv, (t.y - cy * k) * inv, (t.z - c.z * k) * inv);
         out[p * 3 + d] = ga_half_inv * s + dot(dn, gn);
       }
     }
@@ -109,52 +94,28 @@ __global__ __launch_bounds__(256) void face_areas_normals_bwd_kernel(const float
 __global__ __launch_bounds__(256) void vert_normals_face_raw_kernel(const float* __restrict__ verts, const int64_t* __restrict__ faces,
                                                                     int64_t V, int64_t F, float* __restrict__ face_raw) {
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += (int64_t)gridDim.x * 256) {
-    const v3 v0 = corner_vertex(verts, vertex_id(faces, f * 3 + 0, V));
-    const v3 v1 = corner_vertex(verts, vertex_id(faces, f * 3 + 1, V));
-    const v3 v2 = corner_vertex(verts, vertex_id(faces, f * 3 + 2, V));
+    const V3 v0 = corner_vertex(verts, vertex_id(faces, f * 3 + 0, V));
+    const V3 v1 = corner_vertex(verts, vertex_id(faces, f * 3 + 1, V));
+    const V3 v2 = corner_vertex(verts, vertex_id(faces, f * 3 + 2, V));
     store3(face_raw + f * 3, cross(v2 - v1, v0 - v1));
   }
 }
 
-// (b) / (d) one lane per vertex: +0.0f plus the rows of the vertex's corners in list order.  PER_FACE: the row of a corner is its
-// face's (forward: face_raw (F, 3)), else the corner's own (backward: face_rows (3 F, 3)).  NORMALIZE: also s / max(|s|, 1e-6).
-// The list is the caller's: offsets outside [0, 3 F] are clamped and corners outside [0, 3 F) skipped, so a list that breaks its
-// contract gives wrong sums, never a read outside the rows.  A vertex with no corner gets zeros.
-template <bool PER_FACE, bool NORMALIZE>
-__global__ __launch_bounds__(256) void vert_gather_sum_kernel(const float* __restrict__ rows, const int32_t* __restrict__ offsets,
-                                                              const int32_t* __restrict__ corners, int64_t V, int64_t n_corners_max,
-                                                              float* __restrict__ sums, float* __restrict__ normals) {
-  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < V; v += (int64_t)gridDim.x * 256) {
-    int64_t begin = offsets[v], end = offsets[v + 1];
-    begin = begin < 0 ? 0 : begin;
-    end = end > n_corners_max ? n_corners_max : end;
-    v3 s = mkv(0.f, 0.f, 0.f);
-    for (int64_t i = begin; i < end; ++i) {
-      const int64_t c = corners[i];
-      if (c < 0 || c >= n_corners_max) continue;
-      s = s + load3(rows + (PER_FACE ? c / 3 : c) * 3);
-    }
-    store3(sums + v * 3, s);
-    if (NORMALIZE) {
-      float norm = sqrtf(s.x * s.x + s.y * s.y + s.z * s.z);
-      norm = norm < kNormEps ? kNormEps : norm;
-      store3(normals + v * 3, mkv(s.x / norm, s.y / norm, s.z / norm));
-    }
-  }
-}
+// (b) / (d) one lane per vertex: vert_gather_sum_kernel (csr_gather.h) over the vertex's corners in list order.  Forward: PER_FACE
+// (the row of a corner is its face's, face_raw (F, 3)) and NORMALIZE; backward: the corner's own row (face_rows (3 F, 3)).
 
 // The gradient of n = s / max(|s|, 1e-6) at one vertex: g / 1e-6 where the clamp holds (what autograd gives for
 // x / clamp_min(norm, eps) there), (g - n (n . g)) / |s| where it does not.  The clamp is tested as the forward tests it
 // (norm < eps), so a NaN sum -- a vertex that shares a face with an id out of range -- takes the regular branch and stays NaN in
 // every gradient it reaches.  A corner whose vertex is out of range is in no list: it contributes nothing.
-__device__ __forceinline__ v3 normalize_grad(const float* __restrict__ sums, const float* __restrict__ grad_normals, int64_t v) {
-  if (v < 0) return mkv(0.f, 0.f, 0.f);
-  const v3 s = load3(sums + v * 3), g = load3(grad_normals + v * 3);
-  const float norm = sqrtf(s.x * s.x + s.y * s.y + s.z * s.z);
-  if (norm < kNormEps) return mkv(g.x / kNormEps, g.y / kNormEps, g.z / kNormEps);
-  const v3 n = mkv(s.x / norm, s.y / norm, s.z / norm);
+__device__ __forceinline__ V3 normalize_grad(const float* __restrict__ sums, const float* __restrict__ grad_normals, int64_t v) {
+  if (v < 0) return mk(0.f, 0.f, 0.f);
+  const V3 s = load3(sums + v * 3), g = load3(grad_normals + v * 3);
+  const float norm = norm3(s);
+  if (norm < kNormEps) return g / kNormEps;
+  const V3 n = s / norm;
   const float ng = dot(n, g);
-  return mkv((g.x - n.x * ng) / norm, (g.y - n.y * ng) / norm, (g.z - n.z * ng) / norm);
+  return (g - n * ng) / norm;
 }
 
 // (c) per face: G = the sum of its three vertices' sum-gradients in corner order (the face's contribution went to all three), then
@@ -164,13 +125,13 @@ __global__ __launch_bounds__(256) void vert_normals_face_rows_kernel(const float
                                                                      int64_t V, int64_t F, float* __restrict__ face_rows) {
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += (int64_t)gridDim.x * 256) {
     const int64_t i0 = vertex_id(faces, f * 3 + 0, V), i1 = vertex_id(faces, f * 3 + 1, V), i2 = vertex_id(faces, f * 3 + 2, V);
-    const v3 v0 = corner_vertex(verts, i0), v1 = corner_vertex(verts, i1), v2 = corner_vertex(verts, i2);
-    const v3 G = normalize_grad(sums, grad_normals, i0) + normalize_grad(sums, grad_normals, i1) + normalize_grad(sums, grad_normals, i2);
-    const v3 a = v2 - v1, b = v0 - v1;
-    const v3 g2 = cross(b, G), g0 = cross(G, a);
+    const V3 v0 = corner_vertex(verts, i0), v1 = corner_vertex(verts, i1), v2 = corner_vertex(verts, i2);
+    const V3 G = normalize_grad(sums, grad_normals, i0) + normalize_grad(sums, grad_normals, i1) + normalize_grad(sums, grad_normals, i2);
+    const V3 a = v2 - v1, b = v0 - v1;
+    const V3 g2 = cross(b, G), g0 = cross(G, a);
     float* out = face_rows + f * 9;
     store3(out + 0, g0);
-    store3(out + 3, mkv(-(g0.x + g2.x), -(g0.y + g2.y), -(g0.z + g2.z)));
+    store3(out + 3, -(g0 + g2));
     store3(out + 6, g2);
   }
 }
@@ -178,12 +139,6 @@ __global__ __launch_bounds__(256) void vert_normals_face_rows_kernel(const float
 // V == 0 with faces: every id is out of range, every face NaN -- a fill, no kernel
 int fill_nan(float* p, int64_t n, hipStream_t s) {
   return hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(p), 0x7fc00000, (size_t)n, s) == hipSuccess ? P3D_OK : P3D_ERR_LAUNCH;
-}
-
-unsigned stream_blocks(int64_t items) {
-  int64_t blocks = ceil_div(items, 256);
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  return (unsigned)blocks;
 }
 
 }  // namespace
@@ -237,7 +192,7 @@ P3D_API int p3d_verts_normals_forward(const float* verts, const int64_t* faces, 
   if (!face_raw) return P3D_ERR_WORKSPACE;
   LaunchScope ls("verts_normals_forward", s);
   vert_normals_face_raw_kernel<<<stream_blocks(F), 256, 0, s>>>(verts, faces, V, F, face_raw);
-  vert_gather_sum_kernel<true, true><<<stream_blocks(V), 256, 0, s>>>(face_raw, offsets, corners, V, F * 3, sums, normals);
+  vert_gather_sum_kernel<Normals, true, true><<<stream_blocks(V), 256, 0, s>>>(face_raw, offsets, corners, V, F * 3, sums, normals);
   return launch_status();
 }
 
@@ -253,6 +208,6 @@ P3D_API int p3d_verts_normals_backward(const float* grad_normals, const float* v
   if (!face_rows) return P3D_ERR_WORKSPACE;
   LaunchScope ls("verts_normals_backward", s);
   vert_normals_face_rows_kernel<<<stream_blocks(F), 256, 0, s>>>(grad_normals, verts, faces, sums, V, F, face_rows);
-  vert_gather_sum_kernel<false, false><<<stream_blocks(V), 256, 0, s>>>(face_rows, offsets, corners, V, F * 3, grad_verts, nullptr);
+  vert_gather_sum_kernel<Normals, false, false><<<stream_blocks(V), 256, 0, s>>>(face_rows, offsets, corners, V, F * 3, grad_verts, nullptr);
   return launch_status();
 }

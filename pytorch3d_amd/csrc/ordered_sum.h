@@ -73,7 +73,11 @@ __global__ __launch_bounds__(256) void pass1_kernel(Op op, const int64_t* __rest
   for (int i = 0; i < R; ++i) r[i] = 0.0f;
   if (key >= 0) op.row(s, key, chunk, r);
 
-  // the lane where this lane's segment starts inside the wave (lanes past the array are segments of their own)
+  // the lane where this lane's segment starts inside the wave (lanes past the array are segments of their own).  This scan is
+  // written out three times on purpose -- here, transform.hip (camera_grad) and knn.hip (knn_bwd_scatter_kernel): hoisted into one
+  // helper it compiled this kernel to more instructions for gfx950 (MeshOp 1353 -> 1391, PointMeshOp<0, 2> 1651 -> 1700,
+  // SplatOp<4> 977 -> 999: compare / select pairs in their _e64 forms, more waits), and these are the measured backwards of
+  // DESIGN section 8.8.
   const unsigned long long true_heads = __ballot(head);
   const unsigned long long starts = __ballot(head || !valid || lane == 0);
   const int start = 63 - __clzll((long long)(starts & ((2ull << lane) - 1ull)));

@@ -36,6 +36,14 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? P3D_OK : P
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// The grid of a grid-stride loop over `items` with 256 threads per block: at most 4096 blocks, so one pass covers
+// 4096 x 256 = 1 048 576 items and a loop beyond that goes round again.
+inline unsigned stream_blocks(int64_t items) {
+  int64_t blocks = ceil_div(items, 256);
+  if (blocks > 256 * 16) blocks = 256 * 16;
+  return (unsigned)blocks;
+}
+
 // Work items in scattered order: b -> (b * multiplier) mod items is a bijection for an odd multiplier coprime to items; near
 // items / golden ratio it spreads neighbours far apart
 inline unsigned scatter_multiplier(uint64_t items) {

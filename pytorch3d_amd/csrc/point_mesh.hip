@@ -13,12 +13,14 @@
 // Split: a workgroup is S in {1, 2, 4, 8} waves that share the same 64 queries; wave w takes the tiles w, w + S, ... into an LDS
 // region of its own and wave 0 merges the S (distance, index) pairs through LDS by the same order.  Bit-equal for every S.
 //
-// Fused loss: wave 0 also multiplies a query's distance by its element's weight and sums the wave with six butterfly rounds; a second
-// launch (one block per element) adds an element's wave partials in a fixed tree.  No float atomic in the forward.
+// Fused loss: wave 0 also multiplies a query's distance by its element's weight and sums the wave; a second launch (one block per
+// element) adds an element's wave partials: the fixed tree of fixed_sum.h with a wave of 64 queries at level 1.  No float atomic in
+// the forward.
 //
 // Backward: one lane per query, the hit (query, idxs[query]) from point_mesh_geom.h.  The query side is a plain store (or add) to the
 // query's own row.  The target side goes through LDS and leaves as float atomics with lane = hit * values + value, so the 3 / 6 / 9
 // values of one hit come from adjacent lanes (profiles/microbench/global_atomic_mi355x.txt); its ordered form is in ordered_bwd.hip.
+#include "fixed_sum.h"
 #include "point_mesh_geom.h"
 
 namespace p3d {
@@ -35,8 +37,6 @@ using namespace pm;
 constexpr int kTile = P3D_POINT_MESH_TILE;
 constexpr int kMaxSplit = 8;
 static_assert(kTile == kWave, "lane l builds the record of target l of a tile");
-
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
 
 // float4 per staged record
 __host__ __device__ constexpr int rec4(int kind) { return kind == kSeg ? 3 : 7; }
@@ -190,25 +190,18 @@ __global__ __launch_bounds__(64 * kMaxSplit) void pm_forward_kernel(const float*
   }
   if (partials) {  // uniform
     float term = live ? best_d * (weights ? weights[n] : 1.0f) : 0.0f;
+    // fixed_sum.h's wave_sum, written out: through the call the compiler lays out this kernel's tail differently (11 instructions
+    // fewer in all four instantiations), and the kernel is held to its recorded instruction count
 #pragma unroll
     for (int d = 1; d < kWave; d <<= 1) term += __shfl_xor(term, d);
     if (lane == 0) partials[blockIdx.x] = term;
   }
 }
 
-// One block per element: lane t adds the wave partials t, t + 256, ... ascending, then eight butterfly rounds.
-__global__ __launch_bounds__(256) void pm_element_sum_kernel(const float* __restrict__ partials, int64_t blocks_per_elem,
-                                                             float* __restrict__ sums) {
-  __shared__ float part[4];
-  const int64_t n = blockIdx.x;
-  float acc = 0.0f;
-  for (int64_t b = threadIdx.x; b < blocks_per_elem; b += 256) acc += partials[n * blocks_per_elem + b];
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) acc += __shfl_xor(acc, d);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) sums[n] = (part[0] + part[1]) + (part[2] + part[3]);
-}
+// the last step of segment_sum_kernel over an element's wave partials: nothing
+struct ElementSum {
+  __device__ __forceinline__ float operator()(int64_t, float s) const { return s; }
+};
 
 // One lane per query; a block of 256 = four waves, each with an LDS slab of its own for the target side.
 template <int QK, int TK>
@@ -326,7 +319,7 @@ P3D_API int p3d_point_mesh_forward(int query_kind, int target_kind, const float*
   }
   if (sums) {
     LaunchScope ls("point_mesh_element_sum", s);
-    pm_element_sum_kernel<<<(unsigned)N, 256, 0, s>>>(partials, bpe, sums);
+    segment_sum_kernel<<<(unsigned)N, 256, 0, s>>>(partials, bpe, ElementSum{}, sums);
     return launch_status();
   }
   return P3D_OK;

@@ -13,7 +13,7 @@
 
 #include <float.h>
 
-#include "p3d_common.h"
+#include "vec3.h"
 
 namespace p3d {
 namespace pm {
@@ -24,18 +24,6 @@ constexpr float kEps = 1e-8f;  // kEpsilon and vEpsilon of geometry_utils.h
 
 enum Kind { kPoint = 0, kSeg = 1, kTri = 2 };
 __host__ __device__ constexpr int kind_floats(int kind) { return kind == kPoint ? 3 : (kind == kSeg ? 6 : 9); }
-
-struct V3 {
-  float x, y, z;
-};
-P3D_PM_FN V3 mk(float x, float y, float z) { return V3{x, y, z}; }
-P3D_PM_FN V3 load3(const float* p) { return V3{p[0], p[1], p[2]}; }
-P3D_PM_FN V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-P3D_PM_FN V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-P3D_PM_FN V3 operator*(float s, V3 a) { return V3{s * a.x, s * a.y, s * a.z}; }
-P3D_PM_FN V3 operator/(V3 a, float s) { return V3{a.x / s, a.y / s, a.z / s}; }
-P3D_PM_FN float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-P3D_PM_FN V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 struct Seg {
   V3 v0, v1, d;  // d = v1 - v0

@@ -205,7 +205,8 @@ __global__ __launch_bounds__(256) void camera_grad_partial_kernel(const float* _
         r[16 + 3 * i + 2] = i < 3 ? view[i] * gn[3] : gn[3];
       }
     }
-    // the lane where this lane's segment starts inside the wave
+    // the lane where this lane's segment starts inside the wave (the scan of ordered_sum.h's pass1_kernel and knn.hip's
+    // knn_bwd_scatter_kernel, written out in each on purpose: a shared helper compiled pass1_kernel to more instructions, see there)
     const int below = __shfl_up(n, 1), above = __shfl_down(n, 1);
     const unsigned long long starts = __ballot(lane == 0 || below != n);
     const int start = 63 - __clzll((long long)(starts & ((2ull << lane) - 1ull)));

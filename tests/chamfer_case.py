@@ -269,7 +269,7 @@ EDGE_KS = (1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 31, 32)  # both ends and the inside 
 EDGE_BACKWARD = [("rungs", K) for K in (2, 5, 9, 16, 17, 32)] + [("short", K) for K in (8, 16)]
 EDGE_DN = ((3, 2), (2, 1))  # (D, norm) of the backward cases
 MAX_LEFT_OUT = 0.05  # of a case's live queries may fall outside the admission (point_mesh_case.MAX_DROPPED)
-STREAM_CAP = 256 * 16 * 256  # items one pass of a grid-stride loop covers (stream_blocks: 4 096 blocks of 256 threads)
+STREAM_CAP = 256 * 16 * 256  # items one pass of a grid-stride loop covers (csrc/p3d_common.h: stream_blocks, 4 096 blocks of 256 threads)
 BIG_P1 = STREAM_CAP + 300
 
 _EDGE = {}

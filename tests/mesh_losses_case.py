@@ -188,8 +188,8 @@ def gates(name, verts_list, faces_list, tables, grad_output=1.0, f32=None):
 
 
 # ---- larger generated meshes and the vectorised restatements they need (tests/test_*_loss_kernel_edges.py) --------------------------------
-SUM_CAP = 256 * 256          # terms the first round of sum_partials_kernel covers: one partial per 256 terms, 256 lanes
-STREAM_CAP = 256 * 16 * 256  # items one pass of a grid-stride loop covers (stream_blocks: 4 096 blocks of 256 threads)
+SUM_CAP = 256 * 256          # terms the first round of segment_sum_kernel (csrc/fixed_sum.h) covers: one partial per 256 terms, 256 lanes
+STREAM_CAP = 256 * 16 * 256  # items one pass of a grid-stride loop covers (csrc/p3d_common.h: stream_blocks, 4 096 blocks of 256 threads)
 
 
 def jittered_grid(n, gen, spacing=0.1, jitter=0.2):

@@ -301,7 +301,7 @@ def check_mesh_loss(z, name, tag, loss, grad_verts, grad_points, who=""):
 # ---- the second round of the element sums (tests/test_*_loss_kernel_edges.py) ---------------------------------------------------------------
 def sum_depth(n):
     """Additions a term passes through in a fused loss whose largest element has n queries: 6 butterfly rounds in the wave, lane t of
-    one block adding the wave partials t, t + 256, ..., 8 more rounds (include/p3d_amd.h: p3d_point_mesh_forward), then the
+    one block adding the wave partials t, t + 256, ..., 8 more rounds (csrc/fixed_sum.h: segment_sum_kernel), then the
     elements and the two directions added."""
     import math
 

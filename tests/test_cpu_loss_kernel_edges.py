@@ -336,3 +336,32 @@ def test_the_vectorised_normal_restatements_equal_the_loops_on_the_small_input()
     vv = v.double().clone().requires_grad_(True)
     (plain,) = torch.autograd.grad(list(MN.face_areas_normals_restated(vv, f)), vv, [ga, gn])
     assert float((plain - want)[~eps].abs().max()) > 1e-3 * float(want[~eps].abs().max())
+
+
+# ---- E. the restated tree (tests/fixed_sum_case.py) on the torch formulations' distances ----------------------------------------------------
+def test_the_restated_tree_is_a_sum_and_its_inputs_tell_it_from_a_chain():
+    """What section E of the GPU file relies on, shown without the kernels: the restatement is within depth x 2^-24 x sum |term| of
+    the float64 sum, it is not the left-to-right sum on the seeded inputs wherever TELLS_APART says so, and an empty segment is +0."""
+    import numpy as np
+
+    import fixed_sum_case as FS
+    from pytorch3d_amd import knn as knn_mod
+    from pytorch3d_amd import point_mesh as pm
+
+    cases = []
+    for name in FS.CHAMFER_LENGTHS:
+        p1, p2, l1 = FS.chamfer_clouds(name)
+        d = knn_mod.torch_knn_forward(p1, p2, l1, None, 2, 1)[1].reshape(2, -1).numpy()
+        cases += [("chamfer " + name, d[n], -(-p1.shape[1] // 64), FS.CHAMFER_TELLS_APART[name][n]) for n in range(2)]
+    for name in FS.POINT_EDGE_COUNTS:
+        points, pfirst, segms, sfirst, w, max_points = FS.point_edge_case(name)
+        d = pm.torch_forward("point_edge", points, pfirst, segms, sfirst)[0].numpy()
+        ends = pfirst.tolist() + [points.shape[0]]
+        cases += [("point_edge " + name, d[ends[n]:ends[n + 1]] * np.float32(w[n]), -(-max_points // 64), FS.POINT_EDGE_TELLS_APART[name][n])
+                  for n in range(2)]
+    for who, terms, per_segment, tells_apart in cases:
+        tree, chain, exact = FS.tree_sum(terms, per_segment), FS.chain_sum(terms), float(terms.astype(np.float64).sum())
+        depth = 6 + -(-per_segment // 256) + 8
+        assert abs(float(tree) - exact) <= depth * 2.0 ** -24 * float(np.abs(terms).astype(np.float64).sum()), who
+        assert bool((FS.bits(tree) != FS.bits(chain)).all()) == tells_apart, who
+    assert FS.bits(FS.tree_sum(np.zeros(0, np.float32), 3)) == 0

@@ -6,10 +6,12 @@ csrc/point_mesh.hip, csrc/mesh_losses.hip and csrc/normals.hip.
      padding and NaN in the p1 padding;
   B. runs of hits on one target in the scatter of the backward for D = 2 (32 hits per wave) and D = 3 (21);
   C. the second round of the three partial-sum kernels: more than 256 partials per cloud, element or batch;
-  D. the second pass of the grid-stride loops: more than 1 048 576 queries, hits, vertices, faces, edges and pairs.
+  D. the second pass of the grid-stride loops: more than 1 048 576 queries, hits, vertices, faces, edges and pairs;
+  E. the fixed tree of csrc/fixed_sum.h bit for bit: the chamfer and point-edge sums against a numpy float32 restatement of the
+     header's comment (tests/fixed_sum_case.py), on inputs whose left-to-right sum has other bits.
 
-Inputs come from seeded generators (tests/*_case.py); every yardstick is a float64 restatement from those files and every gate is
-the one of the neighbouring test files (test_gpu_chamfer.py, test_gpu_point_mesh.py, test_gpu_mesh_losses.py,
+Inputs come from seeded generators (tests/*_case.py); in A to D every yardstick is a float64 restatement from those files and
+every gate is the one of the neighbouring test files (test_gpu_chamfer.py, test_gpu_point_mesh.py, test_gpu_mesh_losses.py,
 test_gpu_mesh_normals.py), scaled by the error the package's float32 torch formulation makes on the CPU against the same truth.
 tests/test_cpu_loss_kernel_edges.py proves the machinery: the formulation passes every gate and five wrong answers are rejected.
 """
@@ -149,7 +151,7 @@ def test_chamfer_with_more_than_256_wave_partials_per_cloud(D, kw, ordered):
     import pytorch3d_amd as p3d
 
     N, P1, P2, lx, ly = C.SUM_SHAPE
-    assert C.tree_depth(P1) == 16 and -(-lx[1] // 64) == 257  # the second round of chamfer_cloud_sum_kernel, in both clouds
+    assert C.tree_depth(P1) == 16 and -(-lx[1] // 64) == 257  # the second round of segment_sum_kernel (csrc/fixed_sum.h), in both clouds
     t = C.sum_truth(D, kw)
     x, y, ckw = C.sum_inputs(D, kw, device=_dev())
     with _flag(ordered):
@@ -230,7 +232,7 @@ def test_point_mesh_losses_with_more_than_256_wave_partials_in_an_element(tag, o
     import pytorch3d_amd as p3d
 
     t = PM.second_round_truth(tag)
-    assert PM.sum_depth(t["n"]) == 18 and PM.sum_depth(256 * 64) == 17  # pm_element_sum_kernel takes a second round
+    assert PM.sum_depth(t["n"]) == 18 and PM.sum_depth(256 * 64) == 17  # segment_sum_kernel (csrc/fixed_sum.h) takes a second round
     verts, faces, points, _ = PM.second_round_batch()
     with _flag(ordered):
         v, p = [x.to(_dev()).requires_grad_(True) for x in verts], [x.to(_dev()).requires_grad_(True) for x in points]
@@ -410,3 +412,53 @@ def test_face_areas_normals_loops_go_round_twice(large_mesh):
         assert err_a <= 4 * e_a
         assert err_n <= 4 * e_n
         assert err_g <= 4 * e_g
+
+
+# ---- E. the fixed tree, bit for bit (csrc/fixed_sum.h restated by tests/fixed_sum_case.py) -----------------------------------------------------
+def _assert_tree_bits(who, got, terms_per_segment, per_segment, tells_apart):
+    """got[n] has the bits of the restated tree over terms_per_segment[n]; where the inputs tell the orders apart, not those of the
+    left-to-right sum."""
+    import numpy as np
+
+    import fixed_sum_case as FS
+
+    for n, terms in enumerate(terms_per_segment):
+        want, chain = FS.tree_sum(terms, per_segment), FS.chain_sum(terms)
+        print("%s segment %d: %d terms, %d partials, kernel %r tree %r left-to-right %r" % (who, n, len(terms), per_segment, float(got[n]), float(want), float(chain)))
+        assert np.array_equal(FS.bits(got[n]), FS.bits(want)), (who, n)
+        if tells_apart[n]:
+            assert not np.array_equal(FS.bits(chain), FS.bits(want)), (who, n, "the inputs do not tell the tree from a chain")
+
+
+@pytest.mark.parametrize("name", ["small", "second_step"])
+def test_chamfer_cloud_sums_have_the_bits_of_the_documented_tree(name):
+    import fixed_sum_case as FS
+    from pytorch3d_amd import _lib, chamfer
+
+    p1, p2, lengths1 = FS.chamfer_clouds(name)
+    a, b = p1.to(_dev()), p2.to(_dev())
+    with torch.cuda.device(_dev()):
+        _, dists, sums = chamfer._direction_forward(_lib.load(), a, b, lengths1.to(_dev()), None, None, 2, False)
+    dists, sums = dists.cpu().numpy(), sums.cpu().numpy()
+    per_segment = -(-p1.shape[1] // 64)
+    assert per_segment == {"small": 3, "second_step": 258}[name] and -(-int(lengths1.min()) // 64) == {"small": 1, "second_step": 257}[name]
+    assert not dists[1, int(lengths1[1]):].any()  # a row past its cloud's length is +0: the terms are the whole padded row
+    _assert_tree_bits("chamfer " + name, sums, [dists[n] for n in range(2)], per_segment, FS.CHAMFER_TELLS_APART[name])
+
+
+@pytest.mark.parametrize("name", ["second_step", "empty_element"])
+def test_point_edge_element_sums_have_the_bits_of_the_documented_tree(name):
+    import numpy as np
+
+    import fixed_sum_case as FS
+    from pytorch3d_amd import _C
+
+    points, pfirst, segms, sfirst, w, max_points = FS.point_edge_case(name)
+    dists, _, sums = _C.point_mesh_forward("point_edge", points.to(_dev()), pfirst.to(_dev()), segms.to(_dev()), sfirst.to(_dev()),
+                                           max_points, weights=w.to(_dev()), with_sums=True)
+    dists, sums = dists.cpu().numpy(), sums.cpu().numpy()
+    ends = pfirst.tolist() + [points.shape[0]]
+    terms = [dists[ends[n]:ends[n + 1]] * np.float32(w[n]) for n in range(2)]  # one float32 multiplication
+    per_segment = -(-max_points // 64)
+    assert per_segment == {"second_step": 257, "empty_element": 3}[name]
+    _assert_tree_bits("point_edge " + name, sums, terms, per_segment, FS.POINT_EDGE_TELLS_APART[name])
