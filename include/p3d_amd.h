@@ -801,6 +801,45 @@ int p3d_point_mesh_backward(int query_kind, int target_kind, const float* querie
                             unsigned flags, const int64_t* sorted_hits, float* grad_queries, float* grad_targets, void* workspace,
                             size_t workspace_bytes, p3d_stream_t stream);
 
+/* ---- sample_points_from_meshes (pytorch3d/ops/sample_points_from_meshes.py; csrc/sample_points.hip) ------------------------
+ *
+ * Points on the surface of every mesh of a packed batch, a face drawn with probability proportional to its area and the point
+ * uniform on the face.  The randomness is an input: uniforms (N,S,3) f32 in [0, 1); the outputs are a pure function of it.
+ * verts (V,3) f32, faces (F,3) i64 packed vertex ids (a negative id wraps once, an id still out of range gives NaN coordinates),
+ * mesh_to_faces_first_idx / num_faces_per_mesh (N) i64: mesh n owns the faces [first[n], first[n] + num[n]), clamped into [0, F);
+ * first is ascending, as a packed batch has it.
+ * Forward.  (1) cdf (F) f32 in the workspace: per mesh the inclusive prefix sum of the areas |(v1 - v0) x (v2 - v0)| / 2 (the
+ * arithmetic of p3d_face_areas_normals_forward), restarting at every entry of mesh_to_faces_first_idx: a two-level segmented
+ * tree sum whose shape the face counts alone decide, followed by the running maximum over the faces of non-zero area -- exact in any
+ * order -- so that the table is non-decreasing inside a mesh and a face of zero area repeats its predecessor's value (0 at a mesh's
+ * start).  No float atomic, no host round trip; an entry is within D(F) 2^-24 total of the exact prefix sum of the float32 areas,
+ * D(F) = 19 + 4 ceil(ceil(F / 256) / 256).  (2) one lane per sample (n, s): t = u0 * total_n with total_n the mesh's last entry, the
+ * face is the first f of the mesh with cdf[f] > t, t clamped into [0, total_n) -- a product that rounds up to the total takes the
+ * last face of non-zero area; a face of zero area is never taken.  r = sqrt(u1), w0 = 1 - r, w1 = r (1 - u2), w2 = r u2,
+ * sample = (w0 v0 + w1 v1) + w2 v2, normal = c / max(|c|, DBL_EPSILON) with c = (v1 - v0) x (v2 - v1): float32, one operation
+ * each, NOT fused, IEEE sqrt and division.
+ * samples (N,S,3) f32, normals (N,S,3) f32 or NULL, face_idxs (N,S) i64 packed face indices, bary (N,S,3) f32 (w0, w1, w2): every
+ * entry is written, no memset in front.  An empty mesh, or one whose total area is zero or not finite: zero rows, face_idxs -1.
+ * workspace: p3d_sample_points_forward_workspace_bytes(F) bytes; its first F floats are the table. */
+size_t p3d_sample_points_forward_workspace_bytes(int64_t F);
+int p3d_sample_points_forward(const float* verts, const int64_t* faces, const int64_t* mesh_to_faces_first_idx,
+                              const int64_t* num_faces_per_mesh, const float* uniforms, int64_t V, int64_t F, int64_t N, int64_t S,
+                              float* samples, float* normals, int64_t* face_idxs, float* bary, void* workspace,
+                              size_t workspace_bytes, p3d_stream_t stream);
+/* Backward, with the face choice and the weights held fixed: grad_face_verts (F,3,3) f32, every entry written, to be summed per
+ * vertex by p3d_scatter_face_grads or p3d_scatter_face_grads_ordered.  Sample i with f = face_idxs[i] in [0, F) (anything else
+ * contributes nothing) adds bary[i,k] * grad_samples[i] to corner k of face f and, grad_normals != NULL, grad_normals[i] to the
+ * face's normal sum G; one lane per face then adds G through the Jacobian of c / max(|c|, DBL_EPSILON) -- (G - n (n . G)) / |c|, or
+ * G / DBL_EPSILON where the clamp holds -- and of c = (v1 - v0) x (v2 - v1), once per face.  grad_samples (num_samples,3),
+ * grad_normals (num_samples,3) or NULL.  The per-face sums: float atomics after a merge in LDS; or, with sorted_samples != NULL (the
+ * num_sorted samples that hold a face, sorted stably by face), the ordered segmented sum of the deterministic backwards: the same
+ * bits on every run.  workspace: p3d_sample_points_backward_workspace_bytes(F, grad_normals != NULL, num_sorted or 0) bytes. */
+size_t p3d_sample_points_backward_workspace_bytes(int64_t F, int with_normals, int64_t num_sorted);
+int p3d_sample_points_backward(const float* grad_samples, const float* grad_normals, const float* verts, const int64_t* faces,
+                               const int64_t* face_idxs, const float* bary, const int64_t* sorted_samples, int64_t num_sorted,
+                               int64_t V, int64_t F, int64_t num_samples, float* grad_face_verts, void* workspace,
+                               size_t workspace_bytes, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

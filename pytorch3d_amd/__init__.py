@@ -14,6 +14,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     knn_points, knn_gather, chamfer_distance  nearest neighbours between point clouds and the chamfer loss on top, fused
     point_mesh_face_distance, point_mesh_edge_distance, point_face_distance, face_point_distance, point_edge_distance,
     edge_point_distance              distances between a point cloud and the faces / edges of a mesh, fused
+    sample_points_from_meshes, sample_points_packed  points drawn from the surface of a mesh batch, a function of given uniforms, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -33,6 +34,7 @@ from .point_mesh import (edge_point_distance, face_point_distance, point_edge_di
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401
+from .sample_points import sample_points_from_meshes, sample_points_packed  # noqa: F401
 from .shading import (flat_shading, gouraud_shading, phong_shading, phong_shading_vertex_colors,  # noqa: F401
                       soft_phong_shading)
 from .splatter import SplatterBlender, phong_shading_with_pixels, splatter_blend  # noqa: F401

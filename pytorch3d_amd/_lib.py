@@ -198,6 +198,13 @@ _SIGNATURES = {
     "p3d_point_mesh_backward_workspace_bytes": (c_size, [c_int, c_i64]),
     "p3d_point_mesh_backward": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_f64, c_uint,
                                         c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    # sample_points_from_meshes (csrc/sample_points.hip; the ordered per-face sum: csrc/ordered_bwd.hip)
+    "p3d_sample_points_forward_workspace_bytes": (c_size, [c_i64]),
+    "p3d_sample_points_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                          c_size, c_ptr]),
+    "p3d_sample_points_backward_workspace_bytes": (c_size, [c_i64, c_int, c_i64]),
+    "p3d_sample_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_size,
+                                           c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

@@ -102,6 +102,31 @@ struct PointMeshOp {
   }
 };
 
+// ---- sample_points_from_meshes: sample s adds w_k grad_sample to corner k of its face and grad_normal to the face's normal sum ------
+struct SampleOp {
+  static constexpr int R = 12;
+  int64_t nsamples, nkeys;  // N S samples, F faces
+  const int64_t* face_idxs;
+  const float *bary, *gs, *gn;  // gn NULL: the row's last three stay 0 and are not stored
+  int nv;                       // floats of a stored row: 9 or 12
+  float* out;                   // (F, nv)
+  __device__ int64_t key(int64_t s) const { return face_idxs[s]; }
+  __device__ void row(int64_t s, int, int, float (&r)[R]) const {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float w = bary[s * 3 + k];
+      r[3 * k] = w * gs[s * 3], r[3 * k + 1] = w * gs[s * 3 + 1], r[3 * k + 2] = w * gs[s * 3 + 2];
+    }
+    if (gn) r[9] = gn[s * 3], r[10] = gn[s * 3 + 1], r[11] = gn[s * 3 + 2];
+  }
+  __device__ void store(int f, int, const float (&r)[R]) const {
+    float* o = out + (int64_t)f * nv;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+      if (i < nv) o[i] = r[i];
+  }
+};
+
 // ---- points: (2 gd dx, 2 gd dy, gz) per entry (rasterize_points.cu:389-405) ---------------------------------------------------
 struct PointOp {
   static constexpr int R = 3;
@@ -394,6 +419,21 @@ int point_mesh_ordered_scatter(const pm::Hits& h, const int64_t* sorted, int acc
   }
   return h.query_kind == pm::kTri ? point_mesh_ordered_run<pm::kTri, pm::kPoint>(h, sorted, accumulate, grad_targets, workspace, s)
                                   : point_mesh_ordered_run<pm::kSeg, pm::kPoint>(h, sorted, accumulate, grad_targets, workspace, s);
+}
+
+// ---- sample_points_from_meshes (sample_points.hip calls these) --------------------------------------------------------------------------
+size_t sample_points_ordered_bytes(int64_t num_sorted) { return partial_bytes(num_sorted, SampleOp::R, 1); }
+
+// rows (F, nv) <- per face the sum of its samples' rows, `sorted` being the samples that hold a face sorted stably by face
+int sample_points_ordered_rows(const int64_t* face_idxs, const float* bary, const float* grad_samples, const float* grad_normals,
+                               const int64_t* sorted, int64_t num_sorted, int64_t num_samples, int64_t F, int nv, float* rows,
+                               void* workspace, hipStream_t s) {
+  const int st = ordered::fill_zero(rows, F * nv, s);
+  if (st != P3D_OK) return st;
+  SampleOp op;
+  op.nsamples = num_samples, op.nkeys = F;
+  op.face_idxs = face_idxs, op.bary = bary, op.gs = grad_samples, op.gn = grad_normals, op.nv = nv, op.out = rows;
+  return ordered::run(op, sorted, num_sorted, 1, workspace, s, "sample_points_face_sums_ordered");
 }
 
 }  // namespace p3d

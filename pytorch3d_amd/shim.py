@@ -55,6 +55,10 @@ reference classes runs on them end to end:
                                                                  edge gather, two fused brute-force forwards with fixed-tree sums,
                                                                  two backward kernels, the vertex scatter) and no host sync; other
                                                                  inputs go to this package's torch formulation
+    ops.sample_points_from_meshes.sample_points_from_meshes   -> csrc/sample_points.hip: one autograd node, a deterministic function of
+                                                                 ONE torch.rand((N, S, 3)) (torch's multinomial stream is not
+                                                                 reproduced: same distribution, other draws); other inputs go to
+                                                                 this package's torch formulation
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -349,6 +353,7 @@ def patch_reference_python():
     _patch_mesh_losses(wrap)
     _patch_point_losses()
     _patch_point_mesh_losses()
+    _patch_sample_points()
 
 
 def _patch_point_mesh_losses():
@@ -377,6 +382,33 @@ def _patch_point_mesh_losses():
         new.__wrapped__ = orig
         new.__p3d_amd__ = True
         _replace_everywhere(orig, new)
+
+
+def _patch_sample_points():
+    """pytorch3d.ops.sample_points_from_meshes.sample_points_from_meshes -> pytorch3d_amd.sample_points, in every module that copied
+    the name (in the reference that is pytorch3d.ops alone: pytorch3d.loss never imports it).  float32 GPU meshes are one autograd node over csrc/sample_points.hip;
+    everything else takes OUR torch formulation of the same contract.  PATCH_CALLS counts the kernel calls as fused and the
+    formulation as fallbacks.  The face choice follows this package's uniforms, not torch's multinomial stream."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".sample_points")
+    try:  # every module that copied the name must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.ops.sample_points_from_meshes")
+        importlib.import_module("pytorch3d.ops")
+        importlib.import_module("pytorch3d.loss")
+    except ImportError:  # a reference checkout without these packages: nothing to patch
+        return
+
+    def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, return_textures=False, **kwargs):
+        out = ours.sample_points_from_meshes(meshes, num_samples, return_normals, return_textures, **kwargs)
+        _count("sample_points_from_meshes", ours.kernel_path(meshes.verts_packed()))  # (a call that raised is not counted)
+        return out
+
+    orig = ref.sample_points_from_meshes
+    sample_points_from_meshes.__doc__ = getattr(orig, "__doc__", None)
+    sample_points_from_meshes.__wrapped__ = orig
+    sample_points_from_meshes.__p3d_amd__ = True
+    _replace_everywhere(orig, sample_points_from_meshes)
 
 
 def _patch_point_losses():
