@@ -840,6 +840,36 @@ int p3d_sample_points_backward(const float* grad_samples, const float* grad_norm
                                int64_t V, int64_t F, int64_t num_samples, float* grad_face_verts, void* workspace,
                                size_t workspace_bytes, p3d_stream_t stream);
 
+/* ---- farthest point sampling and ball query (pytorch3d/ops/sample_farthest_points.py, ball_query.py; csrc/fps_ball.hip) ------
+ *
+ * Clouds as for the nearest neighbours: (N,P,D) contiguous f32, lengths (N) i64 or NULL (full), clamped into [0, P]; D in {2, 3},
+ * otherwise P3D_ERR_UNSUPPORTED (the caller owns a formulation for the rest).  A squared distance is, per coordinate in order, the
+ * difference and its square, accumulated: one float32 operation each, NOT fused.
+ *
+ * Farthest point sampling (sample_farthest_points_cpu.cpp).  K (N) i64 or NULL (max_K for every cloud), clamped into [0, max_K];
+ * start_idxs (N) i64 or NULL (0), clamped into [0, length).  Row n of idx (N,max_K) i64 holds count = min(K[n], lengths[n])
+ * indices and -1 behind them; every entry is written, no memset in front.  idx[n,0] = start_idxs[n]; every further entry is the
+ * point with the LARGEST minimum squared distance to the entries before it, the minimum kept as d < m ? d : m from +inf; equal
+ * minima go to the LOWEST index, so a cloud of coinciding points repeats index 0 (std::max_element).  A row with count 0 is all
+ * -1 (the reference writes index 0 there).  Coordinates that are not finite are outside the contract; the entries stay inside
+ * [0, length) all the same.
+ * One workgroup per cloud, nothing between workgroups (a small N uses few CUs).  P <= P3D_FPS_REGISTER_POINTS: the cloud lives in
+ * the workgroup's registers and needs no workspace; above: p3d_sample_farthest_points_workspace_bytes(N, P) bytes for the minimum
+ * distances (N,P), every byte read was written by the same call.  N, P or max_K of 0: P3D_OK without a launch. */
+#define P3D_FPS_REGISTER_POINTS 16384
+size_t p3d_sample_farthest_points_workspace_bytes(int64_t N, int64_t P);
+int p3d_sample_farthest_points(const float* points, const int64_t* lengths, const int64_t* K, const int64_t* start_idxs, int64_t N,
+                               int64_t P, int D, int64_t max_K, int64_t* idx, void* workspace, size_t workspace_bytes,
+                               p3d_stream_t stream);
+/* Ball query (ball_query_cpu.cpp).  For n and i < lengths1[n]: the pairs j < lengths2[n] in ASCENDING j with
+ * dist2(p1[n,i], p2[n,j]) < radius2 -- strictly; radius2 = radius * radius in float32 --, the first K of them: idx (N,P1,K) i64
+ * <- j, dists (N,P1,K) f32 <- dist2, in the order found (not sorted by distance).  The slots behind a row's hits and the rows
+ * i >= lengths1[n] hold -1 / 0; every entry is written, no memset in front.  A NaN distance is no hit.  Any K >= 1.  The backward is
+ * p3d_knn_points_backward with norm 2: it skips negative indices.  One lane per query, p2 staged in LDS tiles of P3D_KNN_TILE
+ * points; a wave leaves the scan once all its rows are full.  N or P1 of 0: P3D_OK without a launch. */
+int p3d_ball_query(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
+                   int64_t P2, int D, int K, float radius, int64_t* idx, float* dists, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

@@ -1076,6 +1076,77 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _nee
 
 
 # ----------------------------------------------------------------------------------------------
+# farthest point sampling and ball query (csrc/fps_ball.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
+# POINT_CLOUD_EXPORTS to the wrappers of pytorch3d_amd.sample_farthest_points / pytorch3d_amd.ball_query, which come here for float32
+# GPU tensors with D in (2, 3) and own a torch formulation for everything else.
+def _int64_arg(t, N, dev, name, who):
+    if t is None:
+        return None
+    _need_gpu(t, name)
+    if t.device != dev:
+        raise RuntimeError(f"Expected all tensors to be on the same GPU, but {name} is on {t.device} and points is on {dev}")
+    if t.shape != (N,):
+        raise RuntimeError(f"{who}: {name} must have shape (N,)")
+    return _c(t, torch.int64)
+
+
+def sample_farthest_points(points, lengths, K, start_idxs, max_K_known=-1):
+    """FarthestPointSampling (sample_farthest_points.h): idx (N, max_K) int64, row n holding min(K[n], lengths[n]) indices from
+    start_idxs[n] on and -1 behind them (include/p3d_amd.h).  max_K_known < 0: max(K) is read from the device, once.  lengths, K
+    and start_idxs may be None (full clouds, max_K_known samples each, start at 0) -- not part of the reference's signature."""
+    who = "sample_farthest_points"
+    _need_gpu(points, "points")
+    if points.dim() != 3 or points.shape[2] not in (2, 3):
+        raise RuntimeError(f"{who}: the kernels take points (N, P, D) with D in (2, 3); pytorch3d_amd.sample_farthest_points has a "
+                           "torch formulation for the rest")
+    dev = points.device
+    N, P, D = points.shape
+    lengths, K, start_idxs = (_int64_arg(t, N, dev, name, who) for t, name in ((lengths, "lengths"), (K, "K"), (start_idxs, "start_idxs")))
+    max_K = int(max_K_known)
+    if max_K < 0:
+        if K is None:
+            raise RuntimeError(f"{who}: K is None and max_K_known is not given")
+        max_K = int(K.max()) if N > 0 else 0
+    max_K = max(max_K, 0)
+    points = _c(points, torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        if N == 0 or P == 0 or max_K == 0:
+            return torch.full((N, max_K), -1, dtype=torch.int64, device=dev)
+        idx = torch.empty((N, max_K), dtype=torch.int64, device=dev)
+        nbytes = lib.p3d_sample_farthest_points_workspace_bytes(N, P)
+        ws = _workspace(nbytes, dev) if nbytes else None
+        rc = lib.p3d_sample_farthest_points(_ptr(points), _ptr(lengths), _ptr(K), _ptr(start_idxs), N, P, D, max_K, _ptr(idx), _ptr(ws),
+                                            nbytes, _stream(dev))
+        _lib.check(rc, who)
+    return idx
+
+
+def ball_query(p1, p2, lengths1, lengths2, K, radius, skip_points_outside_cube=False):
+    """BallQuery (ball_query.h): (idx (N, P1, K) int64, dists (N, P1, K)): per query the first K points of its cloud, ascending in
+    index, with a squared distance < radius^2 (float32); -1 / 0 behind them and in the rows past lengths1.  lengths1 / lengths2 may
+    be None (every cloud full).  skip_points_outside_cube is accepted and ignored: it cannot change a result."""
+    who = "ball_query"
+    dev = _same_device(("p1", p1), ("p2", p2))
+    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != p2.shape[0] or p1.shape[2] != p2.shape[2]:
+        raise RuntimeError(f"{who}: p1 (N, P1, D) and p2 (N, P2, D) must share N and D")
+    K = int(K)
+    if p1.shape[2] not in (2, 3) or K < 1:
+        raise RuntimeError(f"{who}: the kernel takes D in (2, 3) and K >= 1; pytorch3d_amd.ball_query has a torch formulation for the rest")
+    N, P1, D = p1.shape
+    lengths1, lengths2 = _int64_arg(lengths1, N, dev, "lengths1", who), _int64_arg(lengths2, N, dev, "lengths2", who)
+    p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+        rc = lib.p3d_ball_query(_ptr(p1), _ptr(p2), _ptr(lengths1), _ptr(lengths2), N, P1, p2.shape[1], D, K, float(radius), _ptr(idx),
+                                _ptr(dists), _stream(dev))
+        _lib.check(rc, who)
+    return idx, dists
+
+
+# ----------------------------------------------------------------------------------------------
 # point-mesh distances (csrc/point_mesh.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the eight names to
 # pytorch3d_amd.point_mesh, which comes here for float32 GPU tensors and owns a torch formulation for everything else.
 _PM_KINDS = {"point_face": (_lib.POINT_MESH_POINT, _lib.POINT_MESH_TRIANGLE), "face_point": (_lib.POINT_MESH_TRIANGLE, _lib.POINT_MESH_POINT),
@@ -1216,6 +1287,8 @@ def edge_point_dist_backward(points, segms, idxs, grad_dists):
 
 POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
+# bound by shim.make_module to the wrappers of pytorch3d_amd.sample_farthest_points / pytorch3d_amd.ball_query (<name>_op)
+POINT_CLOUD_EXPORTS = ("sample_farthest_points", "ball_query")
 
 
 HOT_PATH_EXPORTS = (

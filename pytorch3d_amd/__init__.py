@@ -15,11 +15,13 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     point_mesh_face_distance, point_mesh_edge_distance, point_face_distance, face_point_distance, point_edge_distance,
     edge_point_distance              distances between a point cloud and the faces / edges of a mesh, fused
     sample_points_from_meshes, sample_points_packed  points drawn from the surface of a mesh batch, a function of given uniforms, fused
+    sample_farthest_points, ball_query, masked_gather  farthest point sampling (a cloud in one workgroup's registers) and ball query, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
 """
 from . import _C  # noqa: F401
+from .ball_query import ball_query  # noqa: F401
 from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_alpha_blend, soft_depth_blend,  # noqa: F401
                        softmax_rgb_blend)
 from .chamfer import chamfer_distance  # noqa: F401
@@ -34,6 +36,7 @@ from .point_mesh import (edge_point_distance, face_point_distance, point_edge_di
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401
+from .sample_farthest_points import masked_gather, sample_farthest_points  # noqa: F401
 from .sample_points import sample_points_from_meshes, sample_points_packed  # noqa: F401
 from .shading import (flat_shading, gouraud_shading, phong_shading, phong_shading_vertex_colors,  # noqa: F401
                       soft_phong_shading)

@@ -29,6 +29,7 @@ BWD_MAKE_FACE_PRE = 2
 KNN_MAX_K = 32           # P3D_KNN_MAX_K
 KNN_TILE = 512           # P3D_KNN_TILE: p2 points staged per step
 KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
+FPS_REGISTER_POINTS = 16384  # P3D_FPS_REGISTER_POINTS: the largest cloud the register form of farthest point sampling holds
 POINT_MESH_POINT, POINT_MESH_SEGMENT, POINT_MESH_TRIANGLE = 0, 1, 2  # P3D_POINT_MESH_*: the kind of a query / target object
 POINT_MESH_TILE = 64                # P3D_POINT_MESH_TILE: target records staged per wave and step
 POINT_MESH_ACCUMULATE_QUERIES = 1   # P3D_POINT_MESH_ACCUMULATE_QUERIES
@@ -205,6 +206,10 @@ _SIGNATURES = {
     "p3d_sample_points_backward_workspace_bytes": (c_size, [c_i64, c_int, c_i64]),
     "p3d_sample_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_size,
                                            c_ptr]),
+    # farthest point sampling and ball query (csrc/fps_ball.hip)
+    "p3d_sample_farthest_points_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "p3d_sample_farthest_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_ball_query": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

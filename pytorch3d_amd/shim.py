@@ -11,7 +11,9 @@ interpolate_face_attributes, ...) runs on the MI355X kernels.
 so the module must be in sys.modules before they are imported.  Operators outside the hot path
 (knn, the point_mesh *_array_dist_* operators, pulsar, ...) raise NotImplementedError when called.  The eight point_mesh operators
 under `pytorch3d.loss.point_mesh_face_distance` / `point_mesh_edge_distance` ARE served (csrc/point_mesh.hip), so the unmodified
-reference losses run under plain `shim.install()`.
+reference losses run under plain `shim.install()`.  So are `_C.sample_farthest_points` and `_C.ball_query` (csrc/fps_ball.hip): the
+unmodified `pytorch3d.ops.sample_farthest_points` runs, and so does the forward of `pytorch3d.ops.ball_query`; its backward ends in
+`_C.knn_points_backward`, which stays a stub -- patch_python replaces the whole function.
 
     shim.install(patch_python=True)
 
@@ -59,6 +61,10 @@ reference classes runs on them end to end:
                                                                  ONE torch.rand((N, S, 3)) (torch's multinomial stream is not
                                                                  reproduced: same distribution, other draws); other inputs go to
                                                                  this package's torch formulation
+    ops.sample_farthest_points.sample_farthest_points / ops.ball_query.ball_query -> csrc/fps_ball.hip: farthest point sampling with
+                                                                 one workgroup per cloud and the cloud in registers; ball query as
+                                                                 one autograd node whose backward is the nearest neighbours'; other
+                                                                 inputs go to this package's torch formulation
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -105,6 +111,13 @@ def make_module(flavour="ctypes"):
 
     for name in _ours.POINT_MESH_EXPORTS:
         setattr(mod, name, getattr(point_mesh, name))
+    # farthest point sampling and ball query (pytorch3d_amd/sample_farthest_points.py, ball_query.py): csrc/fps_ball.hip for float32
+    # GPU clouds with D in (2, 3), a torch formulation of the same contract for everything else.  Both flavours serve these wrappers.
+    # (importlib: the package re-exports the FUNCTIONS of these names over the sub-modules)
+    import importlib
+
+    for name in _ours.POINT_CLOUD_EXPORTS:
+        setattr(mod, name, getattr(importlib.import_module(__package__ + "." + name), name + "_op"))
     if flavour == "pybind":
         # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
         def compiled(name):
@@ -354,6 +367,41 @@ def patch_reference_python():
     _patch_point_losses()
     _patch_point_mesh_losses()
     _patch_sample_points()
+    _patch_fps_ball()
+
+
+def _patch_fps_ball():
+    """pytorch3d.ops.sample_farthest_points.sample_farthest_points and pytorch3d.ops.ball_query.ball_query -> this package's
+    functions, in every module that copied the names (pytorch3d.ops).  float32 GPU clouds with D in {2, 3} take csrc/fps_ball.hip --
+    the ball query as one autograd node whose backward is the nearest neighbours' kernels, which the reference's own node cannot
+    reach (`_C.knn_points_backward` stays a stub) --, everything else OUR torch formulation.  PATCH_CALLS counts the kernel calls
+    as fused and the formulation as fallbacks."""
+    import importlib
+
+    ours_fps = importlib.import_module(__package__ + ".sample_farthest_points")
+    ours_ball = importlib.import_module(__package__ + ".ball_query")
+    try:  # every module that copied the names must be loaded before rebinding
+        ref_fps = importlib.import_module("pytorch3d.ops.sample_farthest_points")
+        ref_ball = importlib.import_module("pytorch3d.ops.ball_query")
+        importlib.import_module("pytorch3d.ops")
+    except ImportError:  # a reference checkout without these modules: nothing to patch
+        return
+
+    def sample_farthest_points(points, lengths=None, K=50, random_start_point=False, **kwargs):
+        out = ours_fps.sample_farthest_points(points, lengths, K, random_start_point, **kwargs)
+        _count("sample_farthest_points", ours_fps.kernel_path(points))  # (a call that raised is not counted)
+        return out
+
+    def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2, return_nn=True, skip_points_outside_cube=False):
+        out = ours_ball.ball_query(p1, p2, lengths1, lengths2, K, radius, return_nn, skip_points_outside_cube)
+        _count("ball_query", ours_ball.kernel_path(p1, p2, int(K)))
+        return out
+
+    for orig, new in ((ref_fps.sample_farthest_points, sample_farthest_points), (ref_ball.ball_query, ball_query)):
+        new.__doc__ = getattr(orig, "__doc__", None)
+        new.__wrapped__ = orig
+        new.__p3d_amd__ = True
+        _replace_everywhere(orig, new)
 
 
 def _patch_point_mesh_losses():
