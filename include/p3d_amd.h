@@ -870,6 +870,53 @@ int p3d_sample_farthest_points(const float* points, const int64_t* lengths, cons
 int p3d_ball_query(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
                    int64_t P2, int D, int K, float radius, int64_t* idx, float* dists, p3d_stream_t stream);
 
+/* ---- point clouds into voxel grids (pytorch3d/ops/points_to_volumes.py; csrc/points_to_volumes.hip) ----------------------------
+ *
+ * The contract of the reference's compiled operator (csrc/points_to_volumes/points_to_volumes_cpu.cpp, .cu), NOT of its Python
+ * twin.  points (N,P,3) and feats (N,P,C) contiguous f32, in the volume's local coordinates; grid_sizes (N,3) i64 contiguous:
+ * depth, height, width of cloud n's grid, at most the tensors' (D,H,W) (a larger one is cut at the tensor's extent); mask f32 or NULL
+ * (every point counts), element (n,p) at mask[n * mask_stride_n + p * mask_stride_p] (a stride of 0 is fine), a point with
+ * mask == 0 is skipped.  densities (N,1,D,H,W) and features (N,C,D,H,W) f32 are read through their five ELEMENT strides (host
+ * arrays of 5 i64), so a strided view is updated in place; contributions are ADDED to what they hold.
+ *   location on an axis   (p + 1) * 0.5 * (grid - (align_corners ? 1 : 0)) - (align_corners ? 0 : 0.5): p + 1 in f32, the rest in f64
+ *   splat == 0 (nearest)  voxel = the f64 location rounded half AWAY from zero (lround); weight 1
+ *   splat != 0            the location rounded once to f32, x = trunc (toward ZERO), rx = location - x; corner (x+ux, y+uy, z+uz) has
+ *                         weight (ux ? rx : 1 - rx)(uy ? ry : 1 - ry)(uz ? rz : 1 - rz), an f32 product from the left.  A location in
+ *                         (-1, 0) therefore EXTRAPOLATES: voxel 0 gets 1 - rx > 1, voxel 1 gets rx < 0 (the reference does the same)
+ *   a corner adds weight * point_weight to its density and feats[c] * weight * point_weight to feature c (f32, from the left)
+ * A corner outside [0, grid) on any axis is skipped, in the forward and in both gradients; so is a point whose location is not
+ * finite or does not fit an i64.  N, P, D, H or W of 0: P3D_OK without a launch.
+ *
+ * Forward, atomic form (keys == sorted_samples == NULL): float atomics, the two voxels of an x pair from adjacent lanes.
+ * Forward, ordered form: p3d_points_to_volumes_keys writes the voxel n * D*H*W + (z * H + y) * W + x, or -1, of each of the
+ * N * P * (splat ? 8 : 1) samples (sample = point * 8 + corner, corners in the reference's order ux, uy, uz = bit 2, 1, 0) into keys
+ * (i32); the caller sorts the sample indices STABLY by key into sorted_samples (i64) and passes both with a workspace of
+ * p3d_points_to_volumes_workspace_bytes(N, P, C, splat) bytes.  The rows of a voxel (1 + C floats) are summed by the fixed tree of
+ * ordered_sum.h and the total is added to the volume once: no float atomic, the same bits on every run.  N * D * H * W beyond
+ * INT32_MAX: P3D_ERR_UNSUPPORTED from both entries.
+ *
+ * Backward: a gather per point, no atomics.  grad_feats (N,P,C)[c] += grad_features[c][voxel] * weight * point_weight over the
+ * corners in the reference's order (f32); with splat, grad_points (N,P,3) per axis += source * (+-1) * (the other two axis
+ * weights) * 0.5 * (grid - scale offset) * point_weight in f64, rounded to f32 once per corner, where source = grad_densities[voxel]
+ * + sum_c feats[c] * grad_features[c][voxel] (each product in f32, the sum in f64, as the reference's GPU operator has it).
+ * Both outputs are contiguous and ADDED to (the caller zero-fills).  Without splat grad_points, feats and grad_densities are not
+ * touched and may be NULL.  The gradient volumes are read through their element strides (an expanded gradient has strides of 0). */
+size_t p3d_points_to_volumes_workspace_bytes(int64_t N, int64_t P, int64_t C, int splat);
+int p3d_points_to_volumes_keys(const float* points, const int64_t* grid_sizes, const float* mask, int64_t mask_stride_n,
+                               int64_t mask_stride_p, int64_t N, int64_t P, int64_t D, int64_t H, int64_t W, int align_corners,
+                               int splat, int32_t* keys, p3d_stream_t stream);
+int p3d_points_to_volumes_forward(const float* points, const float* feats, const int64_t* grid_sizes, const float* mask,
+                                  int64_t mask_stride_n, int64_t mask_stride_p, int64_t N, int64_t P, int64_t C, int64_t D, int64_t H,
+                                  int64_t W, float* densities, const int64_t* densities_strides, float* features,
+                                  const int64_t* features_strides, float point_weight, int align_corners, int splat,
+                                  const int32_t* keys, const int64_t* sorted_samples, void* workspace, size_t workspace_bytes,
+                                  p3d_stream_t stream);
+int p3d_points_to_volumes_backward(const float* points, const float* feats, const int64_t* grid_sizes, const float* mask,
+                                   int64_t mask_stride_n, int64_t mask_stride_p, int64_t N, int64_t P, int64_t C, int64_t D, int64_t H,
+                                   int64_t W, const float* grad_densities, const int64_t* grad_densities_strides,
+                                   const float* grad_features, const int64_t* grad_features_strides, float point_weight,
+                                   int align_corners, int splat, float* grad_points, float* grad_feats, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

@@ -1147,6 +1147,112 @@ def ball_query(p1, p2, lengths1, lengths2, K, radius, skip_points_outside_cube=F
 
 
 # ----------------------------------------------------------------------------------------------
+# point clouds into voxel grids (csrc/points_to_volumes.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
+# POINTS_TO_VOLUMES_EXPORTS to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op), which come here for float32 GPU tensors
+# and own a torch formulation of the same contract for CPU tensors.
+POINTS_TO_VOLUMES_CALLS = {"atomic": 0, "ordered": 0}  # forward launches by form: what actually ran (tests read it)
+
+
+def _p2v_cloud(who, points_3d, grid_sizes, mask, **others):
+    """(device, N, P, contiguous points, contiguous grid sizes, mask with its two element strides) after the shape checks."""
+    dev = _same_device(("points_3d", points_3d), ("grid_sizes", grid_sizes), ("mask", mask), *others.items())
+    if points_3d.dim() != 3 or points_3d.shape[2] != 3:
+        raise RuntimeError(f"{who}: points_3d must have shape (N, P, 3)")
+    N, P, _ = points_3d.shape
+    if grid_sizes.shape != (N, 3) or mask.shape != (N, P):
+        raise RuntimeError(f"{who}: grid_sizes must have shape (N, 3) and mask (N, P)")
+    if mask.dtype != torch.float32:
+        raise RuntimeError(f"expected dtype torch.float32, got {mask.dtype}")
+    return dev, N, P, _c(points_3d, torch.float32), _c(grid_sizes, torch.int64), mask
+
+
+def _p2v_volume(who, name, t, N, C, DHW, dev):
+    """The five element strides of a float32 (N, C, D, H, W) volume, as the C ABI takes them."""
+    if t.dtype != torch.float32 or t.device != dev or t.dim() != 5 or t.shape[0] != N or t.shape[1] != C or tuple(t.shape[2:]) != DHW:
+        raise RuntimeError(f"{who}: {name} must be a float32 tensor of shape ({N}, {C}, {DHW[0]}, {DHW[1]}, {DHW[2]}) on {dev}")
+    return (ctypes.c_int64 * 5)(*t.stride())
+
+
+def points_to_volumes_forward(points_3d, points_features, volume_densities, volume_features, grid_sizes, mask, point_weight,
+                              align_corners, splat):
+    """PointsToVolumesForward (points_to_volumes.h): adds the clouds to volume_densities (N, 1, D, H, W) and volume_features
+    (N, C, D, H, W) IN PLACE, through their strides, and returns nothing (include/p3d_amd.h has the arithmetic).  Float atomics or,
+    under torch.use_deterministic_algorithms(True), the ordered sum over the (point, corner) samples sorted by voxel on the device:
+    the same bits on every run.  There N * D * H * W must fit an int32."""
+    who = "points_to_volumes_forward"
+    dev, N, P, points, grid, mask = _p2v_cloud(who, points_3d, grid_sizes, mask, points_features=points_features,
+                                               volume_densities=volume_densities, volume_features=volume_features)
+    if points_features.dim() != 3 or points_features.shape[:2] != (N, P):
+        raise RuntimeError(f"{who}: points_features must have shape (N, P, C)")
+    C = int(points_features.shape[2])
+    if volume_densities.dim() != 5:
+        raise RuntimeError(f"{who}: volume_densities must have shape (N, 1, D, H, W)")
+    DHW = tuple(int(v) for v in volume_densities.shape[2:])
+    dstr = _p2v_volume(who, "volume_densities", volume_densities, N, 1, DHW, dev)
+    fstr = _p2v_volume(who, "volume_features", volume_features, N, C, DHW, dev)
+    feats = _c(points_features, torch.float32)
+    splat, align = int(bool(splat)), int(bool(align_corners))
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        keys = order = ws = None
+        nbytes = 0
+        if _ordered() and N * P > 0 and DHW[0] * DHW[1] * DHW[2] > 0:
+            if N * DHW[0] * DHW[1] * DHW[2] > MAX_INT:
+                raise RuntimeError(f"{who}: the deterministic form keys a voxel by an int32 and N * D * H * W = "
+                                   f"{N * DHW[0] * DHW[1] * DHW[2]} does not fit; add the batch in pieces")
+            keys = torch.empty((N * P * (8 if splat else 1),), dtype=torch.int32, device=dev)
+            rc = lib.p3d_points_to_volumes_keys(_ptr(points), _ptr(grid), _ptr(mask), mask.stride(0), mask.stride(1), N, P, *DHW, align,
+                                                splat, _ptr(keys), _stream(dev))
+            _lib.check(rc, who)
+            order = torch.sort(keys, stable=True).indices
+            nbytes = lib.p3d_points_to_volumes_workspace_bytes(N, P, C, splat)
+            ws = _workspace(nbytes, dev)
+        rc = lib.p3d_points_to_volumes_forward(_ptr(points), _ptr(feats), _ptr(grid), _ptr(mask), mask.stride(0), mask.stride(1), N, P, C,
+                                               *DHW, _ptr(volume_densities), dstr, _ptr(volume_features), fstr, float(point_weight),
+                                               align, splat, _ptr(keys), _ptr(order), _ptr(ws), nbytes, _stream(dev))
+        _lib.check(rc, who)
+    POINTS_TO_VOLUMES_CALLS["ordered" if order is not None else "atomic"] += 1
+
+
+def points_to_volumes_backward(points_3d, points_features, grid_sizes, mask, point_weight, align_corners, splat, grad_volume_densities,
+                               grad_volume_features, grad_points_3d, grad_points_features):
+    """PointsToVolumesBackward: ADDS to grad_points_features (N, P, C) and, with splat, to grad_points_3d (N, P, 3), in place; returns
+    nothing.  A gather per point without atomics: the same bits on every run.  The gradient volumes are read through their strides
+    (an expanded gradient is fine).  Without splat points_features and grad_points_3d are not touched (the reference passes
+    expanded placeholders)."""
+    who = "points_to_volumes_backward"
+    dev, N, P, points, grid, mask = _p2v_cloud(who, points_3d, grid_sizes, mask, grad_volume_densities=grad_volume_densities,
+                                               grad_volume_features=grad_volume_features, grad_points_features=grad_points_features)
+    if grad_points_features.dim() != 3 or grad_points_features.shape[:2] != (N, P) or grad_points_features.dtype != torch.float32:
+        raise RuntimeError(f"{who}: grad_points_features must be a float32 tensor of shape (N, P, C)")
+    C = int(grad_points_features.shape[2])
+    if grad_volume_densities.dim() != 5:
+        raise RuntimeError(f"{who}: grad_volume_densities must have shape (N, 1, D, H, W)")
+    DHW = tuple(int(v) for v in grad_volume_densities.shape[2:])
+    dstr = _p2v_volume(who, "grad_volume_densities", grad_volume_densities, N, 1, DHW, dev)
+    fstr = _p2v_volume(who, "grad_volume_features", grad_volume_features, N, C, DHW, dev)
+    splat = int(bool(splat))
+    feats = gp = None
+    if splat:
+        _same_device(("points_3d", points_3d), ("points_features", points_features), ("grad_points_3d", grad_points_3d))
+        if points_features.shape != (N, P, C) or grad_points_3d.shape != (N, P, 3) or grad_points_3d.dtype != torch.float32:
+            raise RuntimeError(f"{who}: points_features must have shape (N, P, C) and grad_points_3d be float32 of shape (N, P, 3)")
+        feats = _c(points_features, torch.float32)
+        gp = grad_points_3d.contiguous()  # (a copy only for a strided buffer; written back below)
+    gf = grad_points_features.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        rc = lib.p3d_points_to_volumes_backward(_ptr(points), _ptr(feats), _ptr(grid), _ptr(mask), mask.stride(0), mask.stride(1), N, P, C,
+                                                *DHW, _ptr(grad_volume_densities), dstr, _ptr(grad_volume_features), fstr,
+                                                float(point_weight), int(bool(align_corners)), splat, _ptr(gp), _ptr(gf), _stream(dev))
+        _lib.check(rc, who)
+    if gf is not grad_points_features:
+        grad_points_features.copy_(gf)
+    if splat and gp is not grad_points_3d:
+        grad_points_3d.copy_(gp)
+
+
+# ----------------------------------------------------------------------------------------------
 # point-mesh distances (csrc/point_mesh.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the eight names to
 # pytorch3d_amd.point_mesh, which comes here for float32 GPU tensors and owns a torch formulation for everything else.
 _PM_KINDS = {"point_face": (_lib.POINT_MESH_POINT, _lib.POINT_MESH_TRIANGLE), "face_point": (_lib.POINT_MESH_TRIANGLE, _lib.POINT_MESH_POINT),
@@ -1289,6 +1395,8 @@ POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "fa
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
 # bound by shim.make_module to the wrappers of pytorch3d_amd.sample_farthest_points / pytorch3d_amd.ball_query (<name>_op)
 POINT_CLOUD_EXPORTS = ("sample_farthest_points", "ball_query")
+# bound by shim.make_module to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op)
+POINTS_TO_VOLUMES_EXPORTS = ("points_to_volumes_forward", "points_to_volumes_backward")
 
 
 HOT_PATH_EXPORTS = (

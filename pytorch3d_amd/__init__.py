@@ -16,6 +16,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     edge_point_distance              distances between a point cloud and the faces / edges of a mesh, fused
     sample_points_from_meshes, sample_points_packed  points drawn from the surface of a mesh batch, a function of given uniforms, fused
     sample_farthest_points, ball_query, masked_gather  farthest point sampling (a cloud in one workgroup's registers) and ball query, fused
+    add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  point clouds into voxel grids, in place, fused
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -33,6 +34,7 @@ from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_to
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
 from .point_mesh import (edge_point_distance, face_point_distance, point_edge_distance, point_face_distance,  # noqa: F401
                          point_mesh_edge_distance, point_mesh_face_distance)
+from .points_to_volumes import add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401

@@ -210,6 +210,13 @@ _SIGNATURES = {
     "p3d_sample_farthest_points_workspace_bytes": (c_size, [c_i64, c_i64]),
     "p3d_sample_farthest_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_ball_query": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr]),
+    # point clouds into voxel grids (csrc/points_to_volumes.hip)
+    "p3d_points_to_volumes_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_int]),
+    "p3d_points_to_volumes_keys": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
+    "p3d_points_to_volumes_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
+                                              c_ptr, c_ptr, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_points_to_volumes_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
+                                               c_ptr, c_ptr, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

@@ -43,7 +43,8 @@ inline size_t partial_bytes(int64_t S, int R, int chunks) {
   return align_up(waves * (size_t)chunks * 2 * R * sizeof(float), 256) + align_up(waves * (size_t)chunks * 2 * sizeof(int), 256);
 }
 
-__global__ __launch_bounds__(256) void fill_zero_kernel(float* __restrict__ p, int64_t n) {
+// (static: the header is included by more than one translation unit)
+static __global__ __launch_bounds__(256) void fill_zero_kernel(float* __restrict__ p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0.0f;
 }
 

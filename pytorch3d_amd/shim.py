@@ -13,7 +13,8 @@ so the module must be in sys.modules before they are imported.  Operators outsid
 under `pytorch3d.loss.point_mesh_face_distance` / `point_mesh_edge_distance` ARE served (csrc/point_mesh.hip), so the unmodified
 reference losses run under plain `shim.install()`.  So are `_C.sample_farthest_points` and `_C.ball_query` (csrc/fps_ball.hip): the
 unmodified `pytorch3d.ops.sample_farthest_points` runs, and so does the forward of `pytorch3d.ops.ball_query`; its backward ends in
-`_C.knn_points_backward`, which stays a stub -- patch_python replaces the whole function.
+`_C.knn_points_backward`, which stays a stub -- patch_python replaces the whole function.  And `_C.points_to_volumes_forward` /
+`_backward` (csrc/points_to_volumes.hip): the unmodified `pytorch3d.ops.add_pointclouds_to_volumes` runs, forward and backward.
 
     shim.install(patch_python=True)
 
@@ -65,6 +66,10 @@ reference classes runs on them end to end:
                                                                  one workgroup per cloud and the cloud in registers; ball query as
                                                                  one autograd node whose backward is the nearest neighbours'; other
                                                                  inputs go to this package's torch formulation
+
+    ops.points_to_volumes.add_pointclouds_to_volumes / add_points_features_to_volume_densities_features -> csrc/points_to_volumes.hip
+                                                                 as one autograd node (ordered sum under the strict deterministic
+                                                                 flag); CPU tensors go to this package's torch formulation
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -118,6 +123,10 @@ def make_module(flavour="ctypes"):
 
     for name in _ours.POINT_CLOUD_EXPORTS:
         setattr(mod, name, getattr(importlib.import_module(__package__ + "." + name), name + "_op"))
+    # point clouds into voxel grids (pytorch3d_amd/points_to_volumes.py): csrc/points_to_volumes.hip for GPU tensors, a torch formulation
+    # of the same contract for CPU tensors; in place, no return value.  Both flavours serve these wrappers.
+    for name in _ours.POINTS_TO_VOLUMES_EXPORTS:
+        setattr(mod, name, getattr(importlib.import_module(__package__ + ".points_to_volumes"), name + "_op"))
     if flavour == "pybind":
         # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
         def compiled(name):
@@ -368,6 +377,47 @@ def patch_reference_python():
     _patch_point_mesh_losses()
     _patch_sample_points()
     _patch_fps_ball()
+    _patch_points_to_volumes()
+
+
+def _patch_points_to_volumes():
+    """pytorch3d.ops.points_to_volumes.add_pointclouds_to_volumes / add_points_features_to_volume_densities_features -> this
+    package's functions, in every module that copied the names (pytorch3d.ops).  The reference's `_python=True` asks for ITS Python
+    twin, a different function (floor, half to even, no align_corners): such a call goes to the reference unchanged.  PATCH_CALLS
+    counts GPU calls as fused and the torch formulation (CPU tensors) as fallbacks."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".points_to_volumes")
+    try:  # every module that copied the names must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.ops.points_to_volumes")
+        importlib.import_module("pytorch3d.ops")
+    except ImportError:  # a reference checkout without the module: nothing to patch
+        return
+    ref_clouds, ref_tensors = ref.add_pointclouds_to_volumes, ref.add_points_features_to_volume_densities_features
+
+    def add_pointclouds_to_volumes(pointclouds, initial_volumes, mode="trilinear", min_weight=1e-4, rescale_features=True, _python=False):
+        if _python:
+            return ref_clouds(pointclouds, initial_volumes, mode, min_weight, rescale_features, _python=True)
+        out = ours.add_pointclouds_to_volumes(pointclouds, initial_volumes, mode, min_weight, rescale_features)
+        _count("add_pointclouds_to_volumes", ours.kernel_path(initial_volumes.densities()))  # (a call that raised is not counted)
+        return out
+
+    def add_points_features_to_volume_densities_features(points_3d, points_features, volume_densities, volume_features,
+                                                         mode="trilinear", min_weight=1e-4, mask=None, grid_sizes=None,
+                                                         rescale_features=True, _python=False, align_corners=True):
+        if _python:
+            return ref_tensors(points_3d, points_features, volume_densities, volume_features, mode, min_weight, mask, grid_sizes,
+                               rescale_features, True, align_corners)
+        out = ours.add_points_features_to_volume_densities_features(points_3d, points_features, volume_densities, volume_features, mode,
+                                                                    min_weight, mask, grid_sizes, rescale_features, align_corners)
+        _count("add_points_features_to_volume_densities_features", ours.kernel_path(points_3d, volume_densities))
+        return out
+
+    for orig, new in ((ref_clouds, add_pointclouds_to_volumes), (ref_tensors, add_points_features_to_volume_densities_features)):
+        new.__doc__ = getattr(orig, "__doc__", None)
+        new.__wrapped__ = orig
+        new.__p3d_amd__ = True
+        _replace_everywhere(orig, new)
 
 
 def _patch_fps_ball():
