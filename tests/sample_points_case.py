@@ -317,10 +317,16 @@ def gate_distribution(idx, areas, first=0):
     assert counts.sum() == S and worst <= 1.0, (counts, want)
 
 
-def gate_grads(verts, faces, idx, w, got, grad_samples=None, grad_normals=None, what=""):
-    """Case 6: grad_verts against the float64 restatement on the given indices and weights, within the project's measure."""
+def grads_gate(verts, faces, idx, w, grad_samples=None, grad_normals=None):
+    """(truth, tolerance) of gate_grads: the float64 restatement and four times the float32 torch formulation's error against it."""
     truth, _ = grads64(verts, faces, idx, w, grad_samples, grad_normals)
-    tol = measure(formulation_grads32(verts, faces, idx, w, grad_samples, grad_normals), truth)
+    return truth, measure(formulation_grads32(verts, faces, idx, w, grad_samples, grad_normals), truth)
+
+
+def gate_grads(verts, faces, idx, w, got, grad_samples=None, grad_normals=None, what="", known=None):
+    """Case 6: grad_verts against the float64 restatement on the given indices and weights, within the project's measure.
+    known: grads_gate(...) of the same arguments, where several answers are judged on one input."""
+    truth, tol = grads_gate(verts, faces, idx, w, grad_samples, grad_normals) if known is None else known
     err = float(np.abs(np.asarray(got, dtype=np.float64) - truth).max())
     print("grads %s: error %.3g, gate %.3g, largest |gradient| %.3g" % (what, err, tol, float(np.abs(truth).max())))
     assert np.isfinite(np.asarray(got)).all() and err <= tol, what
@@ -343,6 +349,143 @@ def gate_star(idx, w, got):
     err = float(np.abs(np.asarray(got, dtype=np.float64) - truth).max())
     print("star: error %.3g, bound %.3g" % (err, bound))
     assert (np.asarray(idx) == 0).all() and err <= bound
+
+
+def gate_table(areas32, faces, first, nf, u, idx, table):
+    """The cumulative table (F,) float32 of an implementation whose float32 face areas are areas32: non-decreasing inside a mesh,
+    restarting at each mesh, a face of zero area repeating its predecessor, within D(F) 2^-24 total of the float64 prefix sums of
+    those areas; and the choice idx exactly the host's searchsorted on that table."""
+    F = faces.shape[0]
+    rows64 = tables64(areas32, first, nf)
+    assert table.shape == (F,) and table.dtype == np.float32
+    rows32 = [table[int(a):int(a) + int(n)] for a, n in zip(first.tolist(), nf.tolist())]
+    depth, worst = scan_depth(F), 0.0
+    for n, (r32, r64) in enumerate(zip(rows32, rows64)):
+        if r32.size == 0:
+            continue
+        assert (np.diff(r32) >= 0).all(), "the table steps down inside mesh %d" % n
+        assert r32[0] == areas32[int(first[n])], "the table does not restart at mesh %d" % n
+        zero = np.nonzero(areas32[int(first[n]):int(first[n]) + r32.size] == 0)[0]
+        assert all(r32[k] == (r32[k - 1] if k else 0.0) for k in zero), "a face of zero area does not repeat its predecessor"
+        bound = depth * 2.0 ** -24 * float(r64[-1])
+        err = float(np.abs(r32.astype(np.float64) - r64).max())
+        worst = max(worst, err / bound if bound > 0 else err)
+        assert err <= bound, (n, err, bound)
+    print("table: F = %d, D(F) = %d, worst error / bound %.3g" % (F, depth, worst))
+    assert np.array_equal(idx, choose(rows32, first.tolist(), u[:, :, 0].numpy(), dtype=np.float32)), "the choice is not the host's on this table"
+
+
+# ---- long runs of the backward (tests/test_*_cloud_kernel_edges.py, section A) -----------------------------------------------------------
+WAVE_STEP = 64     # csrc/sample_points.hip: face_sums_kernel -- samples a wave adds per step
+FLUSH_AT = 128     # csrc/wave_table.h: WaveTable<9 | 12, 192>::kFlushAt = SLOTS - 64
+LONG_S = 180010    # samples per mesh of long_run_batch(): 3 x 180 010 = 540 030 > 2048 x 64 x 4
+
+
+def backward_plan(num_samples):
+    """(waves, span) of backward_rows_atomic (csrc/sample_points.hip): wave w adds the samples [w span, (w + 1) span), 64 per step."""
+    waves = -(-num_samples // 64)
+    if waves > 2048:
+        waves = max(-(-num_samples // 1024), 2048)
+    waves = min(waves, 4 * 4096)
+    blocks = -(-waves // 4)
+    span = -(-(-(-num_samples // (blocks * 4))) // 64) * 64
+    return -(-num_samples // span), span
+
+
+def long_run_batch(seed=71):
+    """Three meshes for ONE launch over long runs: the single face of star(); a soup of 6 000 faces over 1 500 vertices; the 300-face
+    mesh of ragged_batch() with its faces of zero area.  -> (verts, faces, first, nf) packed."""
+    v0, f0 = star()[:2]
+    v1, f1 = _soup(torch.Generator().manual_seed(seed), 1500, 6000)
+    verts_list, faces_list = ragged_batch()
+    return pack([v0, v1, verts_list[3]], [f0, f1, faces_list[3]])
+
+
+def long_run_grads(which, seed=72):
+    """(uniforms, grad_samples, grad_normals or None) of the long-run case."""
+    gen = torch.Generator().manual_seed(seed)
+    gs = torch.randn(3, LONG_S, 3, generator=gen)
+    gn = torch.randn(3, LONG_S, 3, generator=gen) if which == "both" else None
+    return uniforms(3, LONG_S, seed + 1), gs, gn
+
+
+def long_run_reach(idx, nf):
+    """What the long-run case is for, from the host's plan and the face indices (3, LONG_S) of a forward: asserts every condition and
+    returns the waves that show them {"one_key", "flush", "straddle", "last"}."""
+    flat = np.asarray(idx).reshape(-1)
+    num_samples, S = flat.size, np.asarray(idx).shape[1]
+    waves, span = backward_plan(num_samples)
+    assert num_samples > 2048 * 64 * 4 and span >= 256 and span % WAVE_STEP == 0, (num_samples, span)
+    assert (flat >= 0).all()
+    steps = span // WAVE_STEP
+    # a wave wholly inside mesh 0 (one face): the same key in every step, found in the slot an earlier step left
+    one_key = [w for w in range(waves) if (w + 1) * span <= S]
+    assert one_key and all((flat[w * span:(w + 1) * span] == flat[0]).all() for w in one_key[:3]) and int(nf[0]) == 1
+    # a wave inside mesh 1 with more than kFlushAt distinct faces in its first three steps: step four begins with the flush
+    flush = [w for w in range(-(-S // span), 2 * S // span)
+             if np.unique(flat[w * span:w * span + 3 * WAVE_STEP]).size > FLUSH_AT]
+    assert steps >= 4 and flush, "no wave fills its table"
+    # a wave across each mesh boundary, and a last wave that the clamp of `end` cuts short
+    straddle = [b // span for b in (S, 2 * S) if b % span != 0]
+    assert len(straddle) == 2, "a mesh boundary falls on a wave border"
+    assert num_samples % span != 0 and (waves - 1) * span < num_samples
+    return {"one_key": one_key[0], "flush": flush[0], "straddle": straddle, "last": waves - 1, "span": span, "waves": waves}
+
+
+def drop_fourth_step(idx, wave):
+    """idx with every sample of the fourth step of `wave` set to -1: what the rows hold when a flush loses that step."""
+    flat = np.array(idx).reshape(-1)
+    _, span = backward_plan(flat.size)
+    assert span >= 4 * WAVE_STEP
+    flat[wave * span + 3 * WAVE_STEP:wave * span + 4 * WAVE_STEP] = -1
+    return flat.reshape(np.asarray(idx).shape)
+
+
+# ---- many small meshes (section B) -----------------------------------------------------------------------------------------------------
+def many_small_meshes(seed=81, N=700):
+    """700 meshes with face counts drawn from {0, 0, 1, 2, 3, 70}; three EMPTY meshes at the start, a run of five in the middle and two
+    at the end.  -> (verts, faces, first, nf) packed."""
+    gen = torch.Generator().manual_seed(seed)
+    counts = torch.tensor([0, 0, 1, 2, 3, 70])[torch.randint(0, 6, (N,), generator=gen)].tolist()
+    for n in (0, 1, 2, N // 2, N // 2 + 1, N // 2 + 2, N // 2 + 3, N // 2 + 4, N - 2, N - 1):
+        counts[n] = 0
+    verts_list, faces_list = [], []
+    for c in counts:
+        if c == 0:
+            verts_list.append(torch.rand(3, 3, generator=gen) * 2 - 1), faces_list.append(torch.zeros((0, 3), dtype=torch.int64))
+        else:
+            v, f = _soup(gen, 3 + c // 2, c)
+            verts_list.append(v), faces_list.append(f)
+    return pack(verts_list, faces_list)
+
+
+def small_meshes_reach(first, nf, F):
+    """Asserts what the batch is for: more than one block of level 1, several heads in most waves of 64 faces, runs of empty meshes
+    at the start, in the middle and at the end (first_idx == F there)."""
+    first, nf = np.asarray(first), np.asarray(nf)
+    N = nf.size
+    assert F > 4 * SCAN_BLOCK and not nf[:3].any() and not nf[N // 2:N // 2 + 5].any() and not nf[-2:].any()
+    assert (first[:4] == 0).all() and (first[-2:] == F).all() and len(set(first[N // 2:N // 2 + 6].tolist())) == 1
+    heads = np.bincount(np.unique(first[nf > 0]) // 64, minlength=-(-F // 64))
+    print("small meshes: F = %d, heads per wave: median %d, largest %d" % (F, int(np.median(heads)), int(heads.max())))
+    assert np.median(heads) >= 2 and heads.max() >= 16
+    return heads
+
+
+def gate_small_meshes(verts, faces, first, nf, u, areas32, table, samples, normals, idx, bary):
+    """Section B on numpy outputs: gate_table; -1 and zero rows for the empty meshes; bary the formulation's bits; samples within
+    12 x 2^-24 of the float64 restatement (|v| <= 1: the bound of the second-round test of the scan)."""
+    gate_table(areas32, faces, first, nf, u, idx, table)
+    empty = np.asarray(nf) == 0
+    assert (idx[empty] == -1).all() and (idx[~empty] >= 0).all()
+    for name, t in (("samples", samples), ("normals", normals), ("bary", bary)):
+        assert np.isfinite(t).all() and not t[empty].any(), name
+    w32 = np.where((idx >= 0)[..., None], formulation_weights32(u.numpy()), 0.0)
+    assert bits_equal(bary, w32), "bary differs from the torch formulation in some bit"
+    assert float(verts.abs().max()) <= 1.0
+    err = float(np.abs(samples - samples64(verts, faces, idx, weights64(u.numpy()))).max())
+    print("small meshes: samples error %.3g, bound %.3g" % (err, 12 * 2.0 ** -24))
+    assert err <= 12 * 2.0 ** -24
 
 
 def binomial_bounds(areas, S, sigmas=5.0):

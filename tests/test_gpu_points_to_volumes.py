@@ -3,7 +3,9 @@
 
 Lattice cases must equal the reference's bits in both forward forms; random cases must lie, like the reference's own result, within
 (n + 2) 2^-24 sum |t_i| of the float64 restatement of the same n terms (tests/points_to_volumes_case.py).  The launches do not cap
-their grids (one lane per sample, no grid-stride loop), so there is no second loop round to reach.
+their grids (one lane per sample, no grid-stride loop), so there is no second round of a loop; the second rounds that exist are
+ordered_sum.h's -- pass2_kernel's second block (more than 256 waves of sorted samples) and a segment that runs over many waves --
+and the cases here stop at 65 waves: tests/test_gpu_cloud_kernel_edges.py (section D, "long": 938 waves) reaches them.
 """
 import contextlib
 import importlib

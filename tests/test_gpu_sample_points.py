@@ -96,25 +96,8 @@ def test_edge_uniforms():
 def _gate_table(verts, faces, first, nf, u, idx, table):
     """The table read back from the workspace: non-decreasing inside a mesh, restarting at each mesh, within D(F) 2^-24 total of the
     float64 prefix sums of the kernels' own float32 areas; and the choice exactly the host's searchsorted on that table."""
-    F = faces.shape[0]
     areas32 = _p3d().face_areas_normals(verts.to(_dev()), faces.to(_dev()))[0].cpu().numpy()  # the same arithmetic, by contract
-    rows64 = C.tables64(areas32, first, nf)
-    assert table.shape == (F,) and table.dtype == np.float32
-    rows32 = [table[int(a):int(a) + int(n)] for a, n in zip(first.tolist(), nf.tolist())]
-    depth, worst = C.scan_depth(F), 0.0
-    for n, (r32, r64) in enumerate(zip(rows32, rows64)):
-        if r32.size == 0:
-            continue
-        assert (np.diff(r32) >= 0).all(), "the table steps down inside mesh %d" % n
-        assert r32[0] == areas32[int(first[n])], "the table does not restart at mesh %d" % n
-        zero = np.nonzero(areas32[int(first[n]):int(first[n]) + r32.size] == 0)[0]
-        assert all(r32[k] == (r32[k - 1] if k else 0.0) for k in zero), "a face of zero area does not repeat its predecessor"
-        bound = depth * 2.0 ** -24 * float(r64[-1])
-        err = float(np.abs(r32.astype(np.float64) - r64).max())
-        worst = max(worst, err / bound if bound > 0 else err)
-        assert err <= bound, (n, err, bound)
-    print("table: F = %d, D(F) = %d, worst error / bound %.3g" % (F, depth, worst))
-    assert np.array_equal(idx, C.choose(rows32, first.tolist(), u[:, :, 0].numpy(), dtype=np.float32)), "the choice is not the host's on this table"
+    C.gate_table(areas32, faces, first, nf, u, idx, table)
 
 
 def test_table_of_the_ragged_batch():
