@@ -917,6 +917,38 @@ int p3d_points_to_volumes_backward(const float* points, const float* feats, cons
                                    const float* grad_features, const int64_t* grad_features_strides, float point_weight,
                                    int align_corners, int splat, float* grad_points, float* grad_feats, p3d_stream_t stream);
 
+/* ---- point-cloud covariances, curvatures and local coordinate frames (pytorch3d/ops/points_normals.py; csrc/point_frames.hip) ----
+ *
+ * points (N,P,3) contiguous f32, lengths (N) i64 or NULL (full), clamped into [0, P]; D must be 3 and 1 <= K <= P3D_FRAMES_MAX_K,
+ * otherwise P3D_ERR_UNSUPPORTED (the caller owns a formulation for the rest).  The points are taken as they come: the reference's
+ * `points - cloud mean` is the caller's (pytorch3d_amd/points_normals.py does it with the reference's expression, since it changes
+ * the float32 bits of every distance).  For n and i < lengths[n], in one pass:
+ *   neighbours   the kn = min(K, lengths[n]) points j of the same cloud with the smallest (dist, j), i itself included; dist as for
+ *                the nearest neighbours above (per coordinate the difference and its square, accumulated, NOT fused), ties to the
+ *                lower index: the rows of p3d_knn_points_forward(points, points) for any K it takes
+ *   covariance   mean = (sum of the neighbours, k ascending) / kn; cov = (sum of the outer products of neighbour - mean, k ascending)
+ *                / kn; float32 (ops/utils.py get_point_covariances)
+ *   curvatures   (3) ascending, frames (3,3) with the vectors in the COLUMNS, column 0 the normal: the reference's symeig3x3
+ *                (common/workaround/symeig3x3.py) with eps = float32 eps, operation for operation -- p1.clamp(eps), acos / cos with r
+ *                clamped to +-(1 - eps), the exp(-(p1 / (6 eps))^2) blend of the eigenvalues towards the sorted diagonal, the
+ *                cross-product eigenvectors with their +-eps regularisers.  It is NOT a true eigen-decomposition where the
+ *                off-diagonal energy p1 is about 1e-6 or below, and is not meant to be
+ *   P3D_FRAMES_DISAMBIGUATE (flags)  column 0 and column 2 are negated where fewer than 0.5 * kn neighbours have
+ *                (x_k - x_i) . v > 0, then column 1 = column 0 x column 2 (_disambiguate_vector_directions)
+ * Rows i >= lengths[n] are zeros in every output.  curvatures (N,P,3) and frames (N,P,3,3) come together or are both NULL (then the
+ * eigen step is skipped); cov_out (N,P,3,3) and idx_out (N,P,K) i64 (slots k >= kn hold 0) are optional; at least one output.  Every
+ * entry of a given output is written, no memset in front.  No workspace, no atomics: the same bits on every run and stream.  There
+ * is no backward entry.  One lane per query, the cloud staged in LDS tiles of P3D_KNN_TILE points, a register queue of up to 64
+ * entries; the grid is p3d_point_frames_workgroups(N, P) workgroups, each owning its rows: no loop over the grid.  N or P of 0: P3D_OK, no launch. */
+#define P3D_FRAMES_MAX_K 64
+#define P3D_FRAMES_DISAMBIGUATE 1u
+/* The number of workgroups (of P3D_FRAMES_ROWS_PER_GROUP rows each) that p3d_point_frames launches for (N, P): N * ceil(P /
+ * P3D_FRAMES_ROWS_PER_GROUP), or -1 where that does not fit a launch (the entry then returns P3D_ERR_INVALID_ARG). */
+#define P3D_FRAMES_ROWS_PER_GROUP 64
+int64_t p3d_point_frames_workgroups(int64_t N, int64_t P);
+int p3d_point_frames(const float* points, const int64_t* lengths, int64_t N, int64_t P, int D, int K, unsigned flags,
+                     float* curvatures, float* frames, float* cov_out, int64_t* idx_out, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

@@ -1147,6 +1147,37 @@ def ball_query(p1, p2, lengths1, lengths2, K, radius, skip_points_outside_cube=F
 
 
 # ----------------------------------------------------------------------------------------------
+# point-cloud covariances, curvatures and local coordinate frames (csrc/point_frames.hip).  NOT in HOT_PATH_EXPORTS: the reference
+# has no compiled operator of this kind; pytorch3d_amd.points_normals (and, under patch_python, the reference's two functions) come here.
+def point_frames(points, lengths, K, disambiguate_directions=True, frames=True, cov=False, idx=False):
+    """(curvatures (N, P, 3), frames (N, P, 3, 3), cov (N, P, 3, 3), idx (N, P, K) int64) of p3d_point_frames (include/p3d_amd.h) on
+    the points AS GIVEN (the caller recentres), None for what was not asked for.  lengths (N,) int64 on the GPU or None (full clouds)."""
+    who = "point_frames"
+    _need_gpu(points, "points")
+    K = int(K)
+    if points.dim() != 3 or points.shape[2] != 3 or not 1 <= K <= _lib.FRAMES_MAX_K:
+        raise RuntimeError(f"{who}: the kernel takes points (N, P, 3) and 1 <= K <= {_lib.FRAMES_MAX_K}; pytorch3d_amd.points_normals "
+                           "has a torch formulation for the rest")
+    if not (frames or cov or idx):
+        raise RuntimeError(f"{who}: nothing asked for")
+    dev = points.device
+    N, P, D = points.shape
+    lengths = _int64_arg(lengths, N, dev, "lengths", who)
+    points = _c(points, torch.float32)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        curv_t = torch.empty((N, P, 3), dtype=torch.float32, device=dev) if frames else None
+        frames_t = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev) if frames else None
+        cov_t = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev) if cov else None
+        idx_t = torch.empty((N, P, K), dtype=torch.int64, device=dev) if idx else None
+        flags = _lib.FRAMES_DISAMBIGUATE if disambiguate_directions else 0
+        rc = lib.p3d_point_frames(_ptr(points), _ptr(lengths), N, P, D, K, flags, _ptr(curv_t), _ptr(frames_t), _ptr(cov_t), _ptr(idx_t),
+                                  _stream(dev))
+        _lib.check(rc, who)
+    return curv_t, frames_t, cov_t, idx_t
+
+
+# ----------------------------------------------------------------------------------------------
 # point clouds into voxel grids (csrc/points_to_volumes.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
 # POINTS_TO_VOLUMES_EXPORTS to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op), which come here for float32 GPU tensors
 # and own a torch formulation of the same contract for CPU tensors.

@@ -17,6 +17,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     sample_points_from_meshes, sample_points_packed  points drawn from the surface of a mesh batch, a function of given uniforms, fused
     sample_farthest_points, ball_query, masked_gather  farthest point sampling (a cloud in one workgroup's registers) and ball query, fused
     add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  point clouds into voxel grids, in place, fused
+    estimate_pointcloud_normals, estimate_pointcloud_local_coord_frames, point_covariances  normals, curvatures and local frames of a
+                                     point cloud from its K nearest neighbours, one launch, nothing of size K per point materialised
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -34,6 +36,8 @@ from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_to
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
 from .point_mesh import (edge_point_distance, face_point_distance, point_edge_distance, point_face_distance,  # noqa: F401
                          point_mesh_edge_distance, point_mesh_face_distance)
+from .points_normals import (estimate_pointcloud_local_coord_frames, estimate_pointcloud_normals,  # noqa: F401
+                             point_covariances)
 from .points_to_volumes import add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401

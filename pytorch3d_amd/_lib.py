@@ -29,6 +29,9 @@ BWD_MAKE_FACE_PRE = 2
 KNN_MAX_K = 32           # P3D_KNN_MAX_K
 KNN_TILE = 512           # P3D_KNN_TILE: p2 points staged per step
 KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
+FRAMES_MAX_K = 64        # P3D_FRAMES_MAX_K: the largest neighbourhood of csrc/point_frames.hip
+FRAMES_DISAMBIGUATE = 1  # P3D_FRAMES_DISAMBIGUATE
+FRAMES_ROWS_PER_GROUP = 64  # P3D_FRAMES_ROWS_PER_GROUP: query rows of one workgroup of csrc/point_frames.hip
 FPS_REGISTER_POINTS = 16384  # P3D_FPS_REGISTER_POINTS: the largest cloud the register form of farthest point sampling holds
 POINT_MESH_POINT, POINT_MESH_SEGMENT, POINT_MESH_TRIANGLE = 0, 1, 2  # P3D_POINT_MESH_*: the kind of a query / target object
 POINT_MESH_TILE = 64                # P3D_POINT_MESH_TILE: target records staged per wave and step
@@ -217,6 +220,9 @@ _SIGNATURES = {
                                               c_ptr, c_ptr, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_points_to_volumes_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
                                                c_ptr, c_ptr, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    # point-cloud covariances, curvatures and local coordinate frames (csrc/point_frames.hip)
+    "p3d_point_frames_workgroups": (c_i64, [c_i64, c_i64]),
+    "p3d_point_frames": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_uint, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

@@ -521,6 +521,36 @@ Tensor face_areas_normals_backward(const Tensor& grad_areas, const Tensor& grad_
   return scatter_face_grads(per_corner, f, V, "face_areas_normals_backward");
 }
 
+// ---- point-cloud covariances, curvatures and local frames (csrc/point_frames.hip): pytorch3d_amd/_C.py point_frames ---------------
+std::tuple<c10::optional<Tensor>, c10::optional<Tensor>, c10::optional<Tensor>, c10::optional<Tensor>> point_frames(
+    const Tensor& points, const c10::optional<Tensor>& lengths, int64_t K, bool disambiguate_directions, bool frames, bool cov, bool idx) {
+  check_gpu({{&points, "points"}});
+  TORCH_CHECK(points.dim() == 3 && points.size(2) == 3 && K >= 1 && K <= P3D_FRAMES_MAX_K, "point_frames: the kernel takes points (N, P, 3) and 1 <= K <= ",
+              P3D_FRAMES_MAX_K, "; pytorch3d_amd.points_normals has a torch formulation for the rest");
+  TORCH_CHECK(points.scalar_type() == at::kFloat, "points must be float32");
+  TORCH_CHECK(frames || cov || idx, "point_frames: nothing asked for");
+  DeviceGuard guard(points.device());
+  auto p = points.contiguous();
+  const int64_t N = p.size(0), P = p.size(1);
+  Tensor len;
+  if (lengths.has_value()) {
+    check_gpu({{&points, "points"}, {&*lengths, "lengths"}});
+    TORCH_CHECK(lengths->dim() == 1 && lengths->size(0) == N && lengths->scalar_type() == at::kLong, "lengths must be int64 of shape (N,)");
+    len = lengths->contiguous();
+  }
+  c10::optional<Tensor> curv_t, frames_t, cov_t, idx_t;
+  if (frames) curv_t = at::empty({N, P, 3}, p.options()), frames_t = at::empty({N, P, 3, 3}, p.options());
+  if (cov) cov_t = at::empty({N, P, 3, 3}, p.options());
+  if (idx) idx_t = at::empty({N, P, K}, p.options().dtype(at::kLong));
+  const bool any = N * P > 0;
+  ok(p3d_point_frames(any ? p.data_ptr<float>() : nullptr, len.defined() && N > 0 ? len.data_ptr<int64_t>() : nullptr, N, P, 3, (int)K,
+                      disambiguate_directions ? P3D_FRAMES_DISAMBIGUATE : 0u, frames && any ? curv_t->data_ptr<float>() : nullptr,
+                      frames && any ? frames_t->data_ptr<float>() : nullptr, cov && any ? cov_t->data_ptr<float>() : nullptr,
+                      idx && any ? idx_t->data_ptr<int64_t>() : nullptr, stream_of(p)),
+     "point_frames");
+  return {curv_t, frames_t, cov_t, idx_t};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -548,6 +578,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sigmoid_alpha_blend_backward", &sigmoid_alpha_blend_backward);
   m.def("face_areas_normals_forward", &face_areas_normals_forward);  // ext.cpp: the mesh classes' operators, float32 GPU tensors only
   m.def("face_areas_normals_backward", &face_areas_normals_backward);
+  m.def("point_frames", &point_frames);  // not an operator of ext.cpp: the fused estimate behind pytorch3d_amd.points_normals
   m.attr("EPS") = py::float_(1e-6);  // constants pytorch3d/renderer/points/pulsar/renderer.py reads at import time (ext.cpp:180-185)
   m.attr("MAX_FLOAT") = py::float_(3.4e38);
   m.attr("MAX_INT") = py::int_(2147483647);

@@ -6,7 +6,7 @@
 // points with one ds_read_b128 per coordinate -- identical addresses broadcast, no bank conflict.  A tile's tail up to a multiple
 // of four is filled with NaN coordinates: a NaN distance fails every `<`, so the loop needs no remainder code.
 //   K = 1 (chamfer)  no queue: compare and two selects per pair; for D = 3 that is 3 sub, 3 mul, 2 add, 1 cmp, 2 cndmask.
-//   K > 1            a sorted queue of KQ in {2, 4, 8, 16, 32} (distance, index) pairs in registers.  A candidate is looked at only
+//   K > 1            a sorted queue (knn_queue.h) of KQ in {2, 4, 8, 16, 32} (distance, index) pairs in registers.  A candidate is looked at only
 //                    when some lane of the wave beats its current worst (one ballot per pair); the insert is a fully unrolled,
 //                    branch-free shift: slot s takes its left neighbour where that one is larger than the candidate, else the
 //                    candidate where it itself is larger.  Strict comparisons and ascending j give the (dist, j) order: an equal
@@ -26,6 +26,7 @@
 // terms from knn_grad.h.
 #include "fixed_sum.h"
 #include "knn_grad.h"
+#include "knn_queue.h"
 #include "vec3.h"
 
 namespace p3d {
@@ -33,8 +34,6 @@ namespace {
 
 constexpr int kTile = P3D_KNN_TILE;
 static_assert(kTile % 4 == 0, "a tile is read four points at a time");
-
-__device__ __forceinline__ float pos_inf() { return __int_as_float(0x7f800000); }
 
 template <int NORM>
 __device__ __forceinline__ float coord_term(float x, float y) {
@@ -49,37 +48,6 @@ __device__ __forceinline__ float pair_dist(const float (&q)[D], const float (&y)
   for (int c = 1; c < D; ++c) s = s + coord_term<NORM>(q[c], y[c]);
   return s;
 }
-
-// The KQ smallest (distance, index) pairs seen so far, ascending; +inf / -1 where nothing has arrived yet.
-template <int KQ>
-struct Queue {
-  float d[KQ];
-  int j[KQ];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int s = 0; s < KQ; ++s) d[s] = pos_inf(), j[s] = -1;
-  }
-  __device__ __forceinline__ bool wants(float dn) const { return dn < d[KQ - 1]; }
-  // only lanes that want the candidate change anything: dn < d[KQ - 1] makes exactly one slot take it
-  __device__ __forceinline__ void insert(float dn, int jn) {
-#pragma unroll
-    for (int s = KQ - 1; s >= 0; --s) {
-      const bool shift = s > 0 && d[s > 0 ? s - 1 : 0] > dn;
-      const bool here = !shift && d[s] > dn;
-      const float dl = d[s > 0 ? s - 1 : 0];
-      const int jl = j[s > 0 ? s - 1 : 0];
-      d[s] = shift ? dl : (here ? dn : d[s]);
-      j[s] = shift ? jl : (here ? jn : j[s]);
-    }
-  }
-};
-
-template <>
-struct Queue<1> {
-  float d[1];
-  int j[1];
-  __device__ __forceinline__ void init() { d[0] = pos_inf(), j[0] = -1; }
-};
 
 // grid: N * blocks_per_cloud workgroups of one wave.  K <= KQ.  partials != NULL (KQ == 1 only): the chamfer terms of the wave.
 template <int D, int NORM, int KQ>

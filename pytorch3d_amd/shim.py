@@ -70,6 +70,12 @@ reference classes runs on them end to end:
     ops.points_to_volumes.add_pointclouds_to_volumes / add_points_features_to_volume_densities_features -> csrc/points_to_volumes.hip
                                                                  as one autograd node (ordered sum under the strict deterministic
                                                                  flag); CPU tensors go to this package's torch formulation
+    ops.points_normals.estimate_pointcloud_normals / estimate_pointcloud_local_coord_frames -> csrc/point_frames.hip: neighbours,
+                                                                 covariances, the reference's symeig3x3 and its sign votes in one
+                                                                 launch, nothing of size K per point in memory; Pointclouds.
+                                                                 estimate_normals comes here through `ops`; K > 64, float64, CPU
+                                                                 tensors, eigh and inputs that require grad go to this package's
+                                                                 torch formulation
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -378,6 +384,46 @@ def patch_reference_python():
     _patch_sample_points()
     _patch_fps_ball()
     _patch_points_to_volumes()
+    _patch_points_normals()
+
+
+def _patch_points_normals():
+    """pytorch3d.ops.points_normals.estimate_pointcloud_normals / estimate_pointcloud_local_coord_frames -> this package's
+    functions, in every module that copied the names (pytorch3d.ops; Pointclouds.estimate_normals resolves
+    `ops.estimate_pointcloud_normals` at call time).  float32 GPU clouds with neighborhood_size <= 64, the symeig workaround and no
+    gradient asked for take csrc/point_frames.hip, everything else OUR torch formulation.  PATCH_CALLS counts the kernel calls as
+    fused and the formulation as fallbacks."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".points_normals")
+    try:  # every module that copied the names must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.ops.points_normals")
+        importlib.import_module("pytorch3d.ops")
+    except ImportError:  # a reference checkout without the module: nothing to patch
+        return
+
+    def took_kernel(pointclouds, neighborhood_size, use_symeig_workaround):
+        return ours.kernel_path(ours._clouds(pointclouds)[0], neighborhood_size, use_symeig_workaround)
+
+    def estimate_pointcloud_normals(pointclouds, neighborhood_size=50, disambiguate_directions=True, *, use_symeig_workaround=True):
+        out = ours.estimate_pointcloud_normals(pointclouds, neighborhood_size, disambiguate_directions,
+                                               use_symeig_workaround=use_symeig_workaround)
+        _count("estimate_pointcloud_normals", took_kernel(pointclouds, neighborhood_size, use_symeig_workaround))  # (a call that raised is not counted)
+        return out
+
+    def estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size=50, disambiguate_directions=True, *,
+                                               use_symeig_workaround=True):
+        out = ours.estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size, disambiguate_directions,
+                                                          use_symeig_workaround=use_symeig_workaround)
+        _count("estimate_pointcloud_local_coord_frames", took_kernel(pointclouds, neighborhood_size, use_symeig_workaround))
+        return out
+
+    for orig, new in ((ref.estimate_pointcloud_normals, estimate_pointcloud_normals),
+                      (ref.estimate_pointcloud_local_coord_frames, estimate_pointcloud_local_coord_frames)):
+        new.__doc__ = getattr(orig, "__doc__", None)
+        new.__wrapped__ = orig
+        new.__p3d_amd__ = True
+        _replace_everywhere(orig, new)
 
 
 def _patch_points_to_volumes():
