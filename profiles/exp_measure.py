@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Measure build-flag variants of the two headline kernels in ONE process, on the bench batch (BASELINE configs[2]).
 
-    python profiles/exp_measure.py [--iters 40] [--batch 64] name=path/to/libp3d_<name>.so ...
+    python profiles/exp_measure.py [--iters 40] [--batch 64] [--face-pre] name=path/to/libp3d_<name>.so ...
 
 Every variant library is opened with ctypes next to the product library and driven through the C ABI directly
 (p3d_rasterize_meshes_ex, p3d_rasterize_meshes_backward_ex) on the same device buffers; per variant:
@@ -64,7 +64,9 @@ def main():
     ap.add_argument("--image-size", type=int, default=512)
     ap.add_argument("--faces-per-pixel", type=int, default=8)
     ap.add_argument("--torus-div", type=float, default=1.0, help="hetero_batch torus_div: 1.0 = SURVEY 8(d) config 3 as written (the bench headline), 1.5 = the lighter batch of rounds 1-3")
-    ap.add_argument("variants", nargs="*")
+    ap.add_argument("--face-pre", action="store_true", help="the backward makes and reads the per-face records (P3D_BWD_MAKE_FACE_PRE): the kernel "
+                    "the renderer and bench.py run at K = 4 / 8, not the per-sample-reciprocal one")
+    ap.add_argument("variants", nargs="*", help="name=path; a library may be named several times (parent1=.. new1=.. parent2=..) to alternate")
     args = ap.parse_args()
 
     import _util as U
@@ -93,6 +95,7 @@ def main():
                 torch.empty((B, H, H, K, 3), device=d), torch.empty((B, H, H, K), device=d))
 
     cover = torch.empty((B, (H + 15) // 16, (H + 15) // 16), dtype=torch.int32, device=d)
+    pre = torch.empty((F, 4), device=d) if args.face_pre else None
     bws = torch.empty((int(_lib.load().p3d_rasterize_meshes_backward_workspace_bytes(B, H, H)),), dtype=torch.uint8, device=d)
 
     def run(lib, out, gv, ws):
@@ -101,8 +104,9 @@ def main():
                                                  bin_size, M, 1, 1, 0, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
                                                  out[3].data_ptr(), cover.data_ptr(), 0, ws.data_ptr(), ws.numel(), stream)
         assert rc == 0, rc
-        rc = lib.p3d_rasterize_meshes_backward_ex(fv.data_ptr(), fp.data_ptr(), None, out[0].data_ptr(), gz.data_ptr(), gb.data_ptr(),
-                                                  gd.data_ptr(), cover.data_ptr(), F, V, B, H, H, K, 1, 1, 0, gv.data_ptr(), bws.data_ptr(),
+        rc = lib.p3d_rasterize_meshes_backward_ex(fv.data_ptr(), fp.data_ptr(), pre.data_ptr() if pre is not None else None, out[0].data_ptr(),
+                                                  gz.data_ptr(), gb.data_ptr(), gd.data_ptr(), cover.data_ptr(), F, V, B, H, H, K, 1, 1,
+                                                  _lib.BWD_MAKE_FACE_PRE if pre is not None else 0, gv.data_ptr(), bws.data_ptr(),
                                                   bws.numel(), stream)
         assert rc == 0, rc
 

@@ -329,6 +329,27 @@ __global__ __launch_bounds__(256) void face_pre_kernel(const float* __restrict__
   }
 }
 
+// Build-time switches of the K = 4 / 8 configuration, for A/B variant builds (profiles/ab_variant.py); the defaults are the product
+// (profiles/mesh_bwd_queue_mi355x.txt has the sweep they come from).
+#ifndef P3D_BWD_WAVES
+#define P3D_BWD_WAVES 7    // waves per SIMD of the kernels that read the per-face records
+#endif
+#ifndef P3D_BWD_QUEUE
+#define P3D_BWD_QUEUE 24   // entries of their survivor queue; 0: every step goes to the table
+#endif
+#ifndef P3D_BWD_SLOTS
+#define P3D_BWD_SLOTS 108  // their table slots
+#endif
+#ifndef P3D_BWD_QUEUE6
+#define P3D_BWD_QUEUE6 48  // the same for the K = 4 / 8 kernels without the records (six waves per SIMD)
+#endif
+#ifndef P3D_BWD_SLOTS6
+#define P3D_BWD_SLOTS6 108
+#endif
+#ifndef P3D_BWD_PACKED
+#define P3D_BWD_PACKED 1   // 44-byte table slots
+#endif
+
 template <int KT, bool PRE = false>
 struct RowsCfg {
   // Round 6: with the per-face reciprocals gathered (PRE) the K = 8 / K = 4 kernels fit 73 registers, and seven waves per SIMD with
@@ -336,12 +357,18 @@ struct RowsCfg {
   // -> 0.837 / 0.853 / 0.844 ms alternating on one box, profiles/r06/c42; the light batch 0.555 -> 0.532).  Round 4 had tried seven
   // waves on the kernel of its day: +3..5 % on config 3, -6 % on the light batch, not taken.
   static constexpr bool kSeven = PRE && KT <= 8;
-  static constexpr int kWaves = KT >= 16 ? 5 : (kSeven ? 7 : 6);     // waves per SIMD the kernel is built for (512 / kWaves registers)
-  // 4 waves x kSlots x 56 B of LDS per workgroup (a multiple of 4: bucket probing).  The LDS, not the 70 registers, is what
-  // holds K = 8 at six waves per SIMD: with 100 slots (seven waves) the launch measured 1.036 -> 0.98 / 1.00 ms on config 3 in
-  // two runs but 0.654 -> 0.694 on the light batch, 104 and 92 slots no change (profiles/r04/r04c10/bwd_occ*.txt): not taken.
-  // At eight waves (88 slots, 64 registers) the kernel spills and returns NaN -- the build refuses it.
-  static constexpr int kSlots = KT >= 16 ? 136 : (kSeven ? 100 : 116);
+  static constexpr int kWaves = KT >= 16 ? 5 : (kSeven ? P3D_BWD_WAVES : 6);     // waves per SIMD the kernel is built for (512 / kWaves registers)
+  // K = 4 / 8: the survivors of run_reduce wait in a wave-private LDS queue of kQueue entries (40 B each) and reach the table
+  // together (below); the table's slots are packed (wave_table.h: 44 B instead of 56 B each).  0: no queue.
+  static constexpr int kQueue = KT <= 8 ? (kSeven ? P3D_BWD_QUEUE : P3D_BWD_QUEUE6) : 0;
+  static constexpr bool kPacked = KT <= 8 && P3D_BWD_PACKED;
+  // 4 waves x (kSlots x 44 or 56 B + kQueue x 40 B) of LDS per workgroup (kSlots a multiple of 4: bucket probing).  A CU hands
+  // its 160 KB out in pieces of 1280 B: 18 of them (23040 B) per workgroup at seven workgroups per CU, 21 (26880 B) at six --
+  // a byte more and a workgroup less is resident (27136 B ran as FIVE: +6 % on the bench launch).  Slots and queue share that
+  // budget, and the slots are worth more than a long queue: 24 entries + 108 slots beat 48 + 84 and 64 + 72 at seven waves.
+  // The LDS, not the registers, is what holds K = 8 without the records at six waves per SIMD; at eight waves (64 registers)
+  // the kernel spills and returns NaN -- the build refuses it.
+  static constexpr int kSlots = KT >= 16 ? 136 : (kSeven ? P3D_BWD_SLOTS : P3D_BWD_SLOTS6);
   static constexpr int kPix = 64 / KT;                 // pixels per 64-sample step
 };
 
@@ -404,8 +431,12 @@ __global__ __launch_bounds__(256, (RowsCfg<KT, PRE>::kWaves)) void mesh_backward
   constexpr int SPR = KT / 4;  // steps per 16-pixel row segment
   constexpr int PIX = RowsCfg<KT>::kPix;
   static_assert(KT == 4 || KT == 8 || KT == 16 || KT == 32, "16 K samples per row segment, 64 per step");
-  using Table = WaveTable<9, RowsCfg<KT, PRE>::kSlots, TO_VERTS ? kCorners : kRows, true, true>;
-  __shared__ __align__(16) int s_table[4][Table::kLdsInts];
+  using Cfg = RowsCfg<KT, PRE>;
+  using Table = WaveTable<9, Cfg::kSlots, TO_VERTS ? kCorners : kRows, true, true, Cfg::kPacked>;
+  constexpr int QCAP = Cfg::kQueue;
+  static_assert(Table::kLdsInts % 4 == 0, "every wave's table starts on a 16-byte boundary");
+  __shared__ __align__(16) int s_table[4][Table::kLdsInts + 10 * QCAP];
+  static_assert((sizeof(s_table) + 1279) / 1280 * 1280 * Cfg::kWaves <= 160 * 1024, "kWaves workgroups do not fit the CU's LDS (1280-byte pieces)");
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -465,48 +496,96 @@ __global__ __launch_bounds__(256, (RowsCfg<KT, PRE>::kWaves)) void mesh_backward
   int rn = __builtin_ctz(todo), sn = 0;  // the next step: row, part of the row
   todo &= todo - 1;
   int f_nxt = e < seg ? (int)uniform_ptr(a.p2f + (area_base + (int64_t)rn * row_pitch))[eu] : -1;
+  // The survivor queue (QCAP > 0).  After run_reduce a third of the lanes still carry an entry (18-27 of 64 on the bench batch, in
+  // 9-13 distinct faces), and tab.add costs its ~180 wave-wide instructions whatever the number of live lanes.  So the survivors of a
+  // step are appended to a wave-private queue in LDS -- q_f[QCAP] faces, q_g[9][QCAP] partials, the appending lanes write
+  // consecutive entries of every plane -- and the table is called with as full a wave as there is: when a step's S survivors no
+  // longer fit, they stay in their lanes, the 64 - S free lanes take the newest queue entries, and all go to tab.add together
+  // (one call site for the overflowing step, a step that is too large for the queue, and the tail that empties the queue once the
+  // area's rows are done: there the step is empty).  cnt, S and every branch on them are wave-uniform.  One wave writes and reads
+  // the queue, in program order on the LDS; the wavefront-scope fences keep the compiler from reordering across them.
+  typedef __attribute__((address_space(3))) int LdsQInt;
+  typedef __attribute__((address_space(3))) float LdsQFloat;
+  [[maybe_unused]] LdsQInt* const q_f = (LdsQInt*)(s_table[w] + Table::kLdsInts);
+  [[maybe_unused]] LdsQFloat* const q_g = (LdsQFloat*)(s_table[w] + Table::kLdsInts + QCAP);
+  [[maybe_unused]] int cnt = 0;  // queue entries
 #pragma unroll 1
-  while (rn >= 0) {
-    const int r = rn, s = sn;
-    int f = f_nxt;
-    if (++sn == SPR) {
-      sn = 0;
-      rn = todo ? __builtin_ctz(todo) : -1;
-      todo &= todo - 1;  // (0 stays 0)
-    }
-    {
-      const int en = 64 * sn + e;
-      const auto* prow = uniform_ptr(a.p2f + (area_base + (int64_t)(rn < 0 ? 0 : rn) * row_pitch + 64 * sn));
-      f_nxt = (rn >= 0 && en < seg) ? (int)prow[eu] : -1;
-    }
-    if (__ballot(f >= 0) == 0) continue;  // wave-uniform: nothing rendered in these 64 samples
+  while (rn >= 0 || (QCAP > 0 && cnt > 0)) {
+    const bool tail = QCAP > 0 && rn < 0;  // the rows are done: empty the queue
+    int f = -1;
     FaceGrad g;
-    if (f >= 0) {
-      const int64_t rb = area_base + (int64_t)r * row_pitch + 64 * s;  // uniform
-      const auto* gzp = uniform_ptr(a.grad_zbuf + rb);
-      const auto* gdp = uniform_ptr(a.grad_dists + rb);
-      const auto* gbp = uniform_ptr(a.grad_bary + 3 * rb);
-      const float gz = gzp[eu], gd = gdp[eu];
-      const f3 gb = mk3(gbp[eu3], gbp[eu3 + 1u], gbp[eu3 + 2u]);
-      const float* q = a.face_verts + (int64_t)f * 9;
-      float pxs = px[0];
-#pragma unroll
-      for (int c = 1; c < SPR; ++c) pxs = s == c ? px[c] : pxs;
-      const f2 p = mk2(pxs, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py_rows), r)));
-      BwdFacePre pre = BwdFacePre();
-      if constexpr (PRE) {
-        const float4 r = a.face_pre[f];
-        pre.inv_area = r.x;
-        pre.inv_l01 = r.y;
-        pre.inv_l02 = r.z;
-        pre.inv_l12 = r.w;
+    if (!tail) {
+      const int r = rn, s = sn;
+      f = f_nxt;
+      if (++sn == SPR) {
+        sn = 0;
+        rn = todo ? __builtin_ctz(todo) : -1;
+        todo &= todo - 1;  // (0 stays 0)
       }
-      g = face_sample_bwd<PRE>(mk3(q[0], q[1], q[2]), mk3(q[3], q[4], q[5]), mk3(q[6], q[7], q[8]), p, gz, gb, gd, persp, clip, false, pre);
+      {
+        const int en = 64 * sn + e;
+        const auto* prow = uniform_ptr(a.p2f + (area_base + (int64_t)(rn < 0 ? 0 : rn) * row_pitch + 64 * sn));
+        f_nxt = (rn >= 0 && en < seg) ? (int)prow[eu] : -1;
+      }
+      if (__ballot(f >= 0) == 0) continue;  // wave-uniform: nothing rendered in these 64 samples
+      if (f >= 0) {
+        const int64_t rb = area_base + (int64_t)r * row_pitch + 64 * s;  // uniform
+        const auto* gzp = uniform_ptr(a.grad_zbuf + rb);
+        const auto* gdp = uniform_ptr(a.grad_dists + rb);
+        const auto* gbp = uniform_ptr(a.grad_bary + 3 * rb);
+        const float gz = gzp[eu], gd = gdp[eu];
+        const f3 gb = mk3(gbp[eu3], gbp[eu3 + 1u], gbp[eu3 + 2u]);
+        const float* q = a.face_verts + (int64_t)f * 9;
+        float pxs = px[0];
+#pragma unroll
+        for (int c = 1; c < SPR; ++c) pxs = s == c ? px[c] : pxs;
+        const f2 p = mk2(pxs, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(py_rows), r)));
+        BwdFacePre pre = BwdFacePre();
+        if constexpr (PRE) {
+          const float4 r = a.face_pre[f];
+          pre.inv_area = r.x;
+          pre.inv_l01 = r.y;
+          pre.inv_l02 = r.z;
+          pre.inv_l12 = r.w;
+        }
+        g = face_sample_bwd<PRE>(mk3(q[0], q[1], q[2]), mk3(q[3], q[4], q[5]), mk3(q[6], q[7], q[8]), p, gz, gb, gd, persp, clip, false, pre);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 9; ++j) g.g[j] = 0.0f;  // read by the neighbours' shifts, never added
+      }
+      run_reduce<PIX>(f, g.g, lane);
     } else {
 #pragma unroll
-      for (int j = 0; j < 9; ++j) g.g[j] = 0.0f;  // read by the neighbours' shifts, never added
+      for (int j = 0; j < 9; ++j) g.g[j] = 0.0f;
     }
-    run_reduce<PIX>(f, g.g, lane);
+    if constexpr (QCAP > 0) {
+      const unsigned long long m = __ballot(f >= 0);
+      const int S = __popcll(m);
+      if (!tail && cnt + S <= QCAP) {
+        if (f >= 0) {
+          const int i = cnt + mask_rank(m);  // < QCAP
+          q_f[i] = f;
+#pragma unroll
+          for (int j = 0; j < 9; ++j) q_g[j * QCAP + i] = g.g[j];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        cnt += S;
+        continue;
+      }
+      const int take = min(cnt, 64 - S);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (f < 0) {
+        const int rk = mask_rank(~m);
+        if (rk < take) {
+          const int i = cnt - 1 - rk;  // in [cnt - take, cnt)
+          f = q_f[i];
+#pragma unroll
+          for (int j = 0; j < 9; ++j) g.g[j] = q_g[j * QCAP + i];
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (the next appends overwrite what was read)
+      cnt -= take;
+    }
     tab.add(a.grad_fv, lane, f, g.g);
   }
   if (tab.used > 0) tab.flush(a.grad_fv, lane);

@@ -39,10 +39,17 @@ enum { kRows = 0, kPlanar = 1, kChunk = 2, kCorners = 3, kSplit = 4 };
 // SLOTS % 4 == 0).  A step's probe is a chain of dependent LDS round trips whose length is that of the longest chain among
 // the wave's primitives -- a fresh primitive in a table that is 3/4 full walks ~8 slots -- and in the rasterizer's
 // backward that chain was the largest single part of the table's cost (profiles/r03/bwd_ablate.txt).
-template <int NV, int SLOTS, int LAYOUT = kRows, bool SPILL = false, bool BUCKET = false>
+// PACKED (NV % 4 != 0): a slot's row is NV floats, not NV rounded up to whole 16-byte chunks -- NV = 9: 44 instead of 56 bytes per
+// slot with its key and owner, i.e. 27 % more slots in the same LDS.  Rows then start at 4-byte alignment only, and the head update
+// moves them as 4-byte-aligned LDS operations (ds_read2_b32 / ds_write2_b32 pairs: the compiler forms ds_read_b96 / b128 for gfx950
+// at 16-byte alignment only); the odd row stride spreads the rows of different slots
+// over all 64 banks, though the two-dword operations keep the bank-conflict counter where it was.
+template <int NV, int SLOTS, int LAYOUT = kRows, bool SPILL = false, bool BUCKET = false, bool PACKED = false>
 struct WaveTable {
   static_assert(!BUCKET || SLOTS % 4 == 0, "bucket probing reads the keys as aligned groups of four");
-  static constexpr int kStride = (NV + 3) / 4 * 4;  // floats per slot: values are moved as 16-byte chunks
+  static constexpr bool kPackedRows = PACKED && NV % 4 != 0;
+  static constexpr int kStride = kPackedRows ? NV : (NV + 3) / 4 * 4;  // floats per slot: values are moved as 16-byte chunks unless packed
+  static_assert(!BUCKET || (SLOTS * kStride) % 4 == 0, "the keys follow the values and are read as 16-byte quads");
   // The table is emptied before a step when it is fuller than this.  A step adds up to 64 primitives, so by default 64
   // slots stay in reserve and the table cannot overflow.  SPILL: no reserve -- the table fills up to 3/4 between
   // steps, a lane that finds no free slot for its primitive during a step sends its values straight to memory with
@@ -260,7 +267,19 @@ struct WaveTable {
         prev = prev >= 0 ? pp : -1;
       }
     }
-    if (head) {
+    if (kPackedRows && head) {
+      typedef __attribute__((address_space(3))) float LdsFloat;
+      LdsFloat* row = (LdsFloat*)vals + slot * kStride;
+      float t[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) t[j] = 0.0f;
+      if (!fresh) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) t[j] = row[j];
+      }
+#pragma unroll
+      for (int j = 0; j < NV; ++j) row[j] = t[j] + g[j];
+    } else if (head) {
       float4* row = reinterpret_cast<float4*>(vals + slot * kStride);
 #pragma unroll
       for (int c = 0; c < kStride / 4; ++c) {
