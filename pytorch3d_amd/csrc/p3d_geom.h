@@ -480,6 +480,41 @@ struct TriGrad {
 
 P3D_HD f2 add2(f2 a, f2 b) { return mk2(a.x + b.x, a.y + b.y); }
 
+// Two floats in one 64-bit register pair, for the PACKED form of the per-sample gradient (face_sample_bwd<PRE, true>): the K = 4 / 8
+// backward runs at the vector issue rate, where a fused multiply-add costs about 1.9 ns of a SIMD against 1.0 ns for a multiply, an
+// add or a subtract (profiles/microbench/valu_classes_mi355x.txt) and v_pk_fma_f32 does two for the price of one.  Only FMAs are
+// packed -- two packed multiplies or adds cost what the two scalar ones do; components are read and written as scalars (.x, .y), which
+// costs nothing as long as the register allocator is free to place them.  On the host, and with -DP3D_BWD_PK=0, the type is a plain
+// struct and pk_fma is a multiply and an add per component: the same expression trees as the scalar form.
+#ifndef P3D_BWD_PK
+#define P3D_BWD_PK 1
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && P3D_BWD_PK
+typedef float pk2 __attribute__((ext_vector_type(2)));
+P3D_HD pk2 pk_mk(float x, float y) {
+  pk2 r = {x, y};
+  return r;
+}
+P3D_HD pk2 pk_fma(pk2 a, pk2 b, pk2 c) { return __builtin_elementwise_fma(a, b, c); }
+#else
+struct pk2 {
+  float x, y;
+};
+P3D_HD pk2 pk_mk(float x, float y) {
+  pk2 r;
+  r.x = x;
+  r.y = y;
+  return r;
+}
+P3D_HD pk2 pk_fma(pk2 a, pk2 b, pk2 c) {
+#if defined(__clang__)
+#pragma clang fp contract(fast)
+#endif
+  return pk_mk(a.x * b.x + c.x, a.y * b.y + c.y);
+}
+#endif
+P3D_HD pk2 pk_all(float s) { return pk_mk(s, s); }
+
 // e: the three edge functions of p, inv_area = 1 / bary_area, inv_area2 = 1 / area^2 -- formed by the caller (face_sample_bwd), once
 P3D_HD TriGrad bary_coords_bwd(f2 p, f2 v0, f2 v1, f2 v2, f3 g, f3 e, float inv_area, float inv_area2) {
 #if defined(__clang__)
@@ -502,6 +537,31 @@ P3D_HD TriGrad bary_coords_bwd(f2 p, f2 v0, f2 v1, f2 v2, f3 g, f3 e, float inv_
   return r;
 }
 
+// The same sums with the (x, y) pairs in pk2 and every term but the first of a sum as one packed FMA: nine packed instructions for
+// the 24 multiplies and 12 adds above.  With P_k = (p.y - v_k.y, v_k.x - p.x) and E_jk = (v_k.y - v_j.y, v_j.x - v_k.x) the twelve
+// partials of the four edge functions are +-G * P_k and G_area * E_jk (x - y == -(y - x) exactly, so the signs move into the scalar
+// factor without changing a bit); the sums keep the order of the scalar form: (numerator, numerator), then the area's term.
+P3D_HD TriGrad bary_coords_bwd_pk(f2 p, f2 v0, f2 v1, f2 v2, f3 g, f3 e, float inv_area, float inv_area2) {
+#if defined(__clang__)
+#pragma clang fp contract(fast)  // gradient-only arithmetic (tolerance-gated): let mul+add fuse into FMA
+#endif
+  const float G0 = g.x * inv_area, G1 = g.y * inv_area, G2 = g.z * inv_area;
+  const float GA = -(g.x * e.x + g.y * e.y + g.z * e.z) * inv_area2;
+  const pk2 P0 = pk_mk(p.y - v0.y, v0.x - p.x), P1 = pk_mk(p.y - v1.y, v1.x - p.x), P2 = pk_mk(p.y - v2.y, v2.x - p.x);
+  const pk2 E01 = pk_mk(v1.y - v0.y, v0.x - v1.x), E12 = pk_mk(v2.y - v1.y, v1.x - v2.x), E20 = pk_mk(v0.y - v2.y, v2.x - v0.x);
+  const float nG0 = -G0, nG1 = -G1, nG2 = -G2;
+  // d0 = (n1.db + n2.da) + ar.da,  d1 = (n0.da + n2.db) + ar.db,  d2 = (n0.db + n1.da) + ar.dp
+  const pk2 d0 = pk_fma(pk_all(GA), E12, pk_fma(pk_all(G2), P1, pk_mk(nG1 * P2.x, nG1 * P2.y)));
+  const pk2 d1 = pk_fma(pk_all(GA), E20, pk_fma(pk_all(nG2), P0, pk_mk(G0 * P2.x, G0 * P2.y)));
+  const pk2 d2 = pk_fma(pk_all(GA), E01, pk_fma(pk_all(G1), P0, pk_mk(nG0 * P1.x, nG0 * P1.y)));
+  TriGrad r;
+  r.d0 = mk2(d0.x, d0.y);
+  r.d1 = mk2(d1.x, d1.y);
+  r.d2 = mk2(d2.x, d2.y);
+  return r;
+}
+
+template <bool PK = false>
 P3D_HD f3 bary_clip_bwd(f3 b, f3 g) {
 #if defined(__clang__)
 #pragma clang fp contract(fast)  // gradient-only arithmetic (tolerance-gated): let mul+add fuse into FMA
@@ -533,6 +593,10 @@ P3D_HD f3 bary_clip_bwd(f3 b, f3 g) {
   const float c0 = live != 0.0f ? (w1 + w2) * inv_s2 : inv;
   const float c1 = live != 0.0f ? (w0 + w2) * inv_s2 : inv;
   const float c2 = live != 0.0f ? (w0 + w1) * inv_s2 : inv;
+  if (PK) {  // the first two sums side by side: (g.x c0, g.y c1) + (g.y q1, g.x q0) + g.z q2 -- two packed FMAs for four
+    const pk2 s01 = pk_fma(pk_all(g.z), pk_all(q2), pk_fma(pk_mk(g.y, g.x), pk_mk(q1, q0), pk_mk(g.x * c0, g.y * c1)));
+    return mk3(m0 * s01.x, m1 * s01.y, m2 * (g.z * c2 + g.x * q0 + g.y * q1));
+  }
   return mk3(m0 * (g.x * c0 + g.y * q1 + g.z * q2), m1 * (g.y * c1 + g.x * q0 + g.z * q2), m2 * (g.z * c2 + g.x * q0 + g.y * q1));
 }
 
@@ -573,7 +637,7 @@ P3D_HD BwdFacePre bwd_face_pre_make(f3 v0, f3 v1, f3 v2) {
   return r;
 }
 
-template <bool PRE = false>
+template <bool PRE = false, bool PK = false>
 P3D_HD FaceGrad face_sample_bwd(f3 v0, f3 v1, f3 v2, f2 p, float g_zbuf, f3 g_bary, float g_dist,
                                 bool perspective_correct, bool clip_bary, bool clip_bwd_on_corrected,
                                 BwdFacePre pre = BwdFacePre()) {
@@ -638,7 +702,15 @@ P3D_HD FaceGrad face_sample_bwd(f3 v0, f3 v1, f3 v2, f2 p, float g_zbuf, f3 g_ba
       degenerate = l2 <= 1e-8f;
       t = sat01(qdiv<true>(dot, l2));
     }
-    const float qx = (es[i].x + t * bax) - p.x, qy = (es[i].y + t * bay) - p.y;
+    float qx, qy;
+    if (PK) {  // the closest point's two coordinates: one packed FMA
+      const pk2 c = pk_fma(pk_all(t), pk_mk(bax, bay), pk_mk(es[i].x, es[i].y));
+      qx = c.x - p.x;
+      qy = c.y - p.y;
+    } else {
+      qx = (es[i].x + t * bax) - p.x;
+      qy = (es[i].y + t * bay) - p.y;
+    }
     const float px = p.x - ee[i].x, py = p.y - ee[i].y;
     et[i] = t;
     ex[i] = qx;
@@ -661,23 +733,54 @@ P3D_HD FaceGrad face_sample_bwd(f3 v0, f3 v1, f3 v2, f2 p, float g_zbuf, f3 g_ba
 
   // ---- barycentrics: zbuf = sum bc_i z_i, so its upstream joins the barycentrics' (rasterize_meshes.cu:486-561)
   f3 gb = mk3(g_bary.x + g_zbuf * z0, g_bary.y + g_zbuf * z1, g_bary.z + g_zbuf * z2);
-  if (clip_bary) gb = bary_clip_bwd(clip_bwd_on_corrected ? bp : bw, gb);
+  if (clip_bary) gb = bary_clip_bwd<PK>(clip_bwd_on_corrected ? bp : bw, gb);
   float dz0 = 0.0f, dz1 = 0.0f, dz2 = 0.0f;
   if (perspective_correct) {
     // geometry_utils.cuh:200-228 on the numerators and the reciprocal formed above
     const float gd_top = -t0 * gb.x - t1 * gb.y - t2 * gb.z;
     const float gdn = gd_top * (inv_denom * inv_denom);
-    const float g0 = gdn + gb.x * inv_denom;
-    const float g1 = gdn + gb.y * inv_denom;
+    float g0, g1;
+    if (PK) {
+      const pk2 g01 = pk_fma(pk_mk(gb.x, gb.y), pk_all(inv_denom), pk_all(gdn));
+      g0 = g01.x;
+      g1 = g01.y;
+    } else {
+      g0 = gdn + gb.x * inv_denom;
+      g1 = gdn + gb.y * inv_denom;
+    }
     const float g2p = gdn + gb.z * inv_denom;
     dz0 = g1 * bw.y * z2 + g2p * bw.z * z1;
     dz1 = g0 * bw.x * z2 + g2p * bw.z * z0;
     dz2 = g0 * bw.x * z1 + g1 * bw.y * z0;
     gb = mk3(g0 * z1 * z2, g1 * z0 * z2, g2p * z0 * z1);
   }
-  const TriGrad dbw = bary_coords_bwd(p, a, b, c, gb, e, inv_area, inv_area2);
+  const TriGrad dbw = PK ? bary_coords_bwd_pk(p, a, b, c, gb, e, inv_area, inv_area2) : bary_coords_bwd(p, a, b, c, gb, e, inv_area, inv_area2);
 
   FaceGrad r;
+  if (PK) {
+    // The distance's share joins as one packed FMA per vertex: the selection picks each vertex's scalar WEIGHT (ga, gb_ or 0) instead
+    // of its vector (da, db or zero) -- four selects for eight, no products to form first.  A weight of 0 multiplies the closest
+    // point's offset (sx, sy), which is finite whenever the closest edge's distance is; with no closest edge (sel == 3: NaN distances
+    // on all three edges, i.e. a NaN pixel or two NaN vertices) every barycentric partial is NaN already.
+    const float w0 = sel <= 1 ? ga : 0.0f;
+    const float w1 = sel == 0 ? gb_ : (sel == 2 ? ga : 0.0f);
+    const float w2 = (sel == 1 || sel == 2) ? gb_ : 0.0f;
+    const pk2 sxy = pk_mk(sx, sy);
+    const pk2 r0 = pk_fma(pk_all(w0), sxy, pk_mk(dbw.d0.x, dbw.d0.y));
+    const pk2 r1 = pk_fma(pk_all(w1), sxy, pk_mk(dbw.d1.x, dbw.d1.y));
+    const pk2 r2 = pk_fma(pk_all(w2), sxy, pk_mk(dbw.d2.x, dbw.d2.y));
+    const pk2 z01 = pk_fma(pk_all(g_zbuf), pk_mk(bc.x, bc.y), pk_mk(dz0, dz1));
+    r.g[0] = r0.x;
+    r.g[1] = r0.y;
+    r.g[2] = z01.x;
+    r.g[3] = r1.x;
+    r.g[4] = r1.y;
+    r.g[5] = z01.y;
+    r.g[6] = r2.x;
+    r.g[7] = r2.y;
+    r.g[8] = g_zbuf * bc.z + dz2;
+    return r;
+  }
   r.g[0] = dbw.d0.x + dd0.x;
   r.g[1] = dbw.d0.y + dd0.y;
   r.g[2] = g_zbuf * bc.x + dz0;

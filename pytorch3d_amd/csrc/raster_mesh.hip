@@ -34,6 +34,10 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+// A/B switch of profiles/mesh_valu_diet_mi355x.txt (profiles/ab_variant.py -DP3D_STAGE_RANGE_INDEX=0 builds the form before it)
+#ifndef P3D_STAGE_RANGE_INDEX
+#define P3D_STAGE_RANGE_INDEX 1  // stage_chunk: the pixel-range counts as indices (estimate + one true centre) instead of 64 compares
+#endif
 
 // Probe build (-DP3D_PROBE_CHAIN through P3D_EXTRA_FLAGS into a library of its own, never the product): where the life of an active
 // tile's wave goes.  Lane 0 of every wave of one workgroup in eight (single-chunk tiles of the plan walk) notes the shader clock at
@@ -733,8 +737,49 @@ __device__ __forceinline__ int stage_chunk(const MeshArgs& a, const StageLds& l,
   // this wave stages a face"): every lane of the wave is active here.  Inside `if (has)` the lanes past the end of the list are not,
   // and a lane table may only be read where its source lanes cannot have been restored under a narrower exec mask
   // (profiles/r06/spill_root_cause.md: what cost round 4's spilling kernels their last faces).  Lanes without a face compare zeros.
+  //
+  // The counts are INDICES: the 16 centres of an axis increase strictly, so #(centre < lo) is the first index whose centre is not
+  // below lo.  Counting it took 32 v_readlane and 64 compare + add pairs per wave and chunk; instead each lane estimates the index
+  // from the axis' first centre and the reciprocal pixel pitch, fetches the ONE true centre at the
+  // rounded estimate r from `pxy` (ds_bpermute) and lets the strict comparison with it decide between r and r + 1.  With u the
+  // real number at which the (affine) centre function equals the edge, the count is ceil(u) resp. floor(u) + 1 clamped to
+  // [0, 16]; |r - estimate| <= 0.5, so both candidates are right as long as |estimate - u| < 0.5.  What the estimate is off by:
+  // the rounding of the 16 centres (each within 3 ulp of the axis' half range, pix_to_ndc) and of the pitch taken from fifteen
+  // of them, together below 2^-20 * S pixels on an axis of S pixels, plus 16 * 2^-22 from the estimate's own two roundings --
+  // under 0.1 for every image side up to 2^16.  Nothing else of the estimate is trusted: the count comes out of a comparison with
+  // a true centre.  Edges far outside clamp to r = 0 / 15, where the comparison gives 0 or 16 (-inf / +inf included).  A NaN edge
+  // fails every comparison: the clamps send it to the end at which "no centre is outside" (count 0), as the counting loop did.
   int xb = 0, xa = 0, yb = 0, ya = 0;  // centres below the box's low edge / above its high edge
   if (__ballot(has) != 0) {
+#if P3D_STAGE_RANGE_INDEX
+    // (all sixteen centres of an axis exist as numbers, also those of columns / rows past the image's edge; the reciprocal pitch is
+    // formed here, per chunk, from four lane reads -- behind an empty asm: left alone, the compiler forms it once per wave and keeps
+    // it, a register more in every instantiation and a spill in the K = 8 kernel with tie marks)
+    float pxy = l.pxy;
+    asm volatile("" : "+v"(pxy));
+    const float x0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pxy), 0));
+    const float y0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(pxy), 16));
+    const float inv_dx = 15.0f * __builtin_amdgcn_rcpf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(pxy), 15)) - x0);
+    const float inv_dy = 15.0f * __builtin_amdgcn_rcpf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(pxy), 31)) - y0);
+    // (fmaxf / fminf return the operand that is not NaN)
+    const int rxl = (int)rintf(fminf(fmaxf((fs.xlo - x0) * inv_dx, 0.0f), 15.0f));
+    const int rxh = (int)rintf(fmaxf(fminf((fs.xhi - x0) * inv_dx, 15.0f), 0.0f));
+    const float cxl = __int_as_float(__builtin_amdgcn_ds_bpermute(rxl << 2, __float_as_int(pxy)));
+    const float cxh = __int_as_float(__builtin_amdgcn_ds_bpermute(rxh << 2, __float_as_int(pxy)));
+    xb = rxl + (cxl < fs.xlo ? 1 : 0);
+    xa = 15 - rxh + (cxh > fs.xhi ? 1 : 0);
+    cm = range_mask16(xb, xa) & l.valid_c;
+    // (one axis after the other, each folded into its mask at once: scheduled together, the indices and centres of both axes cost
+    // the K = 8 kernel with tie marks a register it does not have)
+    __builtin_amdgcn_sched_barrier(0);
+    const int ryl = (int)rintf(fminf(fmaxf((fs.ylo - y0) * inv_dy, 0.0f), 15.0f));
+    const int ryh = (int)rintf(fmaxf(fminf((fs.yhi - y0) * inv_dy, 15.0f), 0.0f));
+    const float cyl = __int_as_float(__builtin_amdgcn_ds_bpermute((16 + ryl) << 2, __float_as_int(pxy)));
+    const float cyh = __int_as_float(__builtin_amdgcn_ds_bpermute((16 + ryh) << 2, __float_as_int(pxy)));
+    yb = ryl + (cyl < fs.ylo ? 1 : 0);
+    ya = 15 - ryh + (cyh > fs.yhi ? 1 : 0);
+    rm = range_mask16(yb, ya) & l.valid_r;
+#else
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
       const float xs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l.pxy), c));
@@ -744,10 +789,11 @@ __device__ __forceinline__ int stage_chunk(const MeshArgs& a, const StageLds& l,
       yb += ys < fs.ylo ? 1 : 0;
       ya += ys > fs.yhi ? 1 : 0;
     }
-  }
-  if (has) {
     cm = range_mask16(xb, xa) & l.valid_c;
     rm = range_mask16(yb, ya) & l.valid_r;
+#endif
+  }
+  if (has) {
     keep = !fs.reject && cm != 0 && rm != 0;  // some pixel centre of the tile is inside the box
     if (keep && prune)
       keep = !rect_cannot_hit(mk2(v0.x, v0.y), mk2(v1.x, v1.y), mk2(v2.x, v2.y), tile.x0, tile.x1, tile.y0, tile.y1, a.sqrt_blur);
@@ -789,8 +835,11 @@ __device__ __forceinline__ int stage_chunk(const MeshArgs& a, const StageLds& l,
     // that bound can never admit the face.  Not applicable when barycentrics are unclipped (pz may
     // leave [zmin, zmax]), when the face has a clipped neighbour (it may REPLACE a queued entry,
     // rasterize_meshes.cu:186-215), or for depths so small that bary_clip's 1e-5 floor could bite.
+    // Nor for a face with a NaN x or y (its area, and so fr.rd_area, is NaN): its barycentrics are NaN at every pixel, the clip
+    // turns all three into 0 and the sample's depth is 0, not a combination of the vertex depths -- the reference admits it
+    // within the blur radius of an edge between two sound vertices, in front of everything.
     const float zmin = min3(v0.z, v1.z, v2.z);
-    l.zc[pos] = (clip && nb == -1 && zmin >= 1e-3f) ? zmin * 0.999998f : -INFINITY;
+    l.zc[pos] = (clip && nb == -1 && zmin >= 1e-3f && fr.rd_area == fr.rd_area) ? zmin * 0.999998f : -INFINITY;
   }
   // also the barrier that publishes the staged records
   *general = __syncthreads_or(gen ? 1 : 0) != 0;

@@ -548,7 +548,8 @@ __global__ __launch_bounds__(256, (RowsCfg<KT, PRE>::kWaves)) void mesh_backward
           pre.inv_l02 = r.z;
           pre.inv_l12 = r.w;
         }
-        g = face_sample_bwd<PRE>(mk3(q[0], q[1], q[2]), mk3(q[3], q[4], q[5]), mk3(q[6], q[7], q[8]), p, gz, gb, gd, persp, clip, false, pre);
+        // (PRE && PC && QCAP > 0: the K = 4 / 8 kernel of the renderer takes the packed form of the arithmetic, p3d_geom.h: pk2)
+        g = face_sample_bwd<PRE, P3D_BWD_PK && PRE && PC && (RowsCfg<KT, PRE>::kQueue > 0)>(mk3(q[0], q[1], q[2]), mk3(q[3], q[4], q[5]), mk3(q[6], q[7], q[8]), p, gz, gb, gd, persp, clip, false, pre);
       } else {
 #pragma unroll
         for (int j = 0; j < 9; ++j) g.g[j] = 0.0f;  // read by the neighbours' shifts, never added
