@@ -949,6 +949,34 @@ int64_t p3d_point_frames_workgroups(int64_t N, int64_t P);
 int p3d_point_frames(const float* points, const int64_t* lengths, int64_t N, int64_t P, int D, int K, unsigned flags,
                      float* curvatures, float* frames, float* cov_out, int64_t* idx_out, p3d_stream_t stream);
 
+/* ---- box3d_overlap: intersection volume and IoU of oriented 3D boxes (csrc/box3d.hip) ---- */
+
+/* IoUBox3D by the contract of the reference's CPU operator (iou_box3d/iou_box3d_cpu.cpp over iou_utils.h): for every pair the 12
+ * triangles of each box are clipped through the 6 inward planes of the other, box-2 fragments coplanar with a box-1 fragment of area
+ * > 1e-4 are dropped, and vol = sum |v0 . (v1 x v2)| / 6 about the mean of the face centres, iou = vol / (vol1 + vol2 - vol); a pair
+ * without fragments is exactly (0, 0).  No list is capped and no pair truncated.  There is no backward.
+ * boxes1 (N,8,3), boxes2 (M,8,3) contiguous f32, corners in the reference's order; vol, iou (N,M) f32, every entry written.
+ *
+ * p3d_iou_box3d (device): one wave per pair with its lists in LDS, lds_capacity triangles per list (P3D_BOX3D_LDS_CAPACITY is the
+ * default; tests pass less; outside [12, P3D_BOX3D_LDS_CAPACITY]: P3D_ERR_INVALID_ARG).  A pair whose list would pass it is appended
+ * to a list in the workspace and redone by a second launch, always issued, with lists of P3D_BOX3D_SLAB_CAPACITY = 12 * 2^6
+ * triangles -- more than a pair can produce -- in the workspace.  After the call the first 4 bytes of the workspace hold the number
+ * of such pairs (u32).  Results do not depend on lds_capacity, the run or the stream.  The first launch is at most
+ * P3D_BOX3D_MAX_GROUPS workgroups of P3D_BOX3D_WAVES_PER_GROUP waves and loops beyond that; the second is min(N * M,
+ * P3D_BOX3D_SLAB_WAVES) waves.  workspace: p3d_iou_box3d_workspace_bytes(N, M) bytes, 256-byte aligned (smaller: P3D_ERR_WORKSPACE).
+ * N * M > INT32_MAX: P3D_ERR_UNSUPPORTED.  N or M of 0: P3D_OK without a launch.  No host sync.
+ *
+ * p3d_iou_box3d_host: the same contract on host pointers, a serial loop over the pairs on the same geometry functions. */
+#define P3D_BOX3D_LDS_CAPACITY 64
+#define P3D_BOX3D_SLAB_CAPACITY 768
+#define P3D_BOX3D_WAVES_PER_GROUP 4
+#define P3D_BOX3D_MAX_GROUPS 4096
+#define P3D_BOX3D_SLAB_WAVES 256
+size_t p3d_iou_box3d_workspace_bytes(int64_t N, int64_t M);
+int p3d_iou_box3d(const float* boxes1, const float* boxes2, int64_t N, int64_t M, int lds_capacity, float* vol, float* iou,
+                  void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+int p3d_iou_box3d_host(const float* boxes1, const float* boxes2, int64_t N, int64_t M, float* vol, float* iou);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

@@ -1178,6 +1178,59 @@ def point_frames(points, lengths, K, disambiguate_directions=True, frames=True, 
 
 
 # ----------------------------------------------------------------------------------------------
+# box3d_overlap (csrc/box3d.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the name of BOX3D_EXPORTS to
+# pytorch3d_amd.iou_box3d.iou_box3d_op, which comes here: iou_box3d for GPU tensors, iou_box3d_host for CPU tensors.
+def _check_boxes(boxes1, boxes2, who):
+    for name, b in (("boxes1", boxes1), ("boxes2", boxes2)):
+        if b.dim() != 3 or tuple(b.shape[1:]) != (8, 3):
+            raise RuntimeError(f"{who}: {name} must have shape (B, 8, 3), got {tuple(b.shape)}")
+        if b.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name} must be float32, got {b.dtype}")
+    if boxes1.device != boxes2.device:
+        raise RuntimeError(f"Expected all tensors to be on the same device, but boxes2 is on {boxes2.device} and boxes1 is on {boxes1.device}")
+
+
+def iou_box3d(boxes1, boxes2, lds_capacity=None, return_overflow=False):
+    """IoUBox3D (iou_box3d.h) on GPU tensors: (vol (N, M), iou (N, M)) float32 of p3d_iou_box3d (include/p3d_amd.h).  The boxes are
+    made contiguous here.  lds_capacity: triangles per fragment list of the first launch (default P3D_BOX3D_LDS_CAPACITY; results do
+    not depend on it); return_overflow: also a 0-dim int32 tensor on the device, the number of pairs the second launch redid."""
+    who = "iou_box3d"
+    _check_boxes(boxes1, boxes2, who)
+    dev = _same_device(("boxes1", boxes1), ("boxes2", boxes2))
+    N, M = boxes1.shape[0], boxes2.shape[0]
+    cap = _lib.BOX3D_LDS_CAPACITY if lds_capacity is None else int(lds_capacity)
+    boxes1, boxes2 = boxes1.contiguous(), boxes2.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        vol = torch.empty((N, M), dtype=torch.float32, device=dev)
+        iou = torch.empty((N, M), dtype=torch.float32, device=dev)
+        if N * M == 0:
+            return (vol, iou, torch.zeros((), dtype=torch.int32, device=dev)) if return_overflow else (vol, iou)
+        nbytes = lib.p3d_iou_box3d_workspace_bytes(N, M)
+        ws = _workspace(nbytes, dev)
+        rc = lib.p3d_iou_box3d(_ptr(boxes1), _ptr(boxes2), N, M, cap, _ptr(vol), _ptr(iou), _ptr(ws), nbytes, _stream(dev))
+        _lib.check(rc, who)
+        if return_overflow:
+            return vol, iou, ws[:4].view(torch.int32)[0].clone()
+    return vol, iou
+
+
+def iou_box3d_host(boxes1, boxes2):
+    """The same contract on CPU tensors: p3d_iou_box3d_host, a serial loop over the pairs."""
+    who = "iou_box3d_host"
+    _check_boxes(boxes1, boxes2, who)
+    if boxes1.is_cuda:
+        raise RuntimeError(f"{who}: the host loop takes CPU tensors")
+    N, M = boxes1.shape[0], boxes2.shape[0]
+    boxes1, boxes2 = boxes1.contiguous(), boxes2.contiguous()
+    vol = torch.empty((N, M), dtype=torch.float32)
+    iou = torch.empty((N, M), dtype=torch.float32)
+    if N * M:
+        _lib.check(_lib.load().p3d_iou_box3d_host(_ptr(boxes1), _ptr(boxes2), N, M, _ptr(vol), _ptr(iou)), who)
+    return vol, iou
+
+
+# ----------------------------------------------------------------------------------------------
 # point clouds into voxel grids (csrc/points_to_volumes.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
 # POINTS_TO_VOLUMES_EXPORTS to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op), which come here for float32 GPU tensors
 # and own a torch formulation of the same contract for CPU tensors.
@@ -1428,6 +1481,8 @@ POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "fa
 POINT_CLOUD_EXPORTS = ("sample_farthest_points", "ball_query")
 # bound by shim.make_module to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op)
 POINTS_TO_VOLUMES_EXPORTS = ("points_to_volumes_forward", "points_to_volumes_backward")
+# bound by shim.make_module to the wrapper of pytorch3d_amd.iou_box3d (<name>_op)
+BOX3D_EXPORTS = ("iou_box3d",)
 
 
 HOT_PATH_EXPORTS = (

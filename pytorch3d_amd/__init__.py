@@ -19,6 +19,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  point clouds into voxel grids, in place, fused
     estimate_pointcloud_normals, estimate_pointcloud_local_coord_frames, point_covariances  normals, curvatures and local frames of a
                                      point cloud from its K nearest neighbours, one launch, nothing of size K per point materialised
+    box3d_overlap                    exact intersection volume and IoU of oriented 3D boxes, one wave per pair, no list cap
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -30,6 +31,7 @@ from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_al
 from .chamfer import chamfer_distance  # noqa: F401
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
+from .iou_box3d import box3d_overlap  # noqa: F401
 from .knn import knn_gather, knn_points  # noqa: F401
 from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
                           mesh_normal_consistency)

@@ -32,6 +32,9 @@ KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
 FRAMES_MAX_K = 64        # P3D_FRAMES_MAX_K: the largest neighbourhood of csrc/point_frames.hip
 FRAMES_DISAMBIGUATE = 1  # P3D_FRAMES_DISAMBIGUATE
 FRAMES_ROWS_PER_GROUP = 64  # P3D_FRAMES_ROWS_PER_GROUP: query rows of one workgroup of csrc/point_frames.hip
+BOX3D_LDS_CAPACITY = 64     # P3D_BOX3D_LDS_CAPACITY: triangles per fragment list of csrc/box3d.hip's first launch
+BOX3D_WAVES_PER_GROUP = 4   # P3D_BOX3D_WAVES_PER_GROUP: pairs per workgroup and round of that launch
+BOX3D_MAX_GROUPS = 4096     # P3D_BOX3D_MAX_GROUPS: its largest grid; more pairs take the grid-stride loop
 FPS_REGISTER_POINTS = 16384  # P3D_FPS_REGISTER_POINTS: the largest cloud the register form of farthest point sampling holds
 POINT_MESH_POINT, POINT_MESH_SEGMENT, POINT_MESH_TRIANGLE = 0, 1, 2  # P3D_POINT_MESH_*: the kind of a query / target object
 POINT_MESH_TILE = 64                # P3D_POINT_MESH_TILE: target records staged per wave and step
@@ -223,6 +226,10 @@ _SIGNATURES = {
     # point-cloud covariances, curvatures and local coordinate frames (csrc/point_frames.hip)
     "p3d_point_frames_workgroups": (c_i64, [c_i64, c_i64]),
     "p3d_point_frames": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_uint, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    # box3d_overlap (csrc/box3d.hip): the device entry with its LDS capacity argument, and the host loop
+    "p3d_iou_box3d_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "p3d_iou_box3d": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "p3d_iou_box3d_host": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

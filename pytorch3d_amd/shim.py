@@ -15,6 +15,8 @@ reference losses run under plain `shim.install()`.  So are `_C.sample_farthest_p
 unmodified `pytorch3d.ops.sample_farthest_points` runs, and so does the forward of `pytorch3d.ops.ball_query`; its backward ends in
 `_C.knn_points_backward`, which stays a stub -- patch_python replaces the whole function.  And `_C.points_to_volumes_forward` /
 `_backward` (csrc/points_to_volumes.hip): the unmodified `pytorch3d.ops.add_pointclouds_to_volumes` runs, forward and backward.
+And `_C.iou_box3d` (csrc/box3d.hip: the kernels for GPU tensors, the library's host loop for CPU tensors): the unmodified
+`pytorch3d.ops.box3d_overlap` runs on both.
 
     shim.install(patch_python=True)
 
@@ -76,6 +78,8 @@ reference classes runs on them end to end:
                                                                  estimate_normals comes here through `ops`; K > 64, float64, CPU
                                                                  tensors, eigh and inputs that require grad go to this package's
                                                                  torch formulation
+    ops.iou_box3d.box3d_overlap                               -> pytorch3d_amd.iou_box3d.box3d_overlap: the same operator (csrc/box3d.hip)
+                                                                 behind input checks that cost one host sync instead of four
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -133,6 +137,10 @@ def make_module(flavour="ctypes"):
     # of the same contract for CPU tensors; in place, no return value.  Both flavours serve these wrappers.
     for name in _ours.POINTS_TO_VOLUMES_EXPORTS:
         setattr(mod, name, getattr(importlib.import_module(__package__ + ".points_to_volumes"), name + "_op"))
+    # box3d_overlap's operator (pytorch3d_amd/iou_box3d.py): csrc/box3d.hip's kernels for float32 GPU boxes, the library's host loop for
+    # float32 CPU boxes.  Both flavours serve this wrapper.
+    for name in _ours.BOX3D_EXPORTS:
+        setattr(mod, name, getattr(importlib.import_module(__package__ + ".iou_box3d"), name + "_op"))
     if flavour == "pybind":
         # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
         def compiled(name):
@@ -385,6 +393,32 @@ def patch_reference_python():
     _patch_fps_ball()
     _patch_points_to_volumes()
     _patch_points_normals()
+    _patch_box3d_overlap()
+
+
+def _patch_box3d_overlap():
+    """pytorch3d.ops.iou_box3d.box3d_overlap -> this package's function, in every module that copied the name (pytorch3d.ops).  The
+    operator underneath is the one plain install() already serves; the replacement evaluates the reference's four input checks with
+    one host sync.  PATCH_CALLS counts GPU calls (the kernels) as fused and CPU calls (the host loop) as fallbacks."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".iou_box3d")
+    try:  # every module that copied the name must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.ops.iou_box3d")
+        importlib.import_module("pytorch3d.ops")
+    except ImportError:  # a reference checkout without the module: nothing to patch
+        return
+
+    def box3d_overlap(boxes1, boxes2, eps=1e-4):
+        out = ours.box3d_overlap(boxes1, boxes2, eps)
+        _count("box3d_overlap", ours.kernel_path(boxes1, boxes2))  # (a call that raised is not counted)
+        return out
+
+    orig = ref.box3d_overlap
+    box3d_overlap.__doc__ = getattr(orig, "__doc__", None)
+    box3d_overlap.__wrapped__ = orig
+    box3d_overlap.__p3d_amd__ = True
+    _replace_everywhere(orig, box3d_overlap)
 
 
 def _patch_points_normals():
