@@ -147,8 +147,11 @@ int p3d_rasterize_meshes_cover_check(const int64_t* pix_to_face, const int32_t* 
  * When the forward's tiles are the words of the cover (binned, image sides multiples of 16, at most 512 pixels a side, a full
  * workspace) the list is filled from the tile plan of the coarse stage instead, without atomics: it then holds the word of EVERY
  * tile whose bin list holds a face, in the order the forward walks them (longest list first, or image order for small launches),
- * and the counter is the number of those tiles.  That is a superset of the non-empty words: a tile whose faces reach no pixel
- * centre is listed with a word that ends up 0 (the backward finds no row there and returns).  No word is listed twice. */
+ * and the counter is the number of those tiles.  The list is then the list of the active tiles in walk order, including tiles whose
+ * word is 0: a superset of the non-empty words -- a tile whose faces reach no pixel centre is listed with a word that ends up 0
+ * (the backward finds no row there and returns).  No word is listed twice.
+ * The words and the counter need no clearing by the caller: binned launches clear them in the first pass of the coarse stage, the
+ * others with a memset. */
 size_t p3d_rasterize_meshes_cover_list_bytes(int N, int H, int W);
 
 /* flags of p3d_rasterize_meshes_ex (both) and p3d_rasterize_points_ex (P3D_RASTER_CUDA_TIE_ORDER only) */
@@ -171,7 +174,11 @@ size_t p3d_rasterize_meshes_cover_list_bytes(int N, int H, int W);
  * P3D_TIE_SKIP_REPLAY set in the environment the replay is skipped and the marks (-2) stay in pix_to_face
  * (profiles/tie_order_timing.py --count-marks). */
 
-/* p3d_rasterize_meshes + the row cover of its output.  cover: p3d_rasterize_meshes_cover_bytes, or with P3D_RASTER_COVER_LIST a
+/* clipped_faces_neighbor_idx of p3d_rasterize_meshes_ex, p3d_rasterize_meshes and p3d_rasterize_meshes_naive may be NULL: "no
+ * face has a clipped neighbour", the same as F entries of -1 without the array, its fill and the 8 bytes the fine kernel gathers
+ * of it per (tile, face).  p3d_rasterize_meshes_fine keeps requiring it.
+ *
+ * p3d_rasterize_meshes + the row cover of its output.  cover: p3d_rasterize_meshes_cover_bytes, or with P3D_RASTER_COVER_LIST a
  * p3d_rasterize_meshes_cover_list_bytes buffer; null: no cover (flags may then not hold P3D_RASTER_COVER_LIST).  Unknown bits,
  * or P3D_RASTER_CUDA_TIE_ORDER together with P3D_RASTER_COVER_LIST (a combination no caller reaches): P3D_ERR_INVALID_ARG.
  * Short workspaces are accepted (above). */
@@ -181,6 +188,26 @@ int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh_to_face
                             int clip_barycentric_coords, int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary,
                             float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
                             p3d_stream_t stream);
+
+/* p3d_rasterize_meshes_ex on PACKED vertices: `face_verts = verts_packed[faces_packed]` (p3d_gather_face_verts[_pre] below, the same
+ * index rules and the same bytes) is part of the call.  verts (V,3) f32, faces (F,3) i64 are read; face_verts (F,3,3) f32 and, when
+ * not null, face_pre (F,4) f32 (16-byte aligned; the records of p3d_gather_face_verts_pre) are WRITTEN, for the caller's backward.
+ * zero_verts: null, or (V,3) f32 that the call sets to zero -- the grad_out of the p3d_rasterize_meshes_backward_ex that follows,
+ * handed over with P3D_BWD_GRAD_OUT_ZEROED.  Everything else as p3d_rasterize_meshes_ex, with the same results bit for bit.
+ * A binned launch does all three inside the first pass of the coarse stage (the thread that forms a face's bin rectangle gathers
+ * the face; the workgroups clear zero_verts and the cover as they start): no launch and no memset of their own.  It writes
+ * face_verts / face_pre for every face inside a mesh's range [first, first + count) -- the faces a rasterization can return; faces
+ * of the packed array that belong to no mesh are left as they were.  Naive launches (bin_size or max_faces_per_bin 0) and empty
+ * outputs run the stand-alone gather and a memset first.
+ * Refused before anything is launched (P3D_ERR_INVALID_ARG): unknown flag bits, V < 0, F < 0, F > 0 with a null verts, faces or
+ * face_verts, a face_pre without face_verts or not 16-byte aligned. */
+int p3d_rasterize_meshes_verts_ex(const float* verts, const int64_t* faces, int64_t V, float* face_verts, float* face_pre,
+                                  float* zero_verts, const int64_t* mesh_to_face_first_idx, const int64_t* num_faces_per_mesh,
+                                  const int64_t* clipped_faces_neighbor_idx, int64_t F, int N, int H, int W, float blur_radius,
+                                  int faces_per_pixel, int bin_size, int max_faces_per_bin, int perspective_correct,
+                                  int clip_barycentric_coords, int cull_backfaces, int64_t* pix_to_face, float* zbuf, float* bary,
+                                  float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
+                                  p3d_stream_t stream);
 
 /* Per-face records (round 6; the reference has no counterpart: its backward re-derives them per sample, geometry_utils.cuh:
  * 101-161, 365-385): face_pre (F, 4) f32, 16-byte aligned: 1 / (barycentric area), 1 / |v1 - v0|^2, 1 / |v2 - v0|^2,
@@ -197,11 +224,12 @@ size_t p3d_rasterize_meshes_backward_workspace_bytes(int N, int H, int W);
 /* flags of p3d_rasterize_meshes_backward_ex */
 #define P3D_BWD_COVER_HAS_LIST 1u /* `cover` is the front of a cover-list buffer: take the list, ignore the workspace            */
 #define P3D_BWD_MAKE_FACE_PRE 2u  /* face_pre is scratch (F x 4 f32) that this call fills first with one small launch            */
+#define P3D_BWD_GRAD_OUT_ZEROED 8u /* grad_out holds zeros already (p3d_rasterize_meshes_verts_ex: zero_verts): no memset here    */
 
 /* The backward of p3d_rasterize_meshes[_ex].  faces null: grad_out is grad_face_verts (F,3,3).  faces (F,3) i64: grad_out is the
  * gradient of `face_verts = verts_packed[faces_packed]` (rasterize_meshes.py:146, torch indexing + its index_put backward)
  * fused in, grad_verts (V,3): the per-face partials are flushed straight to the vertices -- no (F,3,3) intermediate, no
- * separate scatter.  grad_out is zeroed and accumulated here.
+ * separate scatter.  grad_out is zeroed (unless P3D_BWD_GRAD_OUT_ZEROED says it is) and accumulated here.
  * cover: the cover of THAT pix_to_face, or null (every row is read).
  * face_pre: per-face records (above), or null (formed per sample).  Without P3D_BWD_MAKE_FACE_PRE they are read as
  * p3d_gather_face_verts_pre wrote them.  Records are used by the launches with perspective_correct && clip_barycentric_coords

@@ -290,6 +290,14 @@ COVER_LIST = os.environ.get("P3D_COVER_LIST", "1") not in ("", "0")
 # written by the fused vertex node's gather (pytorch3d_amd/rasterize_meshes.py), made in the call for rasterize_meshes_backward.
 # 0: formed per sample.  Read at call time, by both.
 FACE_PRE = os.environ.get("P3D_FACE_PRE", "1") not in ("", "0")
+# The step chain of the fused vertex node (pytorch3d_amd/rasterize_meshes.py: _RasterizeMeshVerts), one switch per item, read at call
+# time (profiles/step_chain_mi355x.txt measures each):
+#   NULL_NEIGHBOR    no clipping: no clipped_faces_neighbor_idx tensor at all (a null pointer: include/p3d_amd.h) instead of F x -1
+#   FUSED_GATHER     the face gather inside the count pass of the binning (p3d_rasterize_meshes_verts_ex) instead of its own launch
+#   PRECLEARED_GRAD  the backward's grad_verts allocated by the forward and cleared by that count pass (needs FUSED_GATHER)
+NULL_NEIGHBOR = os.environ.get("P3D_NULL_NEIGHBOR", "1") not in ("", "0")
+FUSED_GATHER = os.environ.get("P3D_FUSED_GATHER", "1") not in ("", "0")
+PRECLEARED_GRAD = os.environ.get("P3D_PRECLEARED_GRAD", "1") not in ("", "0")
 CHECK_COVERS = os.environ.get("P3D_CHECK", "0") not in ("", "0")
 COVER_RECALLS = [0, 0]  # backward calls without an explicit cover: [found the forward's, found none] (read by tests / profiles)
 COVER_CHECKS = [0, 0]   # CHECK_COVERS: [covers verified, of which stale]
@@ -352,16 +360,19 @@ def _recall_cover(p2f):
 
 def _rasterize_meshes_covered(face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size,
                               blur_radius, faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct,
-                              clip_barycentric_coords, cull_backfaces, want_cover=True):
+                              clip_barycentric_coords, cull_backfaces, want_cover=True, packed=None):
     """rasterize_meshes + the row cover of its output (include/p3d_amd.h: p3d_rasterize_meshes_ex) for the autograd
-    nodes of this package: ((pix_to_face, zbuf, bary, dists), cover or None)."""
+    nodes of this package: ((pix_to_face, zbuf, bary, dists), cover or None).
+    clipped_faces_neighbor_idx None (the nodes of this package only): no face has a clipped neighbour, a null pointer.
+    packed = (verts (V,3) f32, faces (F,3) i64, face_pre (F,4) or None, zero_verts (V,3) or None), all contiguous: face_verts is an
+    uninitialised (F,3,3) OUTPUT, gathered inside the call, face_pre and zero_verts with it (p3d_rasterize_meshes_verts_ex)."""
     dev = _same_device(("face_verts", face_verts), ("mesh_to_face_first_idx", mesh_to_face_first_idx),
                        ("num_faces_per_mesh", num_faces_per_mesh),
-                       ("clipped_faces_neighbor_idx", clipped_faces_neighbor_idx))
+                       *([("clipped_faces_neighbor_idx", clipped_faces_neighbor_idx)] if clipped_faces_neighbor_idx is not None else []))
     _check_face_verts(face_verts)
     if num_faces_per_mesh.size(0) != mesh_to_face_first_idx.size(0):
         raise RuntimeError("num_faces_per_mesh must have save size first dimension as mesh_to_faces_packed_first_idx")
-    if clipped_faces_neighbor_idx.size(0) != face_verts.size(0):
+    if clipped_faces_neighbor_idx is not None and clipped_faces_neighbor_idx.size(0) != face_verts.size(0):
         raise RuntimeError("clipped_faces_neighbor_idx must have save size first dimension as face_verts")
     K = int(faces_per_pixel)
     _check_k(K)
@@ -372,12 +383,14 @@ def _rasterize_meshes_covered(face_verts, mesh_to_face_first_idx, num_faces_per_
         _num_bins(H, W, bin_size, "RasterizeCoarseCuda")
     fv = _c(face_verts, torch.float32)
     first, count = _c(mesh_to_face_first_idx, torch.int64), _c(num_faces_per_mesh, torch.int64)
-    nb = _c(clipped_faces_neighbor_idx, torch.int64)
+    nb = _c(clipped_faces_neighbor_idx, torch.int64) if clipped_faces_neighbor_idx is not None else None
     N, F = count.size(0), fv.size(0)
     lib = _lib.load()
     with torch.cuda.device(dev):
         out = _mesh_outputs(N, H, W, K, dev)
         if out[0].numel() == 0:
+            if packed is not None:
+                raise RuntimeError("packed vertices with an empty output: gather the faces with p3d_gather_face_verts instead")
             return out, None
         # (the naive launch needs no workspace; with the CUDA tie order it takes one for the lane masks of the marked pixels --
         # without it the replay finds its pixels by reading a pix_to_face entry of every pixel)
@@ -394,10 +407,17 @@ def _rasterize_meshes_covered(face_verts, mesh_to_face_first_idx, num_faces_per_
             flags |= _lib.RASTER_COVER_LIST
         elif want_cover:
             cover = torch.empty((N, (H + 15) // 16, (W + 15) // 16), dtype=torch.int32, device=dev)
-        rc = lib.p3d_rasterize_meshes_ex(
-            _ptr(fv), _ptr(first), _ptr(count), _ptr(nb), F, N, H, W, float(blur_radius), K, bin_size if binned else 0,
-            M if binned else 0, int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), int(bool(cull_backfaces)),
-            _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(cover), flags, _ptr(ws), ws.numel(), _stream(dev))
+        tail = (_ptr(first), _ptr(count), _ptr(nb), F, N, H, W, float(blur_radius), K, bin_size if binned else 0,
+                M if binned else 0, int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), int(bool(cull_backfaces)),
+                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(cover), flags, _ptr(ws), ws.numel(), _stream(dev))
+        if packed is not None:
+            verts, faces, face_pre, zero_verts = packed
+            if fv is not face_verts:
+                raise RuntimeError("packed vertices: face_verts must be the contiguous float32 buffer the call fills")
+            rc = lib.p3d_rasterize_meshes_verts_ex(_ptr(verts), _ptr(faces), verts.size(0), _ptr(fv), _ptr(face_pre), _ptr(zero_verts),
+                                                   *tail)
+        else:
+            rc = lib.p3d_rasterize_meshes_ex(_ptr(fv), *tail)
         _lib.check(rc, "rasterize_meshes")
         if need is not None:
             need.report_later(ws, need_at, entries)
@@ -508,9 +528,12 @@ def backward_workspace(cover, N, H, W, dev):
 # reciprocals per sample although it has the records -- the entry point that took the records had no workspace argument.
 # Dropping the clause changes results on degenerate edges: a fix of its own.
 def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad_dists, perspective_correct, clip_barycentric_coords,
-                   cover, face_pre=None):
+                   cover, face_pre=None, zeroed_out=None):
     """grad_face_verts (F,3,3) when faces is None, else grad_verts (V,3) through faces (F,3).  Missing grads count as zeros;
-    cover: the row cover of THIS pix_to_face or None; face_pre: the records of p3d_gather_face_verts_pre (faces given) or None."""
+    cover: the row cover of THIS pix_to_face or None; face_pre: the records of p3d_gather_face_verts_pre (faces given) or None.
+    zeroed_out (faces given): a (V,3) float32 buffer of zeros that nobody else holds -- the forward's count pass cleared it
+    (p3d_rasterize_meshes_verts_ex: zero_verts): it becomes the result, and the call clears nothing (BWD_GRAD_OUT_ZEROED).  The
+    deterministic form needs no zeros and ignores it."""
     dev = pix_to_face.device
     zeros = lambda *tail: torch.zeros(tuple(pix_to_face.shape) + tail, dtype=torch.float32, device=dev)
     gz = _c(grad_zbuf, torch.float32) if grad_zbuf is not None else zeros()
@@ -531,7 +554,12 @@ def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad
         else:
             faces = _c(faces, torch.int64)
             # (zeros: with F == 0 nothing is called -- a null faces pointer would ask for the per-face form)
-            out = (torch.empty if F else torch.zeros)((V, 3), dtype=torch.float32, device=dev)
+            if zeroed_out is not None and F and not _ordered() and tuple(zeroed_out.shape) == (V, 3) and zeroed_out.dtype == torch.float32 \
+                    and zeroed_out.device == dev and zeroed_out.is_contiguous():
+                out = zeroed_out
+                flags |= _lib.BWD_GRAD_OUT_ZEROED
+            else:
+                out = (torch.empty if F else torch.zeros)((V, 3), dtype=torch.float32, device=dev)
             if not (has_list or cover is None):
                 face_pre = None  # the QUIRK above
         if F == 0:

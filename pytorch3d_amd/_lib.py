@@ -26,6 +26,7 @@ RASTER_COVER_LIST = 1
 RASTER_CUDA_TIE_ORDER = 2
 BWD_COVER_HAS_LIST = 1
 BWD_MAKE_FACE_PRE = 2
+BWD_GRAD_OUT_ZEROED = 8
 KNN_MAX_K = 32           # P3D_KNN_MAX_K
 KNN_TILE = 512           # P3D_KNN_TILE: p2 points staged per step
 KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
@@ -65,6 +66,9 @@ _SIGNATURES = {
     "p3d_rasterize_meshes_cover_list_bytes": (c_size, [c_int, c_int, c_int]),
     "p3d_rasterize_meshes_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int, c_int, c_int,
                                         c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_uint, c_ptr, c_size, c_ptr]),
+    "p3d_rasterize_meshes_verts_ex": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int,
+                                              c_f32, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_uint,
+                                              c_ptr, c_size, c_ptr]),
     "p3d_rasterize_meshes_backward_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "p3d_gather_face_verts": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     "p3d_gather_face_verts_pre": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),

@@ -120,13 +120,33 @@ size_t bin_workspace_bytes(int64_t E, int N, const BinGeom& g, int M, int64_t li
 // with_z: list entries of two ints, (id, depth bits) (BinWorkspace::stride).
 bool bin_carve(Arena& arena, int64_t E, int N, const BinGeom& g, int M, BinWorkspace* ws, int64_t list_entries = -1, bool with_z = false);
 
+// Work the count pass takes along for the caller (raster_mesh.hip), so that it needs no launch of its own:
+//   the face gather (triangles only; verts != null): the thread of face e reads faces[e] and its three vertices, writes
+//     face_verts[e] (== elems + 9 e, which the count pass would have read) and, when asked for, face_pre[e] -- the bytes of
+//     p3d_gather_face_verts_pre (face_gather.h) -- and forms its rectangle from the registers.  Every face of a mesh's range
+//     [first[n], first[n] + count[n]) is written: those are the faces the fill pass, the fine kernel and the backward can read;
+//   two clears: zero0 / zero1, n0 / n1 32-bit words set to 0 by a grid-stride loop of all workgroups of the launch (the row
+//     cover with its list header; the backward's gradient buffer).  Neither may overlap anything the binning reads or writes.
+struct BinFused {
+  const float* verts = nullptr;    // (V, 3)
+  const int64_t* faces = nullptr;  // (E, 3)
+  int64_t V = 0, E = 0;            // (a face id outside 0 .. E-1 -- first / count that do not describe the packed array -- is
+                                   // neither gathered nor written: its corners read as NaN)
+  float* face_verts = nullptr;     // (E, 3, 3)
+  float4* face_pre = nullptr;      // (E) or null
+  int* zero0 = nullptr;
+  int* zero1 = nullptr;
+  int64_t n0 = 0, n1 = 0;
+};
+
 // Build the CSR lists.  elems: face_verts (E,3,3) or points (E,3); aux: radius (E) for points.
 // ordered = false (points only): ids inside a 1024-primitive chunk land in arrival order (integer LDS
 // atomics) instead of ascending order -- for consumers whose result is order-free; which ids survive
 // an overflowing bin (> M) is then unspecified, as in the reference (rasterize_coarse.cu:186-201).
+// fused (triangles): see BinFused; null: nothing is taken along.
 int bin_build(BinKind kind, const float* elems, const float* aux, const int64_t* first, const int64_t* count, int64_t E,
               int N, const BinGeom& g, int M, float sqrt_blur, const BinWorkspace& ws, hipStream_t stream,
-              bool ordered = true);
+              bool ordered = true, const BinFused* fused = nullptr);
 
 // out[i] = sum(in[0..i)) for i in 0..n (n + 1 outputs, int64); blocksum: scratch of ceil(n / 1024) + 1 entries.
 int exclusive_scan_i32(const int* in, int64_t n, long long* blocksum, int64_t* out, hipStream_t stream);

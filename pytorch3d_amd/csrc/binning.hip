@@ -10,6 +10,7 @@
 // offset + mbcnt-prefix.  Lists come out ascending and exactly sized; nothing is pre-filled.
 #include "binning.h"
 #include "p3d_geom.h"
+#include "face_gather.h"
 
 namespace p3d {
 
@@ -103,13 +104,15 @@ __device__ __forceinline__ int prefix_count(int n, Pred holds) {
 }
 
 // Shared prologue of the count and fill kernels.  chunk_start == nullptr: plan in LDS (cs_l) instead.
-template <int KIND>
+// GATHER (the count pass of a triangle launch that was handed packed vertices, binning.h: BinFused): the face is gathered
+// through `faces` and written to face_verts / face_pre here instead of being read from `elems`.
+template <int KIND, bool GATHER = false>
 __device__ __forceinline__ bool chunk_prologue(const float* __restrict__ elems, const float* __restrict__ aux,
                                                const int64_t* __restrict__ first, const int64_t* __restrict__ count,
                                                const int* chunk_start, int* cs_l, int N, int H, int W, int bin_size,
                                                int BH, int BW, float sqrt_blur, float* xlo_t, float* xhi_t,
                                                float* ylo_t, float* yhi_t, ChunkCtx* c, int* publish_plan = nullptr,
-                                               int* plan_hdr = nullptr) {
+                                               int* plan_hdr = nullptr, const BinFused* fz = nullptr) {
   const int tid = threadIdx.x;
   const int chunk = blockIdx.x;
   if (chunk_start == nullptr) {
@@ -159,7 +162,20 @@ __device__ __forceinline__ bool chunk_prologue(const float* __restrict__ elems, 
     bool skip;
     if (KIND == kTriangles) {
       // TriangleBoundingBoxKernel, rasterize_coarse.cu:28-44
-      const float* q = elems + e * 9;
+      float q[9];
+      if (GATHER) {
+        if (e >= 0 && e < fz->E) {
+          gather_face_corners(fz->verts, fz->faces, fz->V, e, q);
+          store_face(q, e, fz->face_verts, fz->face_pre);
+        } else {
+#pragma unroll
+          for (int k = 0; k < 9; ++k) q[k] = __int_as_float(0x7fc00000);
+        }
+      } else {
+        const float* g = elems + e * 9;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) q[k] = g[k];
+      }
       const float v0x = q[0], v0y = q[1], v0z = q[2];
       const float v1x = q[3], v1y = q[4], v1z = q[5];
       const float v2x = q[6], v2y = q[7], v2z = q[8];
@@ -242,23 +258,31 @@ __device__ __forceinline__ void for_union_bins(const BinRect& u, int lane, F f) 
 // ---------------------------------------------------------------------------------------
 // count: counts[chunk][bin] = members of `bin` among the chunk's 1024 primitives.
 // ---------------------------------------------------------------------------------------
-template <int KIND, bool ORDERED>
+// `fz`: what the pass takes along (binning.h: BinFused) -- the two clears before anything else, by EVERY workgroup of the grid
+// (also those past the last chunk); GATHER: the face gather, in the prologue.
+template <int KIND, bool ORDERED, bool GATHER = false>
 __global__ __launch_bounds__(kBinChunk) void bin_count_kernel(const float* __restrict__ elems,
                                                               const float* __restrict__ aux,
                                                               const int64_t* __restrict__ first,
                                                               const int64_t* __restrict__ count,
                                                               const int* chunk_start, int N, int H, int W,
                                                               int bin_size, int BH, int BW, float sqrt_blur,
-                                                              int* __restrict__ counts, int* publish_plan, int* plan_hdr) {
+                                                              int* __restrict__ counts, int* publish_plan, int* plan_hdr,
+                                                              const BinFused fz) {
   __shared__ float xlo_t[32], xhi_t[32], ylo_t[32], yhi_t[32];
   __shared__ int cs_l[kSelfPlanMax + 1];
   __shared__ int blk_cnt[kMaxBins];
   __shared__ unsigned long long rowm[ORDERED ? kWavesPerChunk : 1][kMaxBinsSide], colm[ORDERED ? kWavesPerChunk : 1][kMaxBinsSide];
   const int nbins = BH * BW;
+  {
+    const int64_t t = (int64_t)blockIdx.x * kBinChunk + threadIdx.x, step = (int64_t)gridDim.x * kBinChunk;
+    for (int64_t i = t; i < fz.n0; i += step) fz.zero0[i] = 0;
+    for (int64_t i = t; i < fz.n1; i += step) fz.zero1[i] = 0;
+  }
   for (int b = threadIdx.x; b < nbins; b += kBinChunk) blk_cnt[b] = 0;
   ChunkCtx c;
-  if (!chunk_prologue<KIND>(elems, aux, first, count, chunk_start, cs_l, N, H, W, bin_size, BH, BW, sqrt_blur, xlo_t,
-                            xhi_t, ylo_t, yhi_t, &c, publish_plan, plan_hdr))
+  if (!chunk_prologue<KIND, GATHER>(elems, aux, first, count, chunk_start, cs_l, N, H, W, bin_size, BH, BW, sqrt_blur, xlo_t,
+                                    xhi_t, ylo_t, yhi_t, &c, publish_plan, plan_hdr, &fz))
     return;
   const int lane = lane_id();
   if (ORDERED) {
@@ -788,8 +812,10 @@ size_t bin_workspace_bytes(int64_t E, int N, const BinGeom& g, int M, int64_t li
 }
 
 int bin_build(BinKind kind, const float* elems, const float* aux, const int64_t* first, const int64_t* count, int64_t E,
-              int N, const BinGeom& g, int M, float sqrt_blur, const BinWorkspace& ws, hipStream_t stream, bool ordered) {
+              int N, const BinGeom& g, int M, float sqrt_blur, const BinWorkspace& ws, hipStream_t stream, bool ordered,
+              const BinFused* fused) {
   if (N <= 0) return P3D_OK;
+  const BinFused fz = (fused != nullptr && kind == kTriangles) ? *fused : BinFused();
   const int64_t rows = (int64_t)N * g.nbins;
   // small launches: three kernels instead of six (no plan kernel, one scan kernel) -- see bin_scan_small_kernel
   const bool small = N <= kSelfPlanMax && rows <= 4096 && ws.max_chunks <= 128;
@@ -805,15 +831,18 @@ int bin_build(BinKind kind, const float* elems, const float* aux, const int64_t*
   const unsigned chunks = (unsigned)ws.max_chunks;
   {
     LaunchScope ls("bin_count", stream);
-    if (kind == kTriangles)
+    if (kind == kTriangles && fz.verts != nullptr)
+      bin_count_kernel<kTriangles, true, true><<<chunks, kBinChunk, 0, stream>>>(elems, aux, first, count, cs, N, g.H, g.W, g.bin_size,
+                                                                                g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr, fz);
+    else if (kind == kTriangles)
       bin_count_kernel<kTriangles, true><<<chunks, kBinChunk, 0, stream>>>(elems, aux, first, count, cs, N, g.H, g.W,
-                                                                          g.bin_size, g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr);
+                                                                          g.bin_size, g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr, fz);
     else if (ordered)
       bin_count_kernel<kPoints, true><<<chunks, kBinChunk, 0, stream>>>(elems, aux, first, count, cs, N, g.H, g.W,
-                                                                       g.bin_size, g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr);
+                                                                       g.bin_size, g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr, fz);
     else
       bin_count_kernel<kPoints, false><<<chunks, kBinChunk, 0, stream>>>(elems, aux, first, count, cs, N, g.H, g.W,
-                                                                        g.bin_size, g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr);
+                                                                        g.bin_size, g.BH, g.BW, sqrt_blur, ws.counts, publish, ws.plan_hdr, fz);
   }
   if (small) {
     LaunchScope ls("bin_scan_small", stream);

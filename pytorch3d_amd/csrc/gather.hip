@@ -9,6 +9,7 @@
 // SURVEY section 8(f) row 3; optional entry points, `pytorch3d._C` is unchanged.
 #include "p3d_common.h"
 #include "p3d_geom.h"
+#include "face_gather.h"
 #include "wave_table.h"
 
 namespace p3d {
@@ -40,22 +41,8 @@ __global__ __launch_bounds__(256) void gather_faces_pre_kernel(const float* __re
                                                                float4* __restrict__ face_pre) {
   for (int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x; f < F; f += (int64_t)gridDim.x * 256) {
     float c[9];
-    const float nan = __int_as_float(0x7fc00000);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      int64_t v = faces[f * 3 + k];
-      if (v < 0) v += V;
-      const bool ok = v >= 0 && v < V;
-      const float* s = verts + (ok ? v : 0) * 3;
-      c[3 * k + 0] = ok ? s[0] : nan;
-      c[3 * k + 1] = ok ? s[1] : nan;
-      c[3 * k + 2] = ok ? s[2] : nan;
-    }
-    float* d = face_verts + f * 9;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) d[k] = c[k];
-    const BwdFacePre r = bwd_face_pre_make(mk3(c[0], c[1], c[2]), mk3(c[3], c[4], c[5]), mk3(c[6], c[7], c[8]));
-    face_pre[f] = make_float4(r.inv_area, r.inv_l01, r.inv_l02, r.inv_l12);
+    gather_face_corners(verts, faces, V, f, c);
+    store_face(c, f, face_verts, face_pre);
   }
 }
 

@@ -706,7 +706,10 @@ struct TileRect {
 // Stage up to 256 faces of the tile's list into LDS: per-face setup (done once per workgroup -- the reference redoes it
 // per pixel), tile cull, ordered compaction (ballot + mbcnt), FaceRec.  Returns the number of staged faces;
 // *general = some staged face has a clipped neighbour (workgroup-uniform).  Ends with a barrier.
-template <bool BINNED, bool PC = false>
+// NB: the launch has a neighbour array (MeshArgs::neighbor); false: null, no face has a clipped neighbour -- a template flag, not a
+// branch on the pointer: the branch cost the kernels at the register limit two more spilled SGPRs and mesh_fine 0.4 % of its time
+// (profiles/step_chain_mi355x.txt), this way the launches with an array run the code they ran before.
+template <bool BINNED, bool PC = false, bool NB = true>
 __device__ __forceinline__ int stage_chunk(const MeshArgs& a, const StageLds& l, const TileRect& tile, int64_t src_base,
                                            int count, int base, int tid, bool cull, bool clip, bool prune, bool* general) {
   const int lane = tid & 63, w = tid >> 6;
@@ -723,7 +726,7 @@ __device__ __forceinline__ int stage_chunk(const MeshArgs& a, const StageLds& l,
     fid = BINNED ? a.csr.list[src_base + i] : (int)(src_base + i);
     P3D_CHAIN_ARRIVED(2, "v"(fid));
     const float* g = a.face_verts + (int64_t)fid * 9;
-    nb = (int)a.neighbor[fid];  // requested together with the vertices: one memory round trip, not two
+    if (NB) nb = (int)a.neighbor[fid];  // requested together with the vertices: one memory round trip, not two
     v0 = mk3(g[0], g[1], g[2]);
     v1 = mk3(g[3], g[4], g[5]);
     v2 = mk3(g[6], g[7], g[8]);
@@ -931,7 +934,7 @@ __device__ __forceinline__ void merge_absorb(Queue& q, int K, const float* slab,
 // configs[1]: 256 tiles for 256 CUs) the launch lasts as long as the longest such walk (~0.2 ms on the cow), while three
 // quarters of the CUs idle.
 template <typename Queue, int KT, bool IN_REGS, bool BINNED, bool EXACT, int WAVES = kFineWaves, bool PC = false,
-          bool SPLIT = false, bool TIES = false>
+          bool SPLIT = false, bool TIES = false, bool NB = true>
 __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) {
   static_assert(!(SPLIT && TIES), "the tie marks of four queues that merge are not tracked: CUDA tie order runs the plain kernels");
   __shared__ float s_merge[SPLIT ? 3 * kMergeWords * KT * kWave : 1];
@@ -1157,7 +1160,7 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
   int tie_drop = kEmptyIdx;
   int staged = 0;
   for (; base < count; base += kStage) {
-    staged = stage_chunk<BINNED, PC>(a, lds, tile, src_base, count, base, tid, cull, clip, prune, &general);
+    staged = stage_chunk<BINNED, PC, NB>(a, lds, tile, src_base, count, base, tid, cull, clip, prune, &general);
     if (general) break;  // uniform
     P3D_CHAIN_STAMP(4);
     chunk_bucket_order(s_zc, staged, s_order, s_qlow, s_ord, tid);
@@ -1195,7 +1198,7 @@ __global__ __launch_bounds__(kStage, WAVES) void mesh_raster_kernel(MeshArgs a) 
       base += kStage;
       if (base >= count) break;
       bool dummy = false;
-      staged = stage_chunk<BINNED, PC>(a, lds, tile, src_base, count, base, tid, cull, clip, prune, &dummy);
+      staged = stage_chunk<BINNED, PC, NB>(a, lds, tile, src_base, count, base, tid, cull, clip, prune, &dummy);
     }
   }
 
@@ -1345,7 +1348,7 @@ __device__ __forceinline__ void replay_pixel(const MeshArgs& a, int n, int yi, i
     if (i < count) {
       b.f = BINNED ? a.csr.list[src + i] : (int)(src + i);
       verts(b.f, &b.v0, &b.v1, &b.v2);
-      b.nb = (int)a.neighbor[b.f];  // (face ids fit 31 bits; -1 stays -1)
+      if (a.neighbor != nullptr) b.nb = (int)a.neighbor[b.f];  // (face ids fit 31 bits; -1 stays -1; null: no clipped neighbours)
     }
     return b;
   };
@@ -1535,39 +1538,39 @@ __global__ __launch_bounds__(kStage) void mesh_cuda_order_kernel(MeshArgs a) {
 }
 
 // The instantiations one (Queue, K) pair can run as: split (few tiles), compile-time persp & clip, or plain.
-template <typename Q, int KT, bool REGS, bool BINNED, bool EXACT, bool TIES>
+template <typename Q, int KT, bool REGS, bool BINNED, bool EXACT, bool TIES, bool NB>
 void launch_fine_variant(const MeshArgs& a, unsigned grid, bool split, size_t dyn_lds, hipStream_t stream) {
   if constexpr (REGS && EXACT && BINNED && !TIES) {
     if (split) {
       // the merge slab (3 x 6 x KT x 64 floats beside the staging arrays) bounds the split kernel's occupancy: declare what
       // the LDS allows (K = 8: 66 KB -> 2 workgroups per CU, K = 4: 47 KB -> 3) instead of an unattainable 4
       constexpr int kSplitWaves = KT >= 8 ? 2 : (KT >= 4 ? 3 : kFineWaves);
-      mesh_raster_kernel<Q, KT, REGS, BINNED, EXACT, kSplitWaves, false, true><<<grid * 4, kStage, 0, stream>>>(a);
+      mesh_raster_kernel<Q, KT, REGS, BINNED, EXACT, kSplitWaves, false, true, false, NB><<<grid * 4, kStage, 0, stream>>>(a);
       return;
     }
   }
   if constexpr (REGS && EXACT) {
     if (a.persp && a.clip) {
-      mesh_raster_kernel<typename PcQueue<Q>::type, KT, REGS, BINNED, EXACT, kFineWaves, true, false, TIES><<<grid, kStage, dyn_lds, stream>>>(a);
+      mesh_raster_kernel<typename PcQueue<Q>::type, KT, REGS, BINNED, EXACT, kFineWaves, true, false, TIES, NB><<<grid, kStage, dyn_lds, stream>>>(a);
       return;
     }
   }
-  mesh_raster_kernel<Q, KT, REGS, BINNED, EXACT, kFineWaves, false, false, TIES><<<grid, kStage, dyn_lds, stream>>>(a);
+  mesh_raster_kernel<Q, KT, REGS, BINNED, EXACT, kFineWaves, false, false, TIES, NB><<<grid, kStage, dyn_lds, stream>>>(a);
 }
 
 // Queues without payload (K <= KT live entries): the perspective + clip instantiation (64-bit key compares; depths are
 // >= +0 there: clipped barycentrics are >= +0 and faces with a vertex depth below 1e-8 never reach the queue, face_setup) when
 // both flags are set.
-template <int KT, bool BINNED, int WAVES, bool TIES>
+template <int KT, bool BINNED, int WAVES, bool TIES, bool NB>
 void launch_long_variant(const MeshArgs& a, unsigned grid, hipStream_t stream) {
   if (a.persp && a.clip)
-    mesh_raster_kernel<TopKPairs<KT, true, 0>, KT, true, BINNED, false, WAVES, true, false, TIES><<<grid, kStage, 0, stream>>>(a);
+    mesh_raster_kernel<TopKPairs<KT, true, 0>, KT, true, BINNED, false, WAVES, true, false, TIES, NB><<<grid, kStage, 0, stream>>>(a);
   else
-    mesh_raster_kernel<TopKPairs<KT, false, 0>, KT, true, BINNED, false, WAVES, false, false, TIES><<<grid, kStage, 0, stream>>>(a);
+    mesh_raster_kernel<TopKPairs<KT, false, 0>, KT, true, BINNED, false, WAVES, false, false, TIES, NB><<<grid, kStage, 0, stream>>>(a);
 }
 
 #define P3D_COMMA ,
-template <bool BINNED, bool TIES>
+template <bool BINNED, bool TIES, bool NB>
 int launch_mesh_raster_t(const MeshArgs& a0, hipStream_t stream) {
   MeshArgs a = a0;
   unsigned grid = tile_grid(a.tm);
@@ -1582,9 +1585,9 @@ int launch_mesh_raster_t(const MeshArgs& a0, hipStream_t stream) {
   a.list_by_plan = a.walk_plan && a.area_list != nullptr && a.overflow == nullptr && a.tm.bin_size == kTile && a.H % kTile == 0 && a.W % kTile == 0 &&
                    a.csr.plan.arank != nullptr;
   const size_t dyn_lds = 0;
-#define P3D_LAUNCH_FINE(KT_, REGS_, EXACT_, Q_) launch_fine_variant<Q_, KT_, REGS_, BINNED, EXACT_, TIES>(a, grid, split, dyn_lds, stream)
-#define P3D_LAUNCH_FINE_W(KT_, WAVES_, Q_) mesh_raster_kernel<Q_, KT_, true, BINNED, false, WAVES_, false, false, TIES><<<grid, kStage, 0, stream>>>(a)
-#define P3D_LAUNCH_LONG(KT_, WAVES_) launch_long_variant<KT_, BINNED, WAVES_, TIES>(a, grid, stream)
+#define P3D_LAUNCH_FINE(KT_, REGS_, EXACT_, Q_) launch_fine_variant<Q_, KT_, REGS_, BINNED, EXACT_, TIES, NB>(a, grid, split, dyn_lds, stream)
+#define P3D_LAUNCH_FINE_W(KT_, WAVES_, Q_) mesh_raster_kernel<Q_, KT_, true, BINNED, false, WAVES_, false, false, TIES, NB><<<grid, kStage, 0, stream>>>(a)
+#define P3D_LAUNCH_LONG(KT_, WAVES_) launch_long_variant<KT_, BINNED, WAVES_, TIES, NB>(a, grid, stream)
   // Up to 8: queues WITH payload in registers.  K = 1, 2, 4, 8 have exact instantiations (vector-row epilogue, no
   // test on K left); 3 and 5..7 run the pair queue of the next capacity with K live entries (topk.h: TopKPairs::insert
   // skips the steps of the dead entries with scalar branches).  Until round 3 those K ran TopKReg queues of 8 / 12 entries
@@ -1632,7 +1635,9 @@ int launch_mesh_raster_t(const MeshArgs& a0, hipStream_t stream) {
 
 template <bool BINNED>
 int launch_mesh_raster(const MeshArgs& a, hipStream_t stream) {
-  return a.ties ? launch_mesh_raster_t<BINNED, true>(a, stream) : launch_mesh_raster_t<BINNED, false>(a, stream);
+  // (a null neighbour array selects the instantiations that never read one: stage_chunk's NB)
+  if (a.neighbor == nullptr) return a.ties ? launch_mesh_raster_t<BINNED, true, false>(a, stream) : launch_mesh_raster_t<BINNED, false, false>(a, stream);
+  return a.ties ? launch_mesh_raster_t<BINNED, true, true>(a, stream) : launch_mesh_raster_t<BINNED, false, true>(a, stream);
 }
 
 void set_tiles(MeshArgs* a, int bin_size, int BH, int BW) { a->tm = make_tile_map(a->N, a->H, a->W, bin_size, BH, BW, true); }
@@ -1744,7 +1749,7 @@ static int mesh_naive_impl(MeshArgs a, int64_t F, int32_t* cover, bool with_list
   const int st = cover_begin(&a, cover, with_list, a.overflow == nullptr, s);  // (also for K == 0: nothing is covered)
   if (st != P3D_OK) return st;
   if ((int64_t)a.N * a.H * a.W * a.K == 0) return P3D_OK;
-  if ((!a.face_verts || !a.neighbor) && F > 0) return P3D_ERR_INVALID_ARG;
+  if (!a.face_verts && F > 0) return P3D_ERR_INVALID_ARG;  // (a null neighbor: no face has a clipped neighbour)
   if (!a.mesh_first || !a.mesh_count || !a.p2f || !a.zbuf || !a.bary || !a.dists) return P3D_ERR_INVALID_ARG;
   set_tiles(&a, a.H > a.W ? a.H : a.W, 1, 1);
   return launch_mesh_raster<false>(a, s);
@@ -1761,9 +1766,11 @@ P3D_API int p3d_rasterize_meshes_naive(const float* face_verts, const int64_t* m
                          F, nullptr, false, (hipStream_t)stream);
 }
 
-static int mesh_fine_from_csr(MeshArgs a, const BinCSR& csr, const BinGeom& g, int32_t* cover, bool with_list, hipStream_t s) {
+// zero: the cover is cleared here (false: the count pass of the binning did it, binning.h: BinFused)
+static int mesh_fine_from_csr(MeshArgs a, const BinCSR& csr, const BinGeom& g, int32_t* cover, bool with_list, hipStream_t s,
+                              bool zero = true) {
   a.csr = csr;
-  const int st = cover_begin(&a, cover, with_list, true, s);
+  const int st = cover_begin(&a, cover, with_list, zero, s);
   if (st != P3D_OK) return st;
   set_tiles(&a, g.bin_size, g.BH, g.BW);
   return launch_mesh_raster<true>(a, s);
@@ -1798,11 +1805,40 @@ static int cuda_order_replay(MeshArgs a, const BinCSR* csr, const BinGeom* g, hi
   return launch_status();
 }
 
-P3D_API int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
-                                    const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K, int bin_size,
-                                    int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary,
-                                    float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
-                                    p3d_stream_t stream) {
+// P3D_BIN_CLEARS_COVER=0 (an ablation build): binned launches clear the cover with a memset ahead of the fine kernel, as before
+#ifndef P3D_BIN_CLEARS_COVER
+#define P3D_BIN_CLEARS_COVER 1
+#endif
+
+// what p3d_rasterize_meshes_verts_ex adds to p3d_rasterize_meshes_ex: face_verts is an OUTPUT, gathered from (verts, faces)
+struct VertsIn {
+  const float* verts;
+  const int64_t* faces;
+  int64_t V;
+  float* face_verts;
+  float* face_pre;    // or null
+  float* zero_verts;  // (V, 3) to clear, or null
+};
+
+// the gather and the clear as launches of their own: every launch that has no count pass to carry them
+static int verts_in_standalone(const VertsIn& vi, int64_t F, hipStream_t s) {
+  if (F > 0) {
+    const int st = vi.face_pre != nullptr ? p3d_gather_face_verts_pre(vi.verts, vi.faces, vi.V, F, vi.face_verts, vi.face_pre, s)
+                                          : p3d_gather_face_verts(vi.verts, vi.faces, vi.V, F, vi.face_verts, s);
+    if (st != P3D_OK) return st;
+  }
+  if (vi.zero_verts != nullptr && vi.V > 0 &&
+      hipMemsetAsync(vi.zero_verts, 0, (size_t)vi.V * 3 * sizeof(float), s) != hipSuccess)
+    return P3D_ERR_LAUNCH;
+  return P3D_OK;
+}
+
+// p3d_rasterize_meshes_ex (vi null) and p3d_rasterize_meshes_verts_ex (vi: face_verts == vi->face_verts, not yet written)
+static int rasterize_meshes_impl(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
+                                 const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K, int bin_size,
+                                 int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary,
+                                 float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
+                                 p3d_stream_t stream, const VertsIn* vi) {
   const bool cuda_order = (flags & P3D_RASTER_CUDA_TIE_ORDER) != 0, with_list = (flags & P3D_RASTER_COVER_LIST) != 0;
   if ((flags & ~(P3D_RASTER_COVER_LIST | P3D_RASTER_CUDA_TIE_ORDER)) != 0 || (cuda_order && with_list) || (with_list && cover == nullptr))
     return P3D_ERR_INVALID_ARG;
@@ -1810,6 +1846,12 @@ P3D_API int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh
   if (rc != P3D_OK) return rc;
   hipStream_t s = (hipStream_t)stream;
   const bool any_output = (int64_t)N * H * W * K != 0;
+  // packed vertices: the count pass of a binned launch gathers the faces (below); every other launch gathers them first
+  const bool fuse_verts = vi != nullptr && bin_size > 0 && max_faces_per_bin > 0 && any_output && F > 0;
+  if (vi != nullptr && !fuse_verts) {
+    const int st = verts_in_standalone(*vi, F, s);
+    if (st != P3D_OK) return st;
+  }
   MeshArgs a = mesh_args(face_verts, mesh_first, mesh_count, neighbor, N, H, W, blur_radius, K, persp, clip, cull, p2f, zbuf, bary, dists);
   a.ties = cuda_order ? 1 : 0;
   // CUDA tie order: the lane masks of the marked pixels (MeshArgs::tie_words) live in the LAST bytes of the workspace when it has
@@ -1840,7 +1882,7 @@ P3D_API int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh
   }
   if (cover != nullptr && !any_output) return cover_begin(&a, cover, with_list, true, s);
   if (!any_output) return P3D_OK;
-  if ((!face_verts || !neighbor) && F > 0) return P3D_ERR_INVALID_ARG;
+  if (!face_verts && F > 0) return P3D_ERR_INVALID_ARG;  // (a null neighbor: no face has a clipped neighbour)
   if (!mesh_first || !mesh_count || !p2f || !zbuf || !bary || !dists) return P3D_ERR_INVALID_ARG;
   const BinGeom gu = make_geom(H, W, bin_size);
   if (gu.BH > P3D_MAX_BINS_PER_SIDE || gu.BW > P3D_MAX_BINS_PER_SIDE) return P3D_ERR_TOO_MANY_BINS;
@@ -1860,16 +1902,69 @@ P3D_API int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh
   }
   const bool is_short = ws.capacity < ws.worst;
   a.overflow = is_short ? ws.plan_hdr + 2 : nullptr;
+  // What the count pass takes along (binning.h: BinFused): the cover's words and the list header are cleared by its workgroups
+  // instead of a memset between the fill pass and the fine kernel -- stream order puts the clear three launches ahead of the fine
+  // kernel, and the binning touches only its workspace; with packed vertices also the face gather and the clear of zero_verts.
+  BinFused fz;
+  const size_t cover_words = cover != nullptr ? p3d_rasterize_meshes_cover_bytes(N, H, W) / sizeof(int32_t) : 0;
+  const bool bin_clears_cover = P3D_BIN_CLEARS_COVER && cover_words > 0;
+  if (bin_clears_cover) {
+    fz.zero0 = cover;
+    fz.n0 = (int64_t)cover_words + (with_list ? 16 : 0);
+  }
+  if (fuse_verts) {
+    fz.verts = vi->verts;
+    fz.faces = vi->faces;
+    fz.V = vi->V;
+    fz.E = F;
+    fz.face_verts = vi->face_verts;
+    fz.face_pre = reinterpret_cast<float4*>(vi->face_pre);
+    if (vi->zero_verts != nullptr) {
+      fz.zero1 = reinterpret_cast<int*>(vi->zero_verts);
+      fz.n1 = vi->V * 3;
+    }
+  }
   int st = bin_build(kTriangles, face_verts, nullptr, mesh_first, mesh_count, F, N, g, max_faces_per_bin,
-                     sqrtf(blur_radius), ws, s);
+                     sqrtf(blur_radius), ws, s, true, &fz);
   if (st != P3D_OK) return st;
   BinCSR csr{ws.offset, ws.total, ws.list, TilePlan{ws.arank, ws.bg_list, ws.plan_hdr, ws.order}};
-  st = mesh_fine_from_csr(a, csr, g, cover, with_list, s);
+  st = mesh_fine_from_csr(a, csr, g, cover, with_list, s, !bin_clears_cover);
   if (st == P3D_OK && is_short) st = mesh_naive_impl(a, F, cover, with_list, s);
   if (st != P3D_OK || !cuda_order) return st;
   st = cuda_order_replay(a, &csr, &g, s);
   if (st != P3D_OK || !is_short) return st;
   return cuda_order_replay(a, nullptr, nullptr, s);
+}
+
+P3D_API int p3d_rasterize_meshes_ex(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,
+                                    const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K, int bin_size,
+                                    int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f, float* zbuf, float* bary,
+                                    float* dists, int32_t* cover, unsigned flags, void* workspace, size_t workspace_bytes,
+                                    p3d_stream_t stream) {
+  return rasterize_meshes_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size, max_faces_per_bin,
+                               persp, clip, cull, p2f, zbuf, bary, dists, cover, flags, workspace, workspace_bytes, stream, nullptr);
+}
+
+P3D_API int p3d_rasterize_meshes_verts_ex(const float* verts, const int64_t* faces, int64_t V, float* face_verts, float* face_pre,
+                                          float* zero_verts, const int64_t* mesh_first, const int64_t* mesh_count,
+                                          const int64_t* neighbor, int64_t F, int N, int H, int W, float blur_radius, int K,
+                                          int bin_size, int max_faces_per_bin, int persp, int clip, int cull, int64_t* p2f,
+                                          float* zbuf, float* bary, float* dists, int32_t* cover, unsigned flags, void* workspace,
+                                          size_t workspace_bytes, p3d_stream_t stream) {
+  // everything that can be refused is refused before the first launch (the gather may be that launch)
+  if ((flags & ~(P3D_RASTER_COVER_LIST | P3D_RASTER_CUDA_TIE_ORDER)) != 0 ||
+      ((flags & P3D_RASTER_CUDA_TIE_ORDER) != 0 && (flags & P3D_RASTER_COVER_LIST) != 0) ||
+      ((flags & P3D_RASTER_COVER_LIST) != 0 && cover == nullptr))
+    return P3D_ERR_INVALID_ARG;
+  if (V < 0 || F < 0) return P3D_ERR_INVALID_ARG;
+  if (face_pre != nullptr && (face_verts == nullptr || ((uintptr_t)face_pre & 15u) != 0)) return P3D_ERR_INVALID_ARG;
+  if (F > 0 && (!verts || !faces || !face_verts)) return P3D_ERR_INVALID_ARG;
+  const int rc = check_common(N, H, W, K);
+  if (rc != P3D_OK) return rc;
+  if ((int64_t)N * H * W * K != 0 && (!mesh_first || !mesh_count || !p2f || !zbuf || !bary || !dists)) return P3D_ERR_INVALID_ARG;
+  const VertsIn vi{verts, faces, V, face_verts, face_pre, zero_verts};
+  return rasterize_meshes_impl(face_verts, mesh_first, mesh_count, neighbor, F, N, H, W, blur_radius, K, bin_size, max_faces_per_bin,
+                               persp, clip, cull, p2f, zbuf, bary, dists, cover, flags, workspace, workspace_bytes, stream, &vi);
 }
 
 P3D_API int p3d_rasterize_meshes(const float* face_verts, const int64_t* mesh_first, const int64_t* mesh_count,

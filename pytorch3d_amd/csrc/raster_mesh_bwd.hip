@@ -692,13 +692,16 @@ P3D_API int p3d_rasterize_meshes_backward_ex(const float* face_verts, const int6
                                               int64_t F, int64_t V, int N, int H, int W, int K, int persp, int clip, unsigned flags,
                                               float* grad_out, void* workspace, size_t workspace_bytes, p3d_stream_t stream) {
   if (F < 0 || V < 0 || N < 0 || H < 0 || W < 0 || K < 0) return P3D_ERR_INVALID_ARG;
-  if ((flags & ~(P3D_BWD_COVER_HAS_LIST | P3D_BWD_MAKE_FACE_PRE)) != 0 || ((uintptr_t)face_pre & 15u)) return P3D_ERR_INVALID_ARG;
+  if ((flags & ~(P3D_BWD_COVER_HAS_LIST | P3D_BWD_MAKE_FACE_PRE | P3D_BWD_GRAD_OUT_ZEROED)) != 0 || ((uintptr_t)face_pre & 15u))
+    return P3D_ERR_INVALID_ARG;
   // grad_out: (F, 3, 3) per face, or (V, 3) per vertex through faces
   const int64_t out_floats = faces ? V * 3 : F * 9;
   if (out_floats == 0) return P3D_OK;
   if (!grad_out) return P3D_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(grad_out, 0, (size_t)out_floats * sizeof(float), s) != hipSuccess) return P3D_ERR_LAUNCH;
+  // (P3D_BWD_GRAD_OUT_ZEROED: the caller hands in zeros -- the forward's count pass cleared them, p3d_rasterize_meshes_verts_ex)
+  if ((flags & P3D_BWD_GRAD_OUT_ZEROED) == 0 && hipMemsetAsync(grad_out, 0, (size_t)out_floats * sizeof(float), s) != hipSuccess)
+    return P3D_ERR_LAUNCH;
   if (F == 0 || (int64_t)N * H * W * K == 0) return P3D_OK;
   if (!face_verts || !p2f || !grad_zbuf || !grad_bary || !grad_dists) return P3D_ERR_INVALID_ARG;
   if (flags & P3D_BWD_MAKE_FACE_PRE) {

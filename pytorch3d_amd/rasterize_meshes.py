@@ -87,7 +87,9 @@ def rasterize_meshes(
         mesh_to_face_first_idx = clipped_faces.mesh_to_face_first_idx
         num_faces_per_mesh = clipped_faces.num_faces_per_mesh
         clipped_faces_neighbor_idx = clipped_faces.clipped_faces_neighbor_idx
-    if clipped_faces_neighbor_idx is None:
+    # nothing was clipped: no face has a clipped neighbour.  The nodes below take None for that (a null pointer at the C ABI): no
+    # fill of F x -1 per call, and no read of it per (tile, face) in the fine kernel
+    if clipped_faces_neighbor_idx is None and not _C.NULL_NEIGHBOR:
         clipped_faces_neighbor_idx = torch.full(
             size=(faces_packed.shape[0] if fused_verts else face_verts.shape[0],), fill_value=-1,
             device=verts_packed.device, dtype=torch.int64)
@@ -185,8 +187,11 @@ class _RasterizeFaceVerts(torch.autograd.Function):
 
 
 class _RasterizeMeshVerts(torch.autograd.Function):
-    """`verts_packed[faces_packed]` + _RasterizeFaceVerts as ONE node: forward = the gather kernel + the rasterizer,
-    backward = p3d_rasterize_meshes_backward_ex with faces, which flushes the per-face partials straight to grad_verts."""
+    """`verts_packed[faces_packed]` + _RasterizeFaceVerts as ONE node: forward = p3d_rasterize_meshes_verts_ex (the face gather runs
+    inside the count pass of the binning; _C.FUSED_GATHER off: the gather kernel + the rasterizer), backward =
+    p3d_rasterize_meshes_backward_ex with faces, which flushes the per-face partials straight to grad_verts.  When the vertices need
+    their gradient the forward also allocates the backward's (V, 3) result and has the same pass clear it (_C.PRECLEARED_GRAD): it
+    waits on the node as a plain attribute, for the FIRST backward only."""
 
     @staticmethod
     def forward(ctx, verts, faces, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size,
@@ -201,7 +206,15 @@ class _RasterizeMeshVerts(torch.autograd.Function):
             face_verts = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
             # per-face reciprocals for the backward (include/p3d_amd.h: p3d_gather_face_verts_pre), written by the gather
             face_pre = torch.empty((F, 4), dtype=torch.float32, device=verts.device) if (_C.FACE_PRE and ctx.needs_input_grad[0]) else None
-            if F and face_pre is not None:
+            K, (H, W) = int(faces_per_pixel), image_size
+            fused = (_C.FUSED_GATHER and F > 0 and mesh_to_face_first_idx.shape[0] * H * W * K > 0 and verts_c.dtype == torch.float32
+                     and faces_c.dtype == torch.int64)
+            zeroed = None
+            if fused:
+                # (not under use_deterministic_algorithms: that backward needs no zeros)
+                if _C.PRECLEARED_GRAD and ctx.needs_input_grad[0] and not _C._ordered():
+                    zeroed = torch.empty((V, 3), dtype=torch.float32, device=verts.device)
+            elif F and face_pre is not None:
                 rc = lib.p3d_gather_face_verts_pre(_C._ptr(verts_c), _C._ptr(faces_c), V, F, _C._ptr(face_verts), _C._ptr(face_pre),
                                                    _C._stream(verts.device))
                 _lib.check(rc, "gather_face_verts_pre")
@@ -211,11 +224,13 @@ class _RasterizeMeshVerts(torch.autograd.Function):
                 _lib.check(rc, "gather_face_verts")
         (pix_to_face, zbuf, barycentric_coords, dists), cover = _C._rasterize_meshes_covered(
             face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
-            faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct, clip_barycentric_coords, cull_backfaces)
+            faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct, clip_barycentric_coords, cull_backfaces,
+            packed=(verts_c, faces_c, face_pre, zeroed) if fused else None)
         ctx.save_for_backward(face_verts, faces_c, pix_to_face, cover, face_pre)
         ctx.mark_non_differentiable(pix_to_face)
         ctx.set_materialize_grads(False)
         ctx.V = V
+        ctx.zeroed_grad_verts = zeroed  # an attribute, not a saved tensor: handed to the first backward and dropped there
         ctx.flags = (int(bool(perspective_correct)), int(bool(clip_barycentric_coords)))
         return pix_to_face, zbuf, barycentric_coords, dists
 
@@ -225,8 +240,11 @@ class _RasterizeMeshVerts(torch.autograd.Function):
         cover = _C.checked_cover(pix_to_face, cover)  # (P3D_CHECK=1: verified on the device before it is trusted)
         if grad_zbuf is None and grad_barycentric_coords is None and grad_dists is None:
             return (None,) * 13
+        # the buffer the forward cleared serves ONE backward (it becomes that backward's result): a second backward of the node
+        # (retain_graph=True) finds None here, allocates its own and clears it in the call
+        zeroed, ctx.zeroed_grad_verts = getattr(ctx, "zeroed_grad_verts", None), None
         grad_verts = _C._mesh_backward(face_verts, faces, ctx.V, pix_to_face, grad_zbuf, grad_barycentric_coords, grad_dists,
-                                       *ctx.flags, cover, face_pre)
+                                       *ctx.flags, cover, face_pre, zeroed_out=zeroed)
         return (grad_verts,) + (None,) * 12
 
 
