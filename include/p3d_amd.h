@@ -1005,6 +1005,67 @@ int p3d_iou_box3d(const float* boxes1, const float* boxes2, int64_t N, int64_t M
                   void* workspace, size_t workspace_bytes, p3d_stream_t stream);
 int p3d_iou_box3d_host(const float* boxes1, const float* boxes2, int64_t N, int64_t M, float* vol, float* iou);
 
+/* ---- graph convolution: per-vertex sums of neighbour rows (csrc/graph_conv.hip) ---- */
+
+/* The neighbour sum of pytorch3d.ops.GraphConv / gather_scatter (gather_scatter/gather_scatter.h) through an inverted index, forward
+ * and backward (the backward is the same call on the transposed table):
+ *   out[v, :] = (base ? base[v, :] : +0.0f) + (((+0.0f + rows[e_0, :]) + rows[e_1, :]) + ...),   e_i = entries[offsets[v] + i],
+ * in list order, in float32.  rows: n_rows rows of D floats, rows_stride floats apart; base (or NULL) and out: V rows of D floats at
+ * base_stride / out_stride; offsets (V + 1) and entries (n_entries) int32.  Offsets outside [0, n_entries] are clamped and entries
+ * outside [0, n_rows) skipped: a broken table gives wrong sums, never a read outside the arrays.  No atomic, no zero fill, no
+ * workspace; every (v, d) is summed by one lane, so the bits are the same for every launch shape, run and stream.  A row of any
+ * length is summed sequentially.  float4 requests when D, the strides and the pointers allow it (multiples of 4 / 16 bytes), else
+ * dwords; the results are the same.  The grid is at most P3D_NEIGHBOR_SUM_MAX_GROUPS workgroups of 256 lanes, each serving
+ * 256 / lanes_per_row vertices per round (lanes_per_row = min(64, next_pow2(D / 4 or D))), and loops beyond that.
+ * V, D or n_entries of 0: P3D_OK without a gather (n_entries of 0 still writes base or zeros; offsets and entries are not read).
+ * Negative sizes, n_entries > INT32_MAX, out_stride < D, a negative stride or a missing pointer: P3D_ERR_INVALID_ARG.  No host sync. */
+#define P3D_NEIGHBOR_SUM_MAX_GROUPS 2048
+int p3d_neighbor_sum(const float* rows, int64_t rows_stride, int64_t n_rows, const float* base, int64_t base_stride,
+                     const int32_t* offsets, const int32_t* entries, int64_t V, int64_t n_entries, int64_t D, float* out,
+                     int64_t out_stride, p3d_stream_t stream);
+
+/* ---- vert_align: image features pooled at vertex positions (csrc/vert_align.hip) ---- */
+
+/* pytorch3d.ops.vert_align for one feature map: ATen's grid_sampler_2d restated in float32 (bilinear or nearest; zeros or border
+ * padding; align_corners or not -- the flags below).  The source coordinate of c on an axis of S pixels is ((c + 1) / 2) * (S - 1)
+ * with P3D_VERT_ALIGN_CORNERS, ((c + 1) * S - 1) / 2 without.  Border: clamped to [0, S - 1], NaN -> 0, gradient 0 where it was at
+ * or beyond an end.  Bilinear: x0 = floor(ix), y0 = floor(iy), corners nw, ne, sw, se with weights (x0+1-ix)(y0+1-iy), (ix-x0)(y0+1-iy),
+ * (x0+1-ix)(iy-y0), (ix-x0)(iy-y0), the in-range corners summed in that order from +0.  Nearest: round half to even; no coordinate
+ * gradient.  OUTSIDE WHAT THE REFERENCE PINS: under zeros padding a source coordinate that is not finite or does not fit an int32
+ * (tested as a float, before the conversion) makes the sample empty -- a zero row, zero gradients.
+ * feat (N,C,H,W) f32 read through its four element strides (NCHW, channels-last and sliced views alike); verts (N,V,>=2) f32 read
+ * through v_sn, v_sv, v_sd (x, then y one v_sd on).  Row r of the output is the padded vertex packed_idx[r] (int64, an index into
+ * (N*V); outside it: an empty sample), or r itself when packed_idx is NULL (then n_rows <= N*V).  forward writes out[r*out_stride + c],
+ * c < C: `out` points at this map's column block of a wider (rows, sum C) tensor.  float4 requests when f_sc == 1 and C, the strides
+ * and the pointers are multiples of 4 floats / 16 bytes, else dwords; the same results.
+ * backward: grad_out as `out`; grad_verts (N,V,3) contiguous or NULL, ADDED to (zero-fill once, then one call per map): the x and y
+ * gradients, z untouched, a gather without atomics; grad_feat (strides g_*) zero-filled by the caller or NULL: float atomics.
+ * Ordered form of grad_feat (no atomics, the same bits on every run): p3d_vert_align_keys writes for sample 4 r + k the pixel
+ * n*H*W + y*W + x of corner k of row r or -1; the caller sorts the samples stably by key (sorted_samples, int64) and
+ * p3d_vert_align_ordered_backward sums them (ordered_sum.h; channels in chunks of 4; workspace of p3d_vert_align_workspace_bytes,
+ * smaller: P3D_ERR_WORKSPACE).  N*H*W >= 2^31 or 4 n_rows > INT32_MAX: P3D_ERR_UNSUPPORTED from both.
+ * n_rows or C of 0: P3D_OK without a launch.  Unknown flags, negative sizes, missing pointers: P3D_ERR_INVALID_ARG.  No host sync. */
+#define P3D_VERT_ALIGN_NEAREST 1u
+#define P3D_VERT_ALIGN_BORDER 2u
+#define P3D_VERT_ALIGN_CORNERS 4u
+#define P3D_VERT_ALIGN_MAX_GROUPS 4096
+int p3d_vert_align_forward(const float* feat, int64_t N, int64_t C, int64_t H, int64_t W, int64_t f_sn, int64_t f_sc, int64_t f_sh,
+                           int64_t f_sw, const float* verts, int64_t V, int64_t v_sn, int64_t v_sv, int64_t v_sd,
+                           const int64_t* packed_idx, int64_t n_rows, unsigned flags, float* out, int64_t out_stride,
+                           p3d_stream_t stream);
+int p3d_vert_align_backward(const float* grad_out, int64_t go_stride, const float* feat, int64_t N, int64_t C, int64_t H, int64_t W,
+                            int64_t f_sn, int64_t f_sc, int64_t f_sh, int64_t f_sw, const float* verts, int64_t V, int64_t v_sn,
+                            int64_t v_sv, int64_t v_sd, const int64_t* packed_idx, int64_t n_rows, unsigned flags, float* grad_feat,
+                            int64_t g_sn, int64_t g_sc, int64_t g_sh, int64_t g_sw, float* grad_verts, p3d_stream_t stream);
+size_t p3d_vert_align_workspace_bytes(int64_t n_rows, int64_t C);
+int p3d_vert_align_keys(int64_t N, int64_t H, int64_t W, const float* verts, int64_t V, int64_t v_sn, int64_t v_sv, int64_t v_sd,
+                        const int64_t* packed_idx, int64_t n_rows, unsigned flags, int32_t* keys, p3d_stream_t stream);
+int p3d_vert_align_ordered_backward(const float* grad_out, int64_t go_stride, int64_t N, int64_t C, int64_t H, int64_t W,
+                                    const float* verts, int64_t V, int64_t v_sn, int64_t v_sv, int64_t v_sd,
+                                    const int64_t* packed_idx, int64_t n_rows, unsigned flags, const int32_t* keys,
+                                    const int64_t* sorted_samples, float* grad_feat, int64_t g_sn, int64_t g_sc, int64_t g_sh,
+                                    int64_t g_sw, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+
 /* ---- built-in per-kernel timing (HIP events on the launch stream) --------------------- */
 
 /* enable != 0: every kernel launch is bracketed by hipEventRecord on its stream. */

@@ -1259,6 +1259,140 @@ def iou_box3d_host(boxes1, boxes2):
 
 
 # ----------------------------------------------------------------------------------------------
+# GraphConv / gather_scatter neighbour sums (csrc/graph_conv.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the name of
+# GRAPH_EXPORTS to pytorch3d_amd.graph_conv.gather_scatter_op, which builds (or recalls) the table and comes here.
+def neighbor_sum(rows, offsets, entries, base=None):
+    """p3d_neighbor_sum (include/p3d_amd.h): out (V, D) float32 with out[v] = (base[v] or +0) + the rows of v's entries in list order.
+    rows (n_rows, D) and base (V, D) float32 GPU tensors whose last dimension is contiguous (any row stride: views are read in
+    place); offsets (V + 1,) and entries (n_entries,) contiguous int32.  No atomics, no zero fill; the same bits on every run."""
+    who = "neighbor_sum"
+    named = [("rows", rows), ("offsets", offsets), ("entries", entries)] + ([("base", base)] if base is not None else [])
+    dev = _same_device(*named)
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise RuntimeError(f"{who}: rows must be (n_rows, D) float32, got {tuple(rows.shape)} {rows.dtype}")
+    if offsets.dim() != 1 or offsets.numel() < 1 or offsets.dtype != torch.int32 or entries.dim() != 1 or entries.dtype != torch.int32:
+        raise RuntimeError(f"{who}: offsets (V + 1,) and entries (n_entries,) must be int32")
+    n_rows, D = rows.shape
+    V = offsets.numel() - 1
+    if base is not None and (base.dtype != torch.float32 or tuple(base.shape) != (V, D)):
+        raise RuntimeError(f"{who}: base must be ({V}, {D}) float32, got {tuple(base.shape)} {base.dtype}")
+
+    def row_view(t):  # rows of D contiguous floats at a non-negative stride; anything else is copied
+        return t if t.numel() == 0 or D == 1 and t.stride(0) >= 0 or t.stride(1) == 1 and t.stride(0) >= 0 else t.contiguous()
+
+    rows = row_view(rows)
+    base = row_view(base) if base is not None else None
+    offsets, entries = offsets.contiguous(), entries.contiguous()
+    with torch.cuda.device(dev):
+        out = torch.empty((V, D), dtype=torch.float32, device=dev)
+        if V * D == 0:
+            return out
+        rc = _lib.load().p3d_neighbor_sum(_ptr(rows), rows.stride(0) if rows.numel() else 0, n_rows, _ptr(base),
+                                          base.stride(0) if base is not None else 0, _ptr(offsets), _ptr(entries), V,
+                                          entries.numel(), D, _ptr(out), D, _stream(dev))
+        _lib.check(rc, who)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# vert_align (csrc/vert_align.hip).  No `_C` operator of the reference stands behind it (its vert_align is torch): used by
+# pytorch3d_amd.vert_align alone.
+VERT_ALIGN_CALLS = {"atomic": 0, "ordered": 0}  # backwards of grad_feats by path (tests read it)
+# A map whose channels are NOT adjacent in memory (NCHW) sends the 64 lanes of an atomic wave-instruction to 64 different lines; on one
+# MI355X that ran 4.5 ms against the torch chain's 3.1 ms and the ordered form's 1.4 ms at (32, 256, 56, 56)
+# (profiles/mesh_refine_mi355x.txt; 512 channels alike).  From this many channels on such a map takes the ordered form even without
+# the deterministic flag; below it (not measured) the sort is assumed to cost more than the atomics.
+VERT_ALIGN_STRIDED_ORDERED_MIN_C = 32
+
+
+def _vert_align_args(who, feats, grid, packed_idx):
+    named = [("verts", grid)] + [("feats[%d]" % i, f) for i, f in enumerate(feats)] + ([("packed_idx", packed_idx)] if packed_idx is not None else [])
+    dev = _same_device(*named)
+    if grid.dim() != 3 or grid.shape[2] < 2 or grid.dtype != torch.float32:
+        raise RuntimeError(f"{who}: verts must be (N, V, >= 2) float32, got {tuple(grid.shape)} {grid.dtype}")
+    for f in feats:
+        if f.dim() != 4 or f.dtype != torch.float32 or f.shape[0] != grid.shape[0]:
+            raise RuntimeError(f"{who}: every feature map must be (N, C, H, W) float32 with the verts' N, got {tuple(f.shape)} {f.dtype}")
+        if f.numel() and min(f.stride()) < 0:
+            raise RuntimeError(f"{who}: negative strides are not supported")
+    if packed_idx is not None and (packed_idx.dim() != 1 or packed_idx.dtype != torch.int64):
+        raise RuntimeError(f"{who}: packed_idx must be (rows,) int64")
+    N, V = grid.shape[:2]
+    rows = N * V if packed_idx is None else packed_idx.numel()
+    return dev, N, V, rows, (None if packed_idx is None else packed_idx.contiguous())
+
+
+def vert_align_forward(feats, grid, packed_idx, flags):
+    """(rows, sum C) float32: one launch per map of `feats` into its column block (p3d_vert_align_forward, include/p3d_amd.h).
+    grid (N, V, >= 2) and the maps are read through their strides; packed_idx: the padded vertex of every output row, or None."""
+    who = "vert_align_forward"
+    dev, N, V, rows, packed_idx = _vert_align_args(who, feats, grid, packed_idx)
+    total = sum(f.shape[1] for f in feats)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        out = torch.empty((rows, total), dtype=torch.float32, device=dev)
+        col = 0
+        for f in feats:
+            C, H, W = f.shape[1:]
+            if H * W == 0 and rows * C:
+                raise RuntimeError(f"{who}: a feature map without pixels")
+            if rows * C:
+                rc = lib.p3d_vert_align_forward(_ptr(f), N, C, H, W, *f.stride(), _ptr(grid), V, *grid.stride(), _ptr(packed_idx), rows,
+                                                flags, ctypes.c_void_p(out.data_ptr() + 4 * col), total, _stream(dev))
+                _lib.check(rc, who)
+            col += C
+    return out
+
+
+def vert_align_backward(grad_out, feats, grid, packed_idx, flags, need_feats, need_verts):
+    """(list of grad_feats or None per map, grad_verts (N, V, 3) or None) for grad_out (rows, sum C).  grad_verts is a gather;
+    grad_feats float atomics, or the keys / stable sort / segmented sum form (the same bits on every run): under _ordered() always,
+    else for a map without adjacent channels from VERT_ALIGN_STRIDED_ORDERED_MIN_C channels on.  Under _ordered() a map whose
+    N * H * W does not fit an int32 cannot be keyed: NotImplementedError, and the caller falls back."""
+    who = "vert_align_backward"
+    dev, N, V, rows, packed_idx = _vert_align_args(who, feats, grid, packed_idx)
+    total = sum(f.shape[1] for f in feats)
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (rows, total) or grad_out.device != dev:
+        raise RuntimeError(f"{who}: grad_out must be ({rows}, {total}) float32 on {dev}")
+    grad_out = grad_out.contiguous()
+    strict = _ordered()
+    if strict and any(nf and N * f.shape[2] * f.shape[3] > MAX_INT for f, nf in zip(feats, need_feats)):
+        raise NotImplementedError(f"{who}: the deterministic form keys a pixel by an int32 and N * H * W does not fit")
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        grad_verts = torch.zeros((N, V, 3), dtype=torch.float32, device=dev) if need_verts else None
+        grads = []
+        col = 0
+        for f, nf in zip(feats, need_feats):
+            C, H, W = f.shape[1:]
+            gf = torch.zeros_like(f) if nf else None
+            go = ctypes.c_void_p(grad_out.data_ptr() + 4 * col)
+            ordered = strict or (f.stride(1) != 1 and C >= VERT_ALIGN_STRIDED_ORDERED_MIN_C and N * H * W <= MAX_INT)
+            if rows * C and H * W and (nf or need_verts):
+                atomic = nf and not ordered
+                if atomic or need_verts:
+                    rc = lib.p3d_vert_align_backward(go, total, _ptr(f), N, C, H, W, *f.stride(), _ptr(grid), V, *grid.stride(), _ptr(packed_idx),
+                                                     rows, flags, _ptr(gf) if atomic else None, *(gf.stride() if atomic else (0, 0, 0, 0)),
+                                                     _ptr(grad_verts), _stream(dev))
+                    _lib.check(rc, who)
+                if nf and ordered:
+                    keys = torch.empty((rows * 4,), dtype=torch.int32, device=dev)
+                    rc = lib.p3d_vert_align_keys(N, H, W, _ptr(grid), V, *grid.stride(), _ptr(packed_idx), rows, flags, _ptr(keys), _stream(dev))
+                    _lib.check(rc, who)
+                    order = torch.sort(keys, stable=True).indices
+                    nbytes = lib.p3d_vert_align_workspace_bytes(rows, C)
+                    ws = _workspace(nbytes, dev)
+                    rc = lib.p3d_vert_align_ordered_backward(go, total, N, C, H, W, _ptr(grid), V, *grid.stride(), _ptr(packed_idx), rows, flags,
+                                                             _ptr(keys), _ptr(order), _ptr(gf), *gf.stride(), _ptr(ws), nbytes, _stream(dev))
+                    _lib.check(rc, who)
+                if nf:
+                    VERT_ALIGN_CALLS["ordered" if ordered else "atomic"] += 1
+            grads.append(gf)
+            col += C
+    return grads, grad_verts
+
+
+# ----------------------------------------------------------------------------------------------
 # point clouds into voxel grids (csrc/points_to_volumes.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
 # POINTS_TO_VOLUMES_EXPORTS to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op), which come here for float32 GPU tensors
 # and own a torch formulation of the same contract for CPU tensors.
@@ -1511,6 +1645,8 @@ POINT_CLOUD_EXPORTS = ("sample_farthest_points", "ball_query")
 POINTS_TO_VOLUMES_EXPORTS = ("points_to_volumes_forward", "points_to_volumes_backward")
 # bound by shim.make_module to the wrapper of pytorch3d_amd.iou_box3d (<name>_op)
 BOX3D_EXPORTS = ("iou_box3d",)
+# bound by shim.make_module to the wrapper of pytorch3d_amd.graph_conv (gather_scatter_op)
+GRAPH_EXPORTS = ("gather_scatter",)
 
 
 HOT_PATH_EXPORTS = (

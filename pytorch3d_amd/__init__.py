@@ -20,6 +20,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     estimate_pointcloud_normals, estimate_pointcloud_local_coord_frames, point_covariances  normals, curvatures and local frames of a
                                      point cloud from its K nearest neighbours, one launch, nothing of size K per point materialised
     box3d_overlap                    exact intersection volume and IoU of oriented 3D boxes, one wave per pair, no list cap
+    gather_scatter, graph_conv, graph_topology  GraphConv's neighbour sums through an inverted index: list order, no atomics, one node
+    vert_align                       image features pooled at the vertices: one launch per map, strided maps, packed rows direct
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -31,6 +33,7 @@ from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_al
 from .chamfer import chamfer_distance  # noqa: F401
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
+from .graph_conv import gather_scatter, graph_conv, graph_topology, topology_of_edges  # noqa: F401
 from .iou_box3d import box3d_overlap  # noqa: F401
 from .knn import knn_gather, knn_points  # noqa: F401
 from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
@@ -51,5 +54,6 @@ from .shading import (flat_shading, gouraud_shading, phong_shading, phong_shadin
 from .splatter import SplatterBlender, phong_shading_with_pixels, splatter_blend  # noqa: F401
 from .structures import PackedMeshes, PackedPointclouds  # noqa: F401
 from .textures import sample_textures_atlas, sample_textures_uv  # noqa: F401
+from .vert_align import vert_align  # noqa: F401
 
 __version__ = "0.2.0"

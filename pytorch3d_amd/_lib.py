@@ -36,6 +36,10 @@ FRAMES_ROWS_PER_GROUP = 64  # P3D_FRAMES_ROWS_PER_GROUP: query rows of one workg
 BOX3D_LDS_CAPACITY = 64     # P3D_BOX3D_LDS_CAPACITY: triangles per fragment list of csrc/box3d.hip's first launch
 BOX3D_WAVES_PER_GROUP = 4   # P3D_BOX3D_WAVES_PER_GROUP: pairs per workgroup and round of that launch
 BOX3D_MAX_GROUPS = 4096     # P3D_BOX3D_MAX_GROUPS: its largest grid; more pairs take the grid-stride loop
+NEIGHBOR_SUM_MAX_GROUPS = 2048  # P3D_NEIGHBOR_SUM_MAX_GROUPS: the largest grid of csrc/graph_conv.hip; more row groups take the grid-stride loop
+NEIGHBOR_SUM_GROUP_LANES = 256  # lanes of one of its workgroups: 256 / lanes_per_row vertices per round
+VERT_ALIGN_NEAREST, VERT_ALIGN_BORDER, VERT_ALIGN_CORNERS = 1, 2, 4  # P3D_VERT_ALIGN_*: flags of csrc/vert_align.hip
+VERT_ALIGN_MAX_GROUPS = 4096  # P3D_VERT_ALIGN_MAX_GROUPS: its largest grid
 FPS_REGISTER_POINTS = 16384  # P3D_FPS_REGISTER_POINTS: the largest cloud the register form of farthest point sampling holds
 POINT_MESH_POINT, POINT_MESH_SEGMENT, POINT_MESH_TRIANGLE = 0, 1, 2  # P3D_POINT_MESH_*: the kind of a query / target object
 POINT_MESH_TILE = 64                # P3D_POINT_MESH_TILE: target records staged per wave and step
@@ -234,6 +238,16 @@ _SIGNATURES = {
     "p3d_iou_box3d_workspace_bytes": (c_size, [c_i64, c_i64]),
     "p3d_iou_box3d": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "p3d_iou_box3d_host": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    # GraphConv / gather_scatter neighbour sums (csrc/graph_conv.hip): one entry, forward and backward
+    "p3d_neighbor_sum": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
+    # vert_align (csrc/vert_align.hip): one feature map per call; the ordered grad_feat is keys + a stable sort + the segmented sum
+    "p3d_vert_align_forward": (c_int, [c_ptr] + [c_i64] * 8 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr, c_i64, c_ptr]),
+    "p3d_vert_align_backward": (c_int, [c_ptr, c_i64, c_ptr] + [c_i64] * 8 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr]
+                                + [c_i64] * 4 + [c_ptr, c_ptr]),
+    "p3d_vert_align_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "p3d_vert_align_keys": (c_int, [c_i64] * 3 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr, c_ptr]),
+    "p3d_vert_align_ordered_backward": (c_int, [c_ptr] + [c_i64] * 5 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr, c_ptr, c_ptr]
+                                        + [c_i64] * 4 + [c_ptr, c_size, c_ptr]),
     "p3d_profile_enable": (None, [c_int]),
     "p3d_profile_collect": (None, []),
     "p3d_profile_num_entries": (c_int, []),

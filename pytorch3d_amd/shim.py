@@ -16,7 +16,8 @@ unmodified `pytorch3d.ops.sample_farthest_points` runs, and so does the forward 
 `_C.knn_points_backward`, which stays a stub -- patch_python replaces the whole function.  And `_C.points_to_volumes_forward` /
 `_backward` (csrc/points_to_volumes.hip): the unmodified `pytorch3d.ops.add_pointclouds_to_volumes` runs, forward and backward.
 And `_C.iou_box3d` (csrc/box3d.hip: the kernels for GPU tensors, the library's host loop for CPU tensors): the unmodified
-`pytorch3d.ops.box3d_overlap` runs on both.
+`pytorch3d.ops.box3d_overlap` runs on both.  And `_C.gather_scatter` (csrc/graph_conv.hip): the unmodified `pytorch3d.ops.GraphConv`
+runs on the GPU, forward and backward, its neighbour sums added in list order instead of by float atomics.
 
     shim.install(patch_python=True)
 
@@ -80,6 +81,14 @@ reference classes runs on them end to end:
                                                                  torch formulation
     ops.iou_box3d.box3d_overlap                               -> pytorch3d_amd.iou_box3d.box3d_overlap: the same operator (csrc/box3d.hip)
                                                                  behind input checks that cost one host sync instead of four
+    ops.graph_conv.GraphConv.forward, ops.graph_conv.gather_scatter
+                                                              -> pytorch3d_amd.graph_conv.graph_conv / gather_scatter: one autograd
+                                                                 node writes w0 x + the neighbour sums (csrc/graph_conv.hip; no zero
+                                                                 fill, no separate add, no atomics)
+    ops.vert_align.vert_align                                 -> pytorch3d_amd.vert_align.vert_align: one launch per feature map into
+                                                                 one output, strided maps, packed rows straight from the index
+                                                                 (csrc/vert_align.hip); an ordered grad_feats under
+                                                                 torch.use_deterministic_algorithms(True)
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -141,6 +150,10 @@ def make_module(flavour="ctypes"):
     # float32 CPU boxes.  Both flavours serve this wrapper.
     for name in _ours.BOX3D_EXPORTS:
         setattr(mod, name, getattr(importlib.import_module(__package__ + ".iou_box3d"), name + "_op"))
+    # GraphConv's neighbour sum (pytorch3d_amd/graph_conv.py): csrc/graph_conv.hip's kernel for float32 GPU tensors, the torch formulation
+    # of the same list order for everything else; the table of an edge tensor is cached.  Both flavours serve this wrapper.
+    for name in _ours.GRAPH_EXPORTS:
+        setattr(mod, name, getattr(importlib.import_module(__package__ + ".graph_conv"), name + "_op"))
     if flavour == "pybind":
         # the compiled boundary has the two face operators too: the same arguments that take the HIP kernels above take them there
         def compiled(name):
@@ -394,6 +407,70 @@ def patch_reference_python():
     _patch_points_to_volumes()
     _patch_points_normals()
     _patch_box3d_overlap()
+    _patch_graph_conv()
+    _patch_vert_align()
+
+
+def _patch_vert_align():
+    """pytorch3d.ops.vert_align.vert_align -> this package's function, in every module that copied the name (pytorch3d.ops).  There
+    is no `_C` operator under the reference's function (it is F.grid_sample and copies), so plain install() leaves it alone.
+    PATCH_CALLS counts float32 GPU calls in a mode the kernels cover as fused, the reference's chain restated as fallbacks."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".vert_align")
+    try:  # every module that copied the name must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.ops.vert_align")
+        importlib.import_module("pytorch3d.ops")
+    except ImportError:  # a reference checkout without the module: nothing to patch
+        return
+
+    def vert_align(feats, verts, return_packed=False, interp_mode="bilinear", padding_mode="zeros", align_corners=True):
+        out = ours.vert_align(feats, verts, return_packed, interp_mode, padding_mode, align_corners)
+        _count("vert_align", ours.kernel_path(feats, verts, interp_mode, padding_mode))  # (a call that raised is not counted)
+        return out
+
+    orig = ref.vert_align
+    vert_align.__doc__ = getattr(orig, "__doc__", None)
+    vert_align.__wrapped__ = orig
+    vert_align.__p3d_amd__ = True
+    _replace_everywhere(orig, vert_align)
+
+
+def _patch_graph_conv():
+    """pytorch3d.ops.graph_conv.GraphConv.forward -> pytorch3d_amd.graph_conv.graph_conv (the two F.linear calls, then ONE node that
+    writes w0 x + the neighbour sums), and pytorch3d.ops.graph_conv.gather_scatter -> this package's, in every module that copied the
+    name.  PATCH_CALLS counts float32 GPU calls (the kernel) as fused and everything else (the torch formulation) as fallbacks."""
+    import importlib
+
+    ours = importlib.import_module(__package__ + ".graph_conv")
+    try:  # every module that copied the names must be loaded before rebinding
+        ref = importlib.import_module("pytorch3d.ops.graph_conv")
+        importlib.import_module("pytorch3d.ops")
+    except ImportError:  # a reference checkout without the module: nothing to patch
+        return
+
+    def gather_scatter(input, edges, directed=False):
+        out = ours.gather_scatter(input, edges, directed)
+        _count("gather_scatter", ours.kernel_path(input))  # (a call that raised is not counted)
+        return out
+
+    orig = ref.gather_scatter
+    gather_scatter.__doc__ = getattr(ref.GatherScatter.forward, "__doc__", None)
+    gather_scatter.__wrapped__ = orig
+    gather_scatter.__p3d_amd__ = True
+    _replace_everywhere(orig, gather_scatter)
+
+    orig_forward = ref.GraphConv.forward
+
+    def forward(self, verts, edges):
+        out = ours.graph_conv(verts, edges, self.w0.weight, self.w0.bias, self.w1.weight, self.w1.bias, self.directed)
+        _count("GraphConv.forward", ours.kernel_path(verts))
+        return out
+
+    forward.__doc__ = orig_forward.__doc__
+    forward.__wrapped__ = orig_forward
+    ref.GraphConv.forward = forward
+    _PATCHED.append((ref.GraphConv, "forward", orig_forward, forward))
 
 
 def _patch_box3d_overlap():
