@@ -22,8 +22,8 @@ MAX_UINT = 4294967295
 MAX_USHORT = 65535
 PULSAR_MAX_GRAD_SPHERES = 128
 
-kMaxPointsPerPixel = 150
-kMaxItemsPerBin = 22
+kMaxPointsPerPixel = _lib.MAX_K
+kMaxItemsPerBin = _lib.MAX_BINS_PER_SIDE + 1
 
 
 def _ptr(t):
@@ -633,7 +633,7 @@ def _point_outputs(N, H, W, K, device):
     return idx, zbuf, dists
 
 
-_SPLAT_MODES = {"alpha": 0, "norm": 1}  # P3D_COMPOSITE_ALPHA / _NORM_SUM: AlphaCompositor / NormWeightedCompositor
+_SPLAT_MODES = {"alpha": _lib.COMPOSITE_ALPHA, "norm": _lib.COMPOSITE_NORM_SUM}  # AlphaCompositor / NormWeightedCompositor
 
 
 def _rasterize_points(who, points, cloud_to_packed_first_idx, num_points_per_cloud, image_size, radius, points_per_pixel, bin_size,
@@ -812,7 +812,7 @@ def rasterize_points_composite_backward(points, features, idxs, dists, grad_imag
 # ----------------------------------------------------------------------------------------------
 # compositors
 # ----------------------------------------------------------------------------------------------
-_ALPHA, _NORM, _SUM = 0, 1, 2
+_ALPHA, _NORM, _SUM = _lib.COMPOSITE_ALPHA, _lib.COMPOSITE_NORM_SUM, _lib.COMPOSITE_SUM
 
 
 def _strides4(t):
@@ -1104,9 +1104,8 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _nee
 
 
 # ----------------------------------------------------------------------------------------------
-# farthest point sampling and ball query (csrc/fps_ball.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
-# POINT_CLOUD_EXPORTS to the wrappers of pytorch3d_amd.sample_farthest_points / pytorch3d_amd.ball_query, which come here for float32
-# GPU tensors with D in (2, 3) and own a torch formulation for everything else.
+# farthest point sampling and ball query (csrc/fps_ball.hip), behind the wrappers of pytorch3d_amd.sample_farthest_points /
+# pytorch3d_amd.ball_query (shim.EXPORTS), which come here for float32 GPU tensors with D in (2, 3).
 def _int64_arg(t, N, dev, name, who):
     if t is None:
         return None
@@ -1206,8 +1205,8 @@ def point_frames(points, lengths, K, disambiguate_directions=True, frames=True, 
 
 
 # ----------------------------------------------------------------------------------------------
-# box3d_overlap (csrc/box3d.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the name of BOX3D_EXPORTS to
-# pytorch3d_amd.iou_box3d.iou_box3d_op, which comes here: iou_box3d for GPU tensors, iou_box3d_host for CPU tensors.
+# box3d_overlap (csrc/box3d.hip), behind pytorch3d_amd.iou_box3d.iou_box3d_op (shim.EXPORTS): iou_box3d for GPU tensors,
+# iou_box3d_host for CPU tensors.
 def _check_boxes(boxes1, boxes2, who):
     for name, b in (("boxes1", boxes1), ("boxes2", boxes2)):
         if b.dim() != 3 or tuple(b.shape[1:]) != (8, 3):
@@ -1259,8 +1258,8 @@ def iou_box3d_host(boxes1, boxes2):
 
 
 # ----------------------------------------------------------------------------------------------
-# GraphConv / gather_scatter neighbour sums (csrc/graph_conv.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the name of
-# GRAPH_EXPORTS to pytorch3d_amd.graph_conv.gather_scatter_op, which builds (or recalls) the table and comes here.
+# GraphConv / gather_scatter neighbour sums (csrc/graph_conv.hip), behind pytorch3d_amd.graph_conv.gather_scatter_op (shim.EXPORTS),
+# which builds (or recalls) the table and comes here.
 def neighbor_sum(rows, offsets, entries, base=None):
     """p3d_neighbor_sum (include/p3d_amd.h): out (V, D) float32 with out[v] = (base[v] or +0) + the rows of v's entries in list order.
     rows (n_rows, D) and base (V, D) float32 GPU tensors whose last dimension is contiguous (any row stride: views are read in
@@ -1393,9 +1392,8 @@ def vert_align_backward(grad_out, feats, grid, packed_idx, flags, need_feats, ne
 
 
 # ----------------------------------------------------------------------------------------------
-# point clouds into voxel grids (csrc/points_to_volumes.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the two names of
-# POINTS_TO_VOLUMES_EXPORTS to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op), which come here for float32 GPU tensors
-# and own a torch formulation of the same contract for CPU tensors.
+# point clouds into voxel grids (csrc/points_to_volumes.hip), behind the wrappers of pytorch3d_amd.points_to_volumes (shim.EXPORTS),
+# which come here for float32 GPU tensors.
 POINTS_TO_VOLUMES_CALLS = {"atomic": 0, "ordered": 0}  # forward launches by form: what actually ran (tests read it)
 
 
@@ -1499,8 +1497,7 @@ def points_to_volumes_backward(points_3d, points_features, grid_sizes, mask, poi
 
 
 # ----------------------------------------------------------------------------------------------
-# point-mesh distances (csrc/point_mesh.hip).  NOT in HOT_PATH_EXPORTS: shim.make_module binds the eight names to
-# pytorch3d_amd.point_mesh, which comes here for float32 GPU tensors and owns a torch formulation for everything else.
+# point-mesh distances (csrc/point_mesh.hip), behind pytorch3d_amd.point_mesh (shim.EXPORTS), which comes here for float32 GPU tensors.
 _PM_KINDS = {"point_face": (_lib.POINT_MESH_POINT, _lib.POINT_MESH_TRIANGLE), "face_point": (_lib.POINT_MESH_TRIANGLE, _lib.POINT_MESH_POINT),
              "point_edge": (_lib.POINT_MESH_POINT, _lib.POINT_MESH_SEGMENT), "edge_point": (_lib.POINT_MESH_SEGMENT, _lib.POINT_MESH_POINT)}
 
@@ -1639,16 +1636,12 @@ def edge_point_dist_backward(points, segms, idxs, grad_dists):
 
 POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
-# bound by shim.make_module to the wrappers of pytorch3d_amd.sample_farthest_points / pytorch3d_amd.ball_query (<name>_op)
+# operators both flavours serve through Python wrappers of their own modules (shim.EXPORTS holds the whole table)
 POINT_CLOUD_EXPORTS = ("sample_farthest_points", "ball_query")
-# bound by shim.make_module to the wrappers of pytorch3d_amd.points_to_volumes (<name>_op)
-POINTS_TO_VOLUMES_EXPORTS = ("points_to_volumes_forward", "points_to_volumes_backward")
-# bound by shim.make_module to the wrapper of pytorch3d_amd.iou_box3d (<name>_op)
 BOX3D_EXPORTS = ("iou_box3d",)
-# bound by shim.make_module to the wrapper of pytorch3d_amd.graph_conv (gather_scatter_op)
 GRAPH_EXPORTS = ("gather_scatter",)
 
-
+# the reference's hot path: what each flavour implements itself (the pybind flavour reads this list)
 HOT_PATH_EXPORTS = (
     "rasterize_meshes", "rasterize_meshes_backward", "_rasterize_meshes_naive", "_rasterize_meshes_coarse",
     "_rasterize_meshes_fine", "rasterize_points", "rasterize_points_backward", "_rasterize_points_naive",

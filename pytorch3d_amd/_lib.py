@@ -1,15 +1,20 @@
 """ctypes binding of libp3d_amd.so (the C ABI declared in include/p3d_amd.h).
 
+The header is the one description of that ABI: the ctypes signatures and the integer constants of this module are read from it at
+import (parse_header), so an entry or a macro added there needs no second copy here.
+
 There is no fallback: if the HIP library is missing or cannot be loaded, every operator of this
 package raises.  Build it with `python -m pytorch3d_amd.build` (hipcc, gfx950).
 """
 import ctypes
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # P3D_LIB_PATH selects an ablation build (profiles/ scripts only; see build.py)
 LIB_PATH = os.environ.get("P3D_LIB_PATH") or os.path.join(_HERE, "libp3d_amd.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "p3d_amd.h")
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -19,250 +24,84 @@ c_f64 = ctypes.c_double
 c_ptr = ctypes.c_void_p
 c_size = ctypes.c_size_t
 
-ABI_VERSION = 3  # P3D_ABI_VERSION of include/p3d_amd.h
 
-# flags of p3d_rasterize_meshes_ex, p3d_rasterize_points_ex (TIE_ORDER only) / p3d_rasterize_meshes_backward_ex (include/p3d_amd.h)
-RASTER_COVER_LIST = 1
-RASTER_CUDA_TIE_ORDER = 2
-BWD_COVER_HAS_LIST = 1
-BWD_MAKE_FACE_PRE = 2
-BWD_GRAD_OUT_ZEROED = 8
-KNN_MAX_K = 32           # P3D_KNN_MAX_K
-KNN_TILE = 512           # P3D_KNN_TILE: p2 points staged per step
-KNN_ACCUMULATE_P2 = 1    # P3D_KNN_ACCUMULATE_P2
-FRAMES_MAX_K = 64        # P3D_FRAMES_MAX_K: the largest neighbourhood of csrc/point_frames.hip
-FRAMES_DISAMBIGUATE = 1  # P3D_FRAMES_DISAMBIGUATE
-FRAMES_ROWS_PER_GROUP = 64  # P3D_FRAMES_ROWS_PER_GROUP: query rows of one workgroup of csrc/point_frames.hip
-BOX3D_LDS_CAPACITY = 64     # P3D_BOX3D_LDS_CAPACITY: triangles per fragment list of csrc/box3d.hip's first launch
-BOX3D_WAVES_PER_GROUP = 4   # P3D_BOX3D_WAVES_PER_GROUP: pairs per workgroup and round of that launch
-BOX3D_MAX_GROUPS = 4096     # P3D_BOX3D_MAX_GROUPS: its largest grid; more pairs take the grid-stride loop
-NEIGHBOR_SUM_MAX_GROUPS = 2048  # P3D_NEIGHBOR_SUM_MAX_GROUPS: the largest grid of csrc/graph_conv.hip; more row groups take the grid-stride loop
-NEIGHBOR_SUM_GROUP_LANES = 256  # lanes of one of its workgroups: 256 / lanes_per_row vertices per round
-VERT_ALIGN_NEAREST, VERT_ALIGN_BORDER, VERT_ALIGN_CORNERS = 1, 2, 4  # P3D_VERT_ALIGN_*: flags of csrc/vert_align.hip
-VERT_ALIGN_MAX_GROUPS = 4096  # P3D_VERT_ALIGN_MAX_GROUPS: its largest grid
-FPS_REGISTER_POINTS = 16384  # P3D_FPS_REGISTER_POINTS: the largest cloud the register form of farthest point sampling holds
-POINT_MESH_POINT, POINT_MESH_SEGMENT, POINT_MESH_TRIANGLE = 0, 1, 2  # P3D_POINT_MESH_*: the kind of a query / target object
-POINT_MESH_TILE = 64                # P3D_POINT_MESH_TILE: target records staged per wave and step
-POINT_MESH_ACCUMULATE_QUERIES = 1   # P3D_POINT_MESH_ACCUMULATE_QUERIES
-POINT_MESH_ACCUMULATE_TARGETS = 2   # P3D_POINT_MESH_ACCUMULATE_TARGETS
+class ExtensionMissing(RuntimeError):
+    pass
 
-_SIGNATURES = {
-    # name: (restype, [argtypes])
-    "p3d_abi_version": (c_int, []),
-    "p3d_error_string": (ctypes.c_char_p, [c_int]),
-    "p3d_rasterize_meshes_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
-    "p3d_rasterize_meshes_short_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int, c_i64]),
-    "p3d_rasterize_meshes_workspace_need_offset": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
-    "p3d_rasterize_meshes": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int, c_int,
-                                     c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_meshes_naive": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int,
-                                           c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_coarse": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int, c_ptr,
-                                            c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_fine_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
-    "p3d_rasterize_meshes_fine": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_f32,
-                                          c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size,
-                                          c_ptr]),
-    "p3d_rasterize_meshes_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int,
-                                              c_int, c_int, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_cover_bytes": (c_size, [c_int, c_int, c_int]),
-    "p3d_rasterize_meshes_cover_check": (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_cover_list_bytes": (c_size, [c_int, c_int, c_int]),
-    "p3d_rasterize_meshes_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_int, c_int, c_int, c_int,
-                                        c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_uint, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_meshes_verts_ex": (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int,
-                                              c_f32, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_uint,
-                                              c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_meshes_backward_workspace_bytes": (c_size, [c_int, c_int, c_int]),
-    "p3d_gather_face_verts": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "p3d_gather_face_verts_pre": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "p3d_rasterize_meshes_backward_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int,
-                                                 c_int, c_int, c_int, c_int, c_uint, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_scatter_face_grads": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "p3d_face_areas_normals_forward": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "p3d_face_areas_normals_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    "p3d_verts_normals_forward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_verts_normals_backward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_verts_normals_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "p3d_verts_normals_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "p3d_mesh_edge_loss_forward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_mesh_laplacian_forward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_mesh_normal_consistency_forward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_mesh_normal_consistency_backward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_mesh_edge_loss_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_size, c_ptr, c_ptr]),
-    "p3d_mesh_edge_loss_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_f32, c_ptr, c_ptr]),
-    "p3d_mesh_laplacian_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr, c_ptr]),
-    "p3d_mesh_laplacian_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_mesh_normal_consistency_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_size, c_ptr, c_ptr]),
-    "p3d_mesh_normal_consistency_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_size,
-                                                     c_ptr, c_ptr]),
-    "p3d_transform_gather_face_verts": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_transform_verts_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_transform_verts_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_transform_backward_workspace_bytes": (c_size, [c_i64, c_int, c_int]),
-    "p3d_transform_backward_cameras": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
-    "p3d_rasterize_points_short_workspace_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int, c_i64]),
-    "p3d_rasterize_points_workspace_need_offset": (c_size, [c_i64, c_int, c_int, c_int, c_int, c_int]),
-    "p3d_rasterize_points_ex": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
-                                        c_ptr, c_int, c_ptr, c_int, c_f32, c_ptr, c_uint, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr,
-                                     c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_naive": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr, c_ptr,
-                                           c_ptr, c_ptr]),
-    "p3d_rasterize_points_coarse": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_ptr,
-                                            c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_fine": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_composite_backward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_int,
-                                                        ctypes.c_float, c_ptr, c_ptr, c_ptr]),
-    "p3d_rasterize_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_ptr,
-                                              c_ptr]),
-    "p3d_composite_forward": (c_int, [c_int, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int, c_int,
-                                      ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, c_ptr]),
-    "p3d_composite_backward": (c_int, [c_int, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_int, c_int, c_i64, c_int, c_int,
-                                       c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr, ctypes.POINTER(c_i64), c_ptr,
-                                       c_ptr]),
-    "p3d_interp_face_attrs_forward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
-    "p3d_interp_face_attrs_backward": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr,
-                                               c_ptr]),
-    "p3d_interp_face_attrs_backward_nhwk": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_i64, c_int,
-                                                    c_ptr, c_ptr, c_ptr]),
-    "p3d_clip_faces_plan_bytes": (c_size, [c_i64]),
-    "p3d_clip_faces_plan": (c_int, [c_ptr, c_i64, ctypes.POINTER(c_f32), c_int, c_int, c_int, c_f32, c_ptr, c_size,
-                                    c_ptr]),
-    "p3d_clip_faces_emit": (c_int, [c_ptr, c_i64, c_ptr, c_int, c_ptr, c_size, c_i64, c_i64, c_i64, c_f32, c_int, c_ptr,
-                                    c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "p3d_clip_faces_backward": (c_int, [c_ptr, c_i64, c_ptr, c_size, c_i64, c_i64, c_f32, c_int, c_ptr, c_ptr, c_ptr,
-                                        c_ptr]),
-    "p3d_convert_clipped_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
-    "p3d_convert_clipped_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
-    "p3d_sigmoid_alpha_blend_forward": (c_int, [c_ptr, c_ptr, c_f32, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_sigmoid_alpha_blend_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_softmax_rgb_blend_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, ctypes.POINTER(c_f32), c_f32,
-                                              c_f32, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_softmax_rgb_blend_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, ctypes.POINTER(c_f32),
-                                               c_f32, c_f32, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr,
-                                               c_ptr]),
-    "p3d_phong_shade_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_int, c_i64,
-                                        c_ptr, c_ptr]),
-    "p3d_phong_shade_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_int, c_int, c_int,
-                                         c_int, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "p3d_soft_phong_supported_k": (c_int, [c_int]),
-    "p3d_soft_phong_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_f32, c_f32,
-                                       ctypes.POINTER(c_f32), c_f32, c_f32, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_i64,
-                                       c_ptr, c_ptr]),
-    "p3d_soft_phong_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_int, c_f32, c_f32,
-                                        ctypes.POINTER(c_f32), c_f32, c_f32, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_i64,
-                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "p3d_sample_uv_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_i64, c_int, c_int, c_int,
-                                      c_int, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_sample_uv_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_int, c_int, c_i64, c_int, c_int,
-                                       c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
-    "p3d_sample_uv_multi_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int, c_i64,
-                                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_sample_uv_multi_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_int,
-                                             c_i64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr,
-                                             c_ptr]),
-    "p3d_sample_atlas_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_sample_atlas_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_hard_rgb_blend_forward": (c_int, [c_ptr, c_ptr, ctypes.POINTER(c_f32), c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_hard_rgb_blend_backward": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_soft_depth_blend_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_soft_depth_blend_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_f32, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
-    "p3d_hard_depth_blend_forward": (c_int, [c_ptr, c_ptr, c_f32, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_hard_depth_blend_backward": (c_int, [c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr]),
-    "p3d_splatter_blend_backward_workspace_bytes": (c_size, [c_int, c_int, c_int]),
-    "p3d_splatter_blend_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_f32, ctypes.POINTER(c_f32), c_int, c_int, c_int, c_int,
-                                           c_ptr, c_ptr]),
-    "p3d_splatter_blend_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_f32, ctypes.POINTER(c_f32), c_int, c_int, c_int,
-                                            c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    # the deterministic backwards (include/p3d_amd.h: *_ordered)
-    "p3d_rasterize_meshes_backward_ordered_workspace_bytes": (c_size, [c_i64, c_int, c_i64]),
-    "p3d_rasterize_meshes_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_i64,
-                                                      c_int, c_int, c_int, c_int, c_int, c_int, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_scatter_face_grads_ordered_workspace_bytes": (c_size, [c_i64]),
-    "p3d_scatter_face_grads_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_backward_ordered_workspace_bytes": (c_size, [c_i64]),
-    "p3d_rasterize_points_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_int, c_int, c_ptr,
-                                                      c_ptr, c_size, c_ptr]),
-    "p3d_rasterize_points_composite_backward_ordered_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int, c_i64]),
-    "p3d_rasterize_points_composite_backward_ordered": (c_int, [c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int,
-                                                                c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_composite_backward_ordered_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int, c_int, c_i64]),
-    "p3d_composite_backward_ordered": (c_int, [c_int, c_ptr, c_ptr, ctypes.POINTER(c_i64), c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_i64,
-                                               c_int, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_ptr,
-                                               ctypes.POINTER(c_i64), c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_interp_face_attrs_backward_ordered_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "p3d_interp_face_attrs_backward_ordered": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr,
-                                                       c_size, c_ptr]),
-    # nearest neighbours and chamfer distance (csrc/knn.hip; the ordered scatter: csrc/ordered_bwd.hip)
-    "p3d_knn_points_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    "p3d_chamfer_forward_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "p3d_chamfer_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr,
-                                    c_size, c_ptr]),
-    "p3d_knn_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_uint,
-                                        c_ptr, c_ptr, c_ptr]),
-    "p3d_knn_points_ordered_backward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_knn_points_ordered_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int,
-                                                c_int, c_int, c_uint, c_ptr, c_ptr, c_size, c_ptr]),
-    # point-mesh distances (csrc/point_mesh.hip; the ordered scatter: csrc/ordered_bwd.hip)
-    "p3d_point_mesh_forward_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "p3d_point_mesh_forward": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_f64, c_int, c_ptr, c_ptr,
-                                       c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_point_mesh_backward_workspace_bytes": (c_size, [c_int, c_i64]),
-    "p3d_point_mesh_backward": (c_int, [c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_f64, c_uint,
-                                        c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    # sample_points_from_meshes (csrc/sample_points.hip; the ordered per-face sum: csrc/ordered_bwd.hip)
-    "p3d_sample_points_forward_workspace_bytes": (c_size, [c_i64]),
-    "p3d_sample_points_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
-                                          c_size, c_ptr]),
-    "p3d_sample_points_backward_workspace_bytes": (c_size, [c_i64, c_int, c_i64]),
-    "p3d_sample_points_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_size,
-                                           c_ptr]),
-    # farthest point sampling and ball query (csrc/fps_ball.hip)
-    "p3d_sample_farthest_points_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "p3d_sample_farthest_points": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_int, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_ball_query": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_int, c_int, c_f32, c_ptr, c_ptr, c_ptr]),
-    # point clouds into voxel grids (csrc/points_to_volumes.hip)
-    "p3d_points_to_volumes_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_int]),
-    "p3d_points_to_volumes_keys": (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    "p3d_points_to_volumes_forward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
-                                              c_ptr, c_ptr, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_points_to_volumes_backward": (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr,
-                                               c_ptr, c_ptr, c_f32, c_int, c_int, c_ptr, c_ptr, c_ptr]),
-    # point-cloud covariances, curvatures and local coordinate frames (csrc/point_frames.hip)
-    "p3d_point_frames_workgroups": (c_i64, [c_i64, c_i64]),
-    "p3d_point_frames": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_uint, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
-    # box3d_overlap (csrc/box3d.hip): the device entry with its LDS capacity argument, and the host loop
-    "p3d_iou_box3d_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "p3d_iou_box3d": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
-    "p3d_iou_box3d_host": (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
-    # GraphConv / gather_scatter neighbour sums (csrc/graph_conv.hip): one entry, forward and backward
-    "p3d_neighbor_sum": (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
-    # vert_align (csrc/vert_align.hip): one feature map per call; the ordered grad_feat is keys + a stable sort + the segmented sum
-    "p3d_vert_align_forward": (c_int, [c_ptr] + [c_i64] * 8 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr, c_i64, c_ptr]),
-    "p3d_vert_align_backward": (c_int, [c_ptr, c_i64, c_ptr] + [c_i64] * 8 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr]
-                                + [c_i64] * 4 + [c_ptr, c_ptr]),
-    "p3d_vert_align_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "p3d_vert_align_keys": (c_int, [c_i64] * 3 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr, c_ptr]),
-    "p3d_vert_align_ordered_backward": (c_int, [c_ptr] + [c_i64] * 5 + [c_ptr] + [c_i64] * 4 + [c_ptr, c_i64, c_uint, c_ptr, c_ptr, c_ptr]
-                                        + [c_i64] * 4 + [c_ptr, c_size, c_ptr]),
-    "p3d_profile_enable": (None, [c_int]),
-    "p3d_profile_collect": (None, []),
-    "p3d_profile_num_entries": (c_int, []),
-    "p3d_profile_entry": (ctypes.c_char_p, [c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)]),
-    "p3d_profile_reset": (None, []),
-}
 
+_SCALARS = {"int": c_int, "unsigned": c_uint, "int64_t": c_i64, "size_t": c_size, "float": c_f32, "double": c_f64}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char*": ctypes.c_char_p})
+_WORDS = set(_SCALARS) | {"void", "char", "long", "short", "signed", "const", "struct"}  # never a parameter's name
+_PARAM = re.compile(r"(const )?(\w+)(?: ?(\*))?(?: ?\b(\w+))?(?: ?(\[\d+\]))?")  # const, type, *, name, [n]
+
+
+def parse_header(text):
+    """({entry: (return type, [parameter types])}, {macro name without P3D_: integer}) of a header in the style of include/p3d_amd.h.
+    The types are C spellings without the parameter names: "const float*", "int64_t", "const int64_t[2]", "p3d_stream_t".  Comments
+    go first (some hold text of the form p3d_x(...)), then preprocessor lines; every statement left must be the stream typedef or a
+    `RET p3d_name(PARAMS)` whose types ctypes_signature knows: anything else raises with the statement's text."""
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    constants = {m.group(1): int(m.group(2)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+P3D_(\w+)[ \t]+\(?(-?\d+)u?\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    declarations = {}
+    for statement in text.split(";"):
+        statement = " ".join(statement.split())
+        if statement in ("", "typedef void* p3d_stream_t"):
+            continue
+        m = re.fullmatch(r"(.+?) ?\b(p3d_\w+) ?\((.*)\)", statement)
+        if m is None:
+            raise ValueError(f"cannot parse the declaration `{statement}`")
+        if m.group(2) in declarations:
+            raise ValueError(f"{m.group(2)} is declared twice")
+        params = []
+        for param in ([] if m.group(3).strip() == "void" else m.group(3).split(",")):
+            p = _PARAM.fullmatch(param.strip())
+            if p is None or p.group(4) in _WORDS or (p.group(3) and p.group(5)):
+                raise ValueError(f"cannot parse the parameter `{param.strip()}` of the declaration `{statement}`")
+            params.append((p.group(1) or "") + p.group(2) + (p.group(3) or "") + (p.group(5) or ""))
+        declarations[m.group(2)] = (m.group(1).replace(" *", "*"), params)
+        ctypes_signature(*declarations[m.group(2)], where=statement)
+    return declarations, constants
+
+
+def ctypes_signature(ret, params, where=None):
+    """(restype, [argtypes]) of a parsed declaration: scalars by _SCALARS, p3d_stream_t and every T* a c_void_p, `const T x[n]` a
+    POINTER(T); returns also void and const char*.  A type outside that raises (with the declaration's text): it is never guessed."""
+    def fail(ctype):
+        raise ValueError(f"no ctypes type for the C type `{ctype}`" + (f" in the declaration `{where}`" if where else ""))
+
+    def arg(ctype):
+        base = ctype[len("const "):] if ctype.startswith("const ") else ctype
+        if base.endswith("]"):
+            base = base[:base.index("[")]
+            return ctypes.POINTER(_SCALARS[base]) if base in _SCALARS else fail(ctype)
+        if base == "p3d_stream_t" or (base.endswith("*") and base != "*"):
+            return c_ptr
+        return _SCALARS[base] if base in _SCALARS else fail(ctype)
+
+    return (_RETURNS[ret] if ret in _RETURNS else fail(ret)), [arg(p) for p in params]
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        DECLARATIONS, CONSTANTS = parse_header(_f.read())
+except OSError as e:
+    raise ExtensionMissing(f"{HEADER_PATH} not found ({e}): the package reads the C ABI of libp3d_amd.so from this header") from e
+
+# every `#define P3D_<NAME> <integer>` of the header as <NAME>: ABI_VERSION, MAX_K, OK, ERR_*, the flags (RASTER_*, BWD_*, ...) and the
+# launch constants the wrappers and tests size their inputs by (KNN_TILE, BOX3D_MAX_GROUPS, ...)
+assert not set(CONSTANTS) & set(globals()), sorted(set(CONSTANTS) & set(globals()))
+globals().update(CONSTANTS)
+# lanes of one workgroup of csrc/graph_conv.hip (256 / lanes_per_row vertices per round).  The one constant written by hand: the kernel
+# spells it as the literal of its launch bounds and launches, so there is no macro to read
+NEIGHBOR_SUM_GROUP_LANES = 256
+
+_SIGNATURES = {name: ctypes_signature(*decl) for name, decl in DECLARATIONS.items()}  # name: (restype, [argtypes])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lock = threading.Lock()
 _lib = None
-
-
-class ExtensionMissing(RuntimeError):
-    pass
 
 
 def load():

@@ -26,8 +26,8 @@ from . import _C, _lib
 from .interp_face_attrs import interpolate_face_attributes
 from .rasterize_meshes import gather_face_verts
 
-PARAM_FLOATS = 25  # include/p3d_amd.h: P3D_SHADE_PARAM_FLOATS
-LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1
+PARAM_FLOATS = _lib.SHADE_PARAM_FLOATS
+LIGHT_DIRECTIONAL, LIGHT_POINT = _lib.LIGHT_DIRECTIONAL, _lib.LIGHT_POINT
 
 
 class Lights(NamedTuple):

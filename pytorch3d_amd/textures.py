@@ -13,8 +13,8 @@ import torch
 
 from . import _C, _lib
 
-_PAD = {"zeros": 0, "border": 1}
-_MODE = {"bilinear": 0, "nearest": 1}
+_PAD = {"zeros": _lib.PAD_ZEROS, "border": _lib.PAD_BORDER}
+_MODE = {"bilinear": _lib.SAMPLE_BILINEAR, "nearest": _lib.SAMPLE_NEAREST}
 
 
 class _SampleUV(torch.autograd.Function):

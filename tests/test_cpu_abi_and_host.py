@@ -634,3 +634,185 @@ def test_pybind_flavour_builds_and_exports_the_operator_set():
     with pytest.raises(RuntimeError, match="GPU tensor"):  # CPU tensors are refused, as in the ctypes flavour
         z = torch.zeros(1, dtype=torch.int64)
         mod.rasterize_meshes(torch.rand(4, 3, 3), z, z + 4, torch.full((4,), -1, dtype=torch.int64), (8, 8), 0.0, 2, 0, 0, False, False, False)
+
+
+# ---- the header as the one description of the ABI: pytorch3d_amd/_lib.py reads its signatures and constants from it ----
+
+def _host_compiler():
+    """The clang++ of the toolchain build._hipcc() resolves to (host compilation only, no offload arch), or hipcc itself as a C++ driver."""
+    import shutil
+
+    from pytorch3d_amd import build
+
+    hipcc = shutil.which(build._hipcc())
+    assert hipcc, "no hipcc"
+    root = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))
+    for clang in (os.path.join(root, "llvm", "bin", "clang++"), os.path.join(root, "lib", "llvm", "bin", "clang++")):
+        if os.path.exists(clang):
+            return [clang]
+    return [hipcc, "-x", "c++"]
+
+
+def test_compiler_confirms_the_parsed_signatures_and_constants(tmp_path):
+    """The C types pytorch3d_amd._lib.parse_header read, restated as function-pointer types, are the types the compiler sees in
+    include/p3d_amd.h -- for EVERY entry: a dropped parameter, an int for an int64_t or a missed entry fails.  The ctypes table is
+    those same C types through the parser's dictionary, and the constants are the values the preprocessor sees."""
+    from pytorch3d_amd import _lib
+
+    assert set(_lib.DECLARATIONS) == set(_declared()) and len(_lib.DECLARATIONS) >= 136
+    lines = ["#include <type_traits>", '#include "p3d_amd.h"']
+    for name, (ret, params) in _lib.DECLARATIONS.items():
+        lines.append(f"static_assert(std::is_same_v<decltype(&{name}), {ret} (*)({', '.join(params)})>, \"{name}\");")
+    for name, value in _lib.CONSTANTS.items():
+        lines.append(f"static_assert(P3D_{name} == {value}, \"P3D_{name}\");")
+    src = tmp_path / "abi_check.cpp"
+    src.write_text("\n".join(lines) + "\n")
+    res = subprocess.run(_host_compiler() + ["-std=c++17", "-fsyntax-only", "-I", os.path.dirname(HEADER), str(src)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr[-4000:]
+
+    assert _lib._SIGNATURES == {name: _lib.ctypes_signature(ret, params) for name, (ret, params) in _lib.DECLARATIONS.items()}
+    assert _lib.EXPORTED_SYMBOLS == tuple(_lib._SIGNATURES)
+    S, P = _lib._SIGNATURES, ctypes.POINTER
+    # hand-written expectations, one of each kind (the types are the aliases of _lib themselves: what load() assigns)
+    assert S["p3d_abi_version"] == (_lib.c_int, []) and S["p3d_profile_collect"] == (None, [])
+    assert S["p3d_error_string"] == (ctypes.c_char_p, [_lib.c_int])
+    assert S["p3d_profile_entry"] == (ctypes.c_char_p, [_lib.c_int, _lib.c_ptr, _lib.c_ptr])
+    assert S["p3d_rasterize_meshes_short_workspace_bytes"] == (_lib.c_size, [_lib.c_i64] + [_lib.c_int] * 5 + [_lib.c_i64])
+    assert S["p3d_point_frames_workgroups"] == (_lib.c_i64, [_lib.c_i64, _lib.c_i64])
+    assert S["p3d_clip_faces_plan"] == (_lib.c_int, [_lib.c_ptr, _lib.c_i64, P(_lib.c_f32), _lib.c_int, _lib.c_int, _lib.c_int, _lib.c_f32,
+                                                     _lib.c_ptr, _lib.c_size, _lib.c_ptr])
+    assert S["p3d_composite_forward"][1][:3] == [_lib.c_int, _lib.c_ptr, P(_lib.c_i64)]
+    assert S["p3d_point_mesh_forward"][1][10] is _lib.c_f64 and S["p3d_vert_align_keys"][1][10] is _lib.c_uint
+
+
+_SYNTHETIC_HEADER = """
+/* a block comment with a declaration inside: int p3d_fake(int); and
+   #define P3D_NOT_A_MACRO 7 on its second line */
+#ifndef FAKE_H_
+#define FAKE_H_
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define P3D_A 3
+#define P3D_B (-2)   /* negative */
+#define P3D_C 8u     // unsigned; int p3d_fake(int);
+#define P3D_NAME_ONLY
+typedef void* p3d_stream_t; /* hipStream_t */
+// int p3d_fake(int);
+int p3d_scalars(int a, unsigned b, int64_t c, size_t d, float e, double f);
+size_t p3d_pointers(const int* a, unsigned* b, const int64_t* c, size_t* d, float* e, const double* f, void* g, const void* h,
+                    int32_t* i, p3d_stream_t stream);
+void p3d_arrays(const int64_t strides[2], const float background[3],
+                const double planes[6],
+                float *spaced);
+const char* p3d_nothing(void);
+int64_t p3d_wide(void); double p3d_real(int n); float p3d_single(int n); unsigned p3d_bits(void);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_parser_on_synthetic_text():
+    from pytorch3d_amd import _lib
+
+    decls, constants = _lib.parse_header(_SYNTHETIC_HEADER)
+    assert constants == {"A": 3, "B": -2, "C": 8}
+    assert decls == {
+        "p3d_scalars": ("int", ["int", "unsigned", "int64_t", "size_t", "float", "double"]),
+        "p3d_pointers": ("size_t", ["const int*", "unsigned*", "const int64_t*", "size_t*", "float*", "const double*", "void*", "const void*",
+                                    "int32_t*", "p3d_stream_t"]),
+        "p3d_arrays": ("void", ["const int64_t[2]", "const float[3]", "const double[6]", "float*"]),
+        "p3d_nothing": ("const char*", []),
+        "p3d_wide": ("int64_t", []), "p3d_real": ("double", ["int"]), "p3d_single": ("float", ["int"]), "p3d_bits": ("unsigned", []),
+    }
+    P, sig = ctypes.POINTER, lambda name: _lib.ctypes_signature(*decls[name])
+    assert sig("p3d_scalars") == (ctypes.c_int, [ctypes.c_int, ctypes.c_uint, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double])
+    assert sig("p3d_pointers") == (ctypes.c_size_t, [ctypes.c_void_p] * 10)
+    assert sig("p3d_arrays") == (None, [P(ctypes.c_int64), P(ctypes.c_float), P(ctypes.c_double), ctypes.c_void_p])
+    assert sig("p3d_nothing") == (ctypes.c_char_p, [])
+    assert [sig(n)[0] for n in ("p3d_wide", "p3d_real", "p3d_single", "p3d_bits")] == [ctypes.c_int64, ctypes.c_double, ctypes.c_float, ctypes.c_uint]
+
+    # what the dictionary does not hold is refused with the declaration's text, never guessed
+    for bad in ("int p3d_bad(long double x);", "int p3d_bad(int n, long double);", "long double p3d_bad(void);", "int p3d_bad(unsigned int n);",
+                "int p3d_bad(struct thing* t);", "int* p3d_bad(void);", "int p3d_bad(char c);", "int p3d_bad(const int64_t* strides[2]);"):
+        with pytest.raises(ValueError, match=re.escape(bad[:-1])):
+            _lib.parse_header(bad)
+    with pytest.raises(ValueError, match="long double"):
+        _lib.parse_header("int p3d_good(int n);\nint p3d_bad(long double x);")
+    with pytest.raises(ValueError, match=re.escape("struct p3d_options { int k")):  # not a declaration of an entry
+        _lib.parse_header("struct p3d_options { int k; };")
+    with pytest.raises(ValueError, match="p3d_twice"):
+        _lib.parse_header("int p3d_twice(void); int p3d_twice(int n);")
+
+
+def test_every_integer_macro_of_the_header_is_a_constant_of_lib():
+    from pytorch3d_amd import _lib
+
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    macros = dict(re.findall(r"^#define (P3D_\w+)[ \t]+(\S.*?)\s*$", text, re.M))  # every macro that has a value (not the include guard)
+    assert len(macros) >= 47 and "P3D_AMD_H_" not in macros
+    for macro, value in macros.items():
+        assert re.fullmatch(r"\(?-?\d+u?\)?", value), (macro, value)  # the header holds integer macros only
+        assert getattr(_lib, macro[len("P3D_"):]) == int(value.strip("()u")) == _lib.CONSTANTS[macro[len("P3D_"):]], macro
+    # the names the package and the tests used before the header was read, with the values they had
+    before = {"ABI_VERSION": 3, "RASTER_COVER_LIST": 1, "RASTER_CUDA_TIE_ORDER": 2, "BWD_COVER_HAS_LIST": 1, "BWD_MAKE_FACE_PRE": 2,
+              "BWD_GRAD_OUT_ZEROED": 8, "KNN_MAX_K": 32, "KNN_TILE": 512, "KNN_ACCUMULATE_P2": 1, "FRAMES_MAX_K": 64, "FRAMES_DISAMBIGUATE": 1,
+              "FRAMES_ROWS_PER_GROUP": 64, "BOX3D_LDS_CAPACITY": 64, "BOX3D_WAVES_PER_GROUP": 4, "BOX3D_MAX_GROUPS": 4096,
+              "NEIGHBOR_SUM_MAX_GROUPS": 2048, "VERT_ALIGN_NEAREST": 1, "VERT_ALIGN_BORDER": 2, "VERT_ALIGN_CORNERS": 4,
+              "VERT_ALIGN_MAX_GROUPS": 4096, "FPS_REGISTER_POINTS": 16384, "POINT_MESH_POINT": 0, "POINT_MESH_SEGMENT": 1,
+              "POINT_MESH_TRIANGLE": 2, "POINT_MESH_TILE": 64, "POINT_MESH_ACCUMULATE_QUERIES": 1, "POINT_MESH_ACCUMULATE_TARGETS": 2}
+    assert len(before) == 27 and all(_lib.CONSTANTS[name] == value == getattr(_lib, name) for name, value in before.items())
+    assert _lib.NEIGHBOR_SUM_GROUP_LANES == 256 and "NEIGHBOR_SUM_GROUP_LANES" not in _lib.CONSTANTS  # the one written by hand
+    # the copies elsewhere in the package are these
+    from pytorch3d_amd import _C, shading, textures
+
+    assert (_C.kMaxPointsPerPixel, _C.kMaxItemsPerBin) == (150, 22) == (_lib.MAX_K, _lib.MAX_BINS_PER_SIDE + 1)
+    assert (_C._ALPHA, _C._NORM, _C._SUM) == (0, 1, 2) == (_lib.COMPOSITE_ALPHA, _lib.COMPOSITE_NORM_SUM, _lib.COMPOSITE_SUM)
+    assert (shading.PARAM_FLOATS, shading.LIGHT_DIRECTIONAL, shading.LIGHT_POINT) == (25, 0, 1)
+    assert textures._PAD == {"zeros": 0, "border": 1} and textures._MODE == {"bilinear": 0, "nearest": 1}
+
+
+def test_missing_header_is_an_extension_missing_error(tmp_path):
+    """The header travels with the package (<package>/../include/p3d_amd.h); without it the import names the path."""
+    import importlib.util
+
+    from pytorch3d_amd import _lib
+
+    os.makedirs(tmp_path / "pkg")
+    copy = tmp_path / "pkg" / "_lib.py"
+    copy.write_text(open(_lib.__file__).read())
+    spec = importlib.util.spec_from_file_location("_lib_without_header", str(copy))
+    with pytest.raises(Exception, match=re.escape(str(tmp_path / "include" / "p3d_amd.h"))) as info:
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
+    assert type(info.value).__name__ == "ExtensionMissing" and isinstance(info.value, RuntimeError)
+
+
+def test_profile_snapshot_without_a_device():
+    """p3d_profile_entry's out-parameters are plain pointers in the header, so c_void_p in the table: byref() results pass."""
+    from pytorch3d_amd import _lib
+
+    snap = _lib.profile_snapshot()  # nothing was launched: no entry with a launch
+    assert isinstance(snap, dict) and all(n > 0 and ms >= 0.0 for n, ms in snap.values())
+    lib, n, ms = _lib.load(), _lib.c_i64(-7), _lib.c_f64(-7.0)
+    assert lib.p3d_profile_entry(lib.p3d_profile_num_entries(), ctypes.byref(n), ctypes.byref(ms)) is None  # past the end: untouched
+    assert (n.value, ms.value) == (-7, -7.0)
+
+
+def test_build_dependency_lists_are_what_is_on_disk():
+    """needs_build() compares the library with SOURCES + HEADERS: a kernel file that is not compiled, or a header that is included and
+    not listed, would leave a stale library in place."""
+    from pytorch3d_amd import build
+
+    on_disk = sorted(os.listdir(build.CSRC))
+    assert [f for f in on_disk if f.endswith(".hip")] == sorted(s for s in build.SOURCES if s.endswith(".hip"))
+    assert len(set(build.SOURCES)) == len(build.SOURCES) and "bind.cpp" not in build.SOURCES
+    assert all(os.path.isfile(os.path.join(build.CSRC, f)) for f in build.SOURCES + build.HEADERS)
+    headers = {os.path.normpath(h) for h in build.HEADERS}
+    assert headers == {f for f in on_disk if f.endswith(".h")} | {os.path.normpath("../../include/p3d_amd.h")}
+    for f in build.SOURCES + build.HEADERS:
+        here = os.path.dirname(f)  # quoted includes are relative to the including file
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(build.CSRC, f)).read(), re.M):
+            assert os.path.normpath(os.path.join(here, inc)) in headers, (f, inc)
