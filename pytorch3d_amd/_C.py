@@ -317,12 +317,9 @@ def forget_cover(pix_to_face):
 def cover_is_current(p2f, cover):
     """CHECK_COVERS: True unless `p2f` holds a face in a 16-pixel row segment that `cover` calls empty (device check + host sync)."""
     N, H, W, K = p2f.shape
-    lib = _lib.load()
-    with torch.cuda.device(p2f.device):
-        stale = torch.empty((1,), dtype=torch.int32, device=p2f.device)
-        rc = lib.p3d_rasterize_meshes_cover_check(_ptr(p2f), _ptr(cover), N, H, W, K, _ptr(stale), _stream(p2f.device))
-        _lib.check(rc, "rasterize_meshes_cover_check")
-        bad = bool(int(stale.item()))
+    stale = torch.empty((1,), dtype=torch.int32, device=p2f.device)
+    _lib.call("p3d_rasterize_meshes_cover_check", "rasterize_meshes_cover_check", p2f.device, p2f, cover, N, H, W, K, stale)
+    bad = bool(int(stale.item()))
     COVER_CHECKS[0] += 1
     COVER_CHECKS[1] += int(bad)
     return not bad
@@ -407,18 +404,16 @@ def _rasterize_meshes_covered(face_verts, mesh_to_face_first_idx, num_faces_per_
             flags |= _lib.RASTER_COVER_LIST
         elif want_cover:
             cover = torch.empty((N, (H + 15) // 16, (W + 15) // 16), dtype=torch.int32, device=dev)
-        tail = (_ptr(first), _ptr(count), _ptr(nb), F, N, H, W, float(blur_radius), K, bin_size if binned else 0,
+        tail = (first, count, nb, F, N, H, W, float(blur_radius), K, bin_size if binned else 0,
                 M if binned else 0, int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), int(bool(cull_backfaces)),
-                _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(cover), flags, _ptr(ws), ws.numel(), _stream(dev))
+                out[0], out[1], out[2], out[3], cover, flags, ws, ws.numel())
         if packed is not None:
             verts, faces, face_pre, zero_verts = packed
             if fv is not face_verts:
                 raise RuntimeError("packed vertices: face_verts must be the contiguous float32 buffer the call fills")
-            rc = lib.p3d_rasterize_meshes_verts_ex(_ptr(verts), _ptr(faces), verts.size(0), _ptr(fv), _ptr(face_pre), _ptr(zero_verts),
-                                                   *tail)
+            _lib.call("p3d_rasterize_meshes_verts_ex", "rasterize_meshes", dev, verts, faces, verts.size(0), fv, face_pre, zero_verts, *tail)
         else:
-            rc = lib.p3d_rasterize_meshes_ex(_ptr(fv), *tail)
-        _lib.check(rc, "rasterize_meshes")
+            _lib.call("p3d_rasterize_meshes_ex", "rasterize_meshes", dev, fv, *tail)
         if need is not None:
             need.report_later(ws, need_at, entries)
     return out, cover
@@ -446,14 +441,12 @@ def _rasterize_meshes_coarse(face_verts, mesh_to_face_first_idx, num_faces_per_m
     first, count = _c(mesh_to_face_first_idx, torch.int64), _c(num_faces_per_mesh, torch.int64)
     N, F = count.size(0), fv.size(0)
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((N, BH, BW, M), dtype=torch.int32, device=dev)
-        if out.numel() == 0:
-            return out
-        ws = _workspace(lib.p3d_rasterize_meshes_workspace_bytes(F, N, H, W, bin_size, M), dev)
-        rc = lib.p3d_rasterize_meshes_coarse(_ptr(fv), _ptr(first), _ptr(count), F, N, H, W, float(blur_radius),
-                                             bin_size, M, _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "_rasterize_meshes_coarse")
+    out = torch.empty((N, BH, BW, M), dtype=torch.int32, device=dev)
+    if out.numel() == 0:
+        return out
+    ws = _workspace(lib.p3d_rasterize_meshes_workspace_bytes(F, N, H, W, bin_size, M), dev)
+    _lib.call("p3d_rasterize_meshes_coarse", "_rasterize_meshes_coarse", dev, fv, first, count, F, N, H, W, float(blur_radius), bin_size, M, out,
+              ws, ws.numel())
     return out
 
 
@@ -476,26 +469,28 @@ def _rasterize_meshes_fine(face_verts, bin_faces, clipped_faces_neighbor_idx, im
     nb = _c(clipped_faces_neighbor_idx, torch.int64)
     N, BH, BW, M = bf.shape
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = _mesh_outputs(N, H, W, K, dev)
-        if out[0].numel() == 0:
-            return out
-        ws = _workspace(lib.p3d_rasterize_fine_workspace_bytes(N, BH, BW, M), dev)
-        rc = lib.p3d_rasterize_meshes_fine(_ptr(fv), _ptr(bf), _ptr(nb), fv.size(0), N, BH, BW, M, H, W,
-                                           float(blur_radius), int(bin_size), K, int(bool(perspective_correct)),
-                                           int(bool(clip_barycentric_coords)), int(bool(cull_backfaces)), _ptr(out[0]),
-                                           _ptr(out[1]), _ptr(out[2]), _ptr(out[3]), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "_rasterize_meshes_fine")
+    out = _mesh_outputs(N, H, W, K, dev)
+    if out[0].numel() == 0:
+        return out
+    ws = _workspace(lib.p3d_rasterize_fine_workspace_bytes(N, BH, BW, M), dev)
+    _lib.call("p3d_rasterize_meshes_fine", "_rasterize_meshes_fine", dev, fv, bf, nb, fv.size(0), N, BH, BW, M, H, W, float(blur_radius),
+              int(bin_size), K, int(bool(perspective_correct)), int(bool(clip_barycentric_coords)), int(bool(cull_backfaces)), out[0], out[1],
+              out[2], out[3], ws, ws.numel())
     return out
 
 
-def cover_ptr(cover, N, H, W):
-    """Pointer of a row cover after checking that it is the cover of an (N, H, W, .) rasterization; None -> null."""
+def checked_cover_of(cover, N, H, W):
+    """A row cover after checking that it is the cover of an (N, H, W, .) rasterization; None stays None (a null pointer)."""
     if cover is None:
         return None
     if cover.dtype != torch.int32 or tuple(cover.shape) != (N, (H + 15) // 16, (W + 15) // 16) or not cover.is_contiguous():
         raise RuntimeError("row cover does not belong to this pix_to_face")
-    return _ptr(cover)
+    return cover
+
+
+def cover_ptr(cover, N, H, W):
+    """Its pointer, for raw calls on _lib.load() (the tests), like _ptr and _stream above."""
+    return None if cover is None else _ptr(checked_cover_of(cover, N, H, W))
 
 
 def cover_has_list(cover, N, H, W):
@@ -545,42 +540,37 @@ def _mesh_backward(face_verts, faces, V, pix_to_face, grad_zbuf, grad_bary, grad
     persp, clip = int(bool(perspective_correct)), int(bool(clip_barycentric_coords))
     has_list = cover_has_list(cover, N, H, W)
     flags = _lib.BWD_COVER_HAS_LIST if has_list else 0
-    with torch.cuda.device(dev):
-        if faces is None:
-            out = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
-            if FACE_PRE and persp and clip and K in (4, 8):
-                face_pre = torch.empty((F, 4), dtype=torch.float32, device=dev)  # scratch the call fills first (one small launch)
-                flags |= _lib.BWD_MAKE_FACE_PRE
+    if faces is None:
+        out = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+        if FACE_PRE and persp and clip and K in (4, 8):
+            face_pre = torch.empty((F, 4), dtype=torch.float32, device=dev)  # scratch the call fills first (one small launch)
+            flags |= _lib.BWD_MAKE_FACE_PRE
+    else:
+        faces = _c(faces, torch.int64)
+        # (zeros: with F == 0 nothing is called -- a null faces pointer would ask for the per-face form)
+        if zeroed_out is not None and F and not _ordered() and tuple(zeroed_out.shape) == (V, 3) and zeroed_out.dtype == torch.float32 \
+                and zeroed_out.device == dev and zeroed_out.is_contiguous():
+            out = zeroed_out
+            flags |= _lib.BWD_GRAD_OUT_ZEROED
         else:
-            faces = _c(faces, torch.int64)
-            # (zeros: with F == 0 nothing is called -- a null faces pointer would ask for the per-face form)
-            if zeroed_out is not None and F and not _ordered() and tuple(zeroed_out.shape) == (V, 3) and zeroed_out.dtype == torch.float32 \
-                    and zeroed_out.device == dev and zeroed_out.is_contiguous():
-                out = zeroed_out
-                flags |= _lib.BWD_GRAD_OUT_ZEROED
-            else:
-                out = (torch.empty if F else torch.zeros)((V, 3), dtype=torch.float32, device=dev)
-            if not (has_list or cover is None):
-                face_pre = None  # the QUIRK above
-        if F == 0:
-            return out
-        if _ordered():
-            # the same bits whatever the cover, the records or the caller (the cover only says where NOT to look; the list below
-            # is made from pix_to_face itself)
-            lib = _lib.load()
-            hits = _sorted_hits(p2f)
-            corners = _sorted_corners(faces, V) if faces is not None else None
-            ws = _workspace(lib.p3d_rasterize_meshes_backward_ordered_workspace_bytes(F, int(faces is not None), hits.numel()), dev)
-            rc = lib.p3d_rasterize_meshes_backward_ordered(
-                _ptr(fv), _ptr(faces), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), _ptr(hits), hits.numel(), _ptr(corners),
-                corners.numel() if corners is not None else 0, F, V, N, H, W, K, persp, clip, _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-            _lib.check(rc, "rasterize_meshes_backward")
-            return out
-        ws = backward_workspace(cover, N, H, W, dev)
-        rc = _lib.load().p3d_rasterize_meshes_backward_ex(
-            _ptr(fv), _ptr(faces), _ptr(face_pre), _ptr(p2f), _ptr(gz), _ptr(gb), _ptr(gd), cover_ptr(cover, N, H, W), F, V, N, H, W,
-            K, persp, clip, flags, _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "rasterize_meshes_backward")
+            out = (torch.empty if F else torch.zeros)((V, 3), dtype=torch.float32, device=dev)
+        if not (has_list or cover is None):
+            face_pre = None  # the QUIRK above
+    if F == 0:
+        return out
+    if _ordered():
+        # the same bits whatever the cover, the records or the caller (the cover only says where NOT to look; the list below
+        # is made from pix_to_face itself)
+        lib = _lib.load()
+        hits = _sorted_hits(p2f)
+        corners = _sorted_corners(faces, V) if faces is not None else None
+        ws = _workspace(lib.p3d_rasterize_meshes_backward_ordered_workspace_bytes(F, int(faces is not None), hits.numel()), dev)
+        _lib.call("p3d_rasterize_meshes_backward_ordered", "rasterize_meshes_backward", dev, fv, faces, p2f, gz, gb, gd, hits, hits.numel(),
+                  corners, corners.numel() if corners is not None else 0, F, V, N, H, W, K, persp, clip, out, ws, ws.numel())
+        return out
+    ws = backward_workspace(cover, N, H, W, dev)
+    _lib.call("p3d_rasterize_meshes_backward_ex", "rasterize_meshes_backward", dev, fv, faces, face_pre, p2f, gz, gb, gd,
+              checked_cover_of(cover, N, H, W), F, V, N, H, W, K, persp, clip, flags, out, ws, ws.numel())
     return out
 
 
@@ -591,18 +581,15 @@ def scatter_face_grads(grad_face_verts, faces, V):
     g, faces = _c(grad_face_verts, torch.float32), _c(faces, torch.int64)
     F = faces.shape[0]
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        if not V:
-            return out
-        if _ordered():
-            corners = _sorted_corners(faces, V)
-            ws = _workspace(lib.p3d_scatter_face_grads_ordered_workspace_bytes(F), dev)
-            rc = lib.p3d_scatter_face_grads_ordered(_ptr(g), _ptr(faces), _ptr(corners), corners.numel(), V, F, _ptr(out), _ptr(ws),
-                                                    ws.numel(), _stream(dev))
-        else:
-            rc = lib.p3d_scatter_face_grads(_ptr(g), _ptr(faces), V, F, _ptr(out), _stream(dev))
-        _lib.check(rc, "scatter_face_grads")
+    out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    if not V:
+        return out
+    if _ordered():
+        corners = _sorted_corners(faces, V)
+        ws = _workspace(lib.p3d_scatter_face_grads_ordered_workspace_bytes(F), dev)
+        _lib.call("p3d_scatter_face_grads_ordered", "scatter_face_grads", dev, g, faces, corners, corners.numel(), V, F, out, ws, ws.numel())
+    else:
+        _lib.call("p3d_scatter_face_grads", "scatter_face_grads", dev, g, faces, V, F, out)
     return out
 
 
@@ -667,10 +654,8 @@ def _rasterize_points(who, points, cloud_to_packed_first_idx, num_points_per_clo
             return out, images
         ws, need, need_at, entries = _mesh_workspace(lib, P, N, H, W, bin_size, M, dev, "points") if binned else (_workspace(0, dev), None, 0, None)
         flags = _lib.RASTER_CUDA_TIE_ORDER if CUDA_TIE_ORDER and not splat else 0
-        rc = lib.p3d_rasterize_points_ex(_ptr(pts), _ptr(first), _ptr(count), _ptr(rad), P, N, H, W, K, bin_size if binned else 0,
-                                         M if binned else 0, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _SPLAT_MODES[mode] if splat else 0,
-                                         _ptr(feats), C, float(inv_r2), _ptr(images), flags, _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, who)
+        _lib.call("p3d_rasterize_points_ex", who, dev, pts, first, count, rad, P, N, H, W, K, bin_size if binned else 0, M if binned else 0, out[0],
+                  out[1], out[2], _SPLAT_MODES[mode] if splat else 0, feats, C, float(inv_r2), images, flags, ws, ws.numel())
         if need is not None:
             need.report_later(ws, need_at, entries)
     return out, images
@@ -703,14 +688,12 @@ def _rasterize_points_coarse(points, cloud_to_packed_first_idx, num_points_per_c
     first, count = _c(cloud_to_packed_first_idx, torch.int64), _c(num_points_per_cloud, torch.int64)
     N, P = count.size(0), pts.size(0)
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((N, BH, BW, M), dtype=torch.int32, device=dev)
-        if out.numel() == 0:
-            return out
-        ws = _workspace(lib.p3d_rasterize_points_workspace_bytes(P, N, H, W, bin_size, M), dev)
-        rc = lib.p3d_rasterize_points_coarse(_ptr(pts), _ptr(first), _ptr(count), _ptr(rad), P, N, H, W, bin_size, M,
-                                             _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        _lib.check(rc, "_rasterize_points_coarse")
+    out = torch.empty((N, BH, BW, M), dtype=torch.int32, device=dev)
+    if out.numel() == 0:
+        return out
+    ws = _workspace(lib.p3d_rasterize_points_workspace_bytes(P, N, H, W, bin_size, M), dev)
+    _lib.call("p3d_rasterize_points_coarse", "_rasterize_points_coarse", dev, pts, first, count, rad, P, N, H, W, bin_size, M, out, ws,
+              ws.numel())
     return out
 
 
@@ -726,15 +709,12 @@ def _rasterize_points_fine(points, bin_points, image_size, radius, bin_size, poi
     bp = _c(bin_points, torch.int32)
     N, BH, BW, M = bp.shape
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = _point_outputs(N, H, W, K, dev)
-        if out[0].numel() == 0:
-            return out
-        ws = _workspace(lib.p3d_rasterize_fine_workspace_bytes(N, BH, BW, M), dev)
-        rc = lib.p3d_rasterize_points_fine(_ptr(pts), _ptr(bp), _ptr(rad), pts.size(0), N, BH, BW, M, H, W,
-                                           int(bin_size), K, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(ws),
-                                           ws.numel(), _stream(dev))
-        _lib.check(rc, "_rasterize_points_fine")
+    out = _point_outputs(N, H, W, K, dev)
+    if out[0].numel() == 0:
+        return out
+    ws = _workspace(lib.p3d_rasterize_fine_workspace_bytes(N, BH, BW, M), dev)
+    _lib.call("p3d_rasterize_points_fine", "_rasterize_points_fine", dev, pts, bp, rad, pts.size(0), N, BH, BW, M, H, W, int(bin_size), K,
+              out[0], out[1], out[2], ws, ws.numel())
     return out
 
 
@@ -747,19 +727,16 @@ def rasterize_points_backward(points, idxs, grad_zbuf, grad_dists):
     N, H, W, K = ix.shape
     P = pts.size(0)
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        if P == 0:
-            return out
-        if _ordered():
-            hits = _sorted_hits(ix)
-            ws = _workspace(lib.p3d_rasterize_points_backward_ordered_workspace_bytes(hits.numel()), dev)
-            rc = lib.p3d_rasterize_points_backward_ordered(_ptr(pts), _ptr(ix), _ptr(gz), _ptr(gd), _ptr(hits), hits.numel(), P, N, H, W, K,
-                                                           _ptr(out), _ptr(ws), ws.numel(), _stream(dev))
-        else:
-            rc = lib.p3d_rasterize_points_backward(_ptr(pts), _ptr(ix), _ptr(gz), _ptr(gd), P, N, H, W, K, _ptr(out),
-                                                   _stream(dev))
-        _lib.check(rc, "rasterize_points_backward")
+    out = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    if P == 0:
+        return out
+    if _ordered():
+        hits = _sorted_hits(ix)
+        ws = _workspace(lib.p3d_rasterize_points_backward_ordered_workspace_bytes(hits.numel()), dev)
+        _lib.call("p3d_rasterize_points_backward_ordered", "rasterize_points_backward", dev, pts, ix, gz, gd, hits, hits.numel(), P, N, H, W, K,
+                  out, ws, ws.numel())
+    else:
+        _lib.call("p3d_rasterize_points_backward", "rasterize_points_backward", dev, pts, ix, gz, gd, P, N, H, W, K, out)
     return out
 
 
@@ -791,21 +768,18 @@ def rasterize_points_composite_backward(points, features, idxs, dists, grad_imag
     if tuple(gi.shape) != (N, H, W, C):
         raise RuntimeError("grad_images must be of shape (N, H, W, C)")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        gp = torch.empty((P, 3), dtype=torch.float32, device=dev)
-        gf = torch.empty((P, C), dtype=torch.float32, device=dev)
-        if P == 0:
-            return gp, gf
-        if _ordered():
-            hits = _sorted_hits(ix)
-            ws = _workspace(lib.p3d_rasterize_points_composite_backward_ordered_workspace_bytes(N, H, W, K, C, hits.numel()), dev)
-            rc = lib.p3d_rasterize_points_composite_backward_ordered(
-                _SPLAT_MODES[mode], _ptr(pts), _ptr(feats), _ptr(ix), _ptr(ds), _ptr(gi), _ptr(hits), hits.numel(), P, C, N, H, W, K,
-                float(inv_r2), _ptr(gp), _ptr(gf), _ptr(ws), ws.numel(), _stream(dev))
-        else:
-            rc = lib.p3d_rasterize_points_composite_backward(_SPLAT_MODES[mode], _ptr(pts), _ptr(feats), _ptr(ix), _ptr(ds), _ptr(gi), P, C, N, H, W, K,
-                                                             float(inv_r2), _ptr(gp), _ptr(gf), _stream(dev))
-        _lib.check(rc, "rasterize_points_composite_backward")
+    gp = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    gf = torch.empty((P, C), dtype=torch.float32, device=dev)
+    if P == 0:
+        return gp, gf
+    if _ordered():
+        hits = _sorted_hits(ix)
+        ws = _workspace(lib.p3d_rasterize_points_composite_backward_ordered_workspace_bytes(N, H, W, K, C, hits.numel()), dev)
+        _lib.call("p3d_rasterize_points_composite_backward_ordered", "rasterize_points_composite_backward", dev, _SPLAT_MODES[mode], pts, feats,
+                  ix, ds, gi, hits, hits.numel(), P, C, N, H, W, K, float(inv_r2), gp, gf, ws, ws.numel())
+    else:
+        _lib.call("p3d_rasterize_points_composite_backward", "rasterize_points_composite_backward", dev, _SPLAT_MODES[mode], pts, feats, ix, ds,
+                  gi, P, C, N, H, W, K, float(inv_r2), gp, gf)
     return gp, gf
 
 
@@ -813,10 +787,6 @@ def rasterize_points_composite_backward(points, features, idxs, dists, grad_imag
 # compositors
 # ----------------------------------------------------------------------------------------------
 _ALPHA, _NORM, _SUM = _lib.COMPOSITE_ALPHA, _lib.COMPOSITE_NORM_SUM, _lib.COMPOSITE_SUM
-
-
-def _strides4(t):
-    return (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
 
 
 def _composite_check(features, alphas, points_idx):
@@ -843,23 +813,15 @@ def _feature_layout(features):
     return f, (P, 1), False
 
 
-def _strides2(st):
-    return (ctypes.c_int64 * 2)(int(st[0]), int(st[1]))
-
-
 def _composite_forward(mode, name, features, alphas, points_idx):
     dev = _composite_check(features, alphas, points_idx)
     feats, fst, _ = _feature_layout(features)
     N, K, H, W = alphas.shape
     C, P = feats.shape
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
-        if out.numel() == 0:
-            return out
-        rc = lib.p3d_composite_forward(mode, _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
-                                       _strides4(alphas), _strides4(points_idx), _ptr(out), _stream(dev))
-        _lib.check(rc, name)
+    out = torch.empty((N, C, H, W), dtype=torch.float32, device=dev)
+    if out.numel() == 0:
+        return out
+    _lib.call("p3d_composite_forward", name, dev, mode, feats, fst, alphas, points_idx, N, C, P, K, H, W, alphas.stride(), points_idx.stride(), out)
     return out
 
 
@@ -871,24 +833,21 @@ def _composite_backward(mode, name, grad_outputs, features, alphas, points_idx):
     N, K, H, W = alphas.shape
     C, P = feats.shape
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        # grad_features in the layout of the features: (C, P) planes, or -- for the renderers' transposed (P, C) view -- the
-        # transposed view of a (P, C) tensor (the permute in front of the operator then hands autograd a contiguous gradient)
-        if interleaved:
-            gf = torch.empty((P, C), dtype=torch.float32, device=dev).t()
-        else:
-            gf = torch.empty((C, P), dtype=torch.float32, device=dev)
-        ga = torch.empty((N, K, H, W), dtype=torch.float32, device=dev)
-        if _ordered():
-            hits = _sorted_hits(points_idx)  # in the logical (N, K, H, W) order, whatever the strides
-            ws = _workspace(lib.p3d_composite_backward_ordered_workspace_bytes(N, K, H, W, C, hits.numel()), dev)
-            rc = lib.p3d_composite_backward_ordered(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), _ptr(hits),
-                                                    hits.numel(), N, C, P, K, H, W, _strides4(alphas), _strides4(points_idx), _ptr(gf),
-                                                    _strides2(fst), _ptr(ga), _ptr(ws), ws.numel(), _stream(dev))
-        else:
-            rc = lib.p3d_composite_backward(mode, _ptr(go), _ptr(feats), _strides2(fst), _ptr(alphas), _ptr(points_idx), N, C, P, K, H, W,
-                                            _strides4(alphas), _strides4(points_idx), _ptr(gf), _strides2(fst), _ptr(ga), _stream(dev))
-        _lib.check(rc, name)
+    # grad_features in the layout of the features: (C, P) planes, or -- for the renderers' transposed (P, C) view -- the
+    # transposed view of a (P, C) tensor (the permute in front of the operator then hands autograd a contiguous gradient)
+    if interleaved:
+        gf = torch.empty((P, C), dtype=torch.float32, device=dev).t()
+    else:
+        gf = torch.empty((C, P), dtype=torch.float32, device=dev)
+    ga = torch.empty((N, K, H, W), dtype=torch.float32, device=dev)
+    if _ordered():
+        hits = _sorted_hits(points_idx)  # in the logical (N, K, H, W) order, whatever the strides
+        ws = _workspace(lib.p3d_composite_backward_ordered_workspace_bytes(N, K, H, W, C, hits.numel()), dev)
+        _lib.call("p3d_composite_backward_ordered", name, dev, mode, go, feats, fst, alphas, points_idx, hits, hits.numel(), N, C, P, K, H, W,
+                  alphas.stride(), points_idx.stride(), gf, fst, ga, ws, ws.numel())
+    else:
+        _lib.call("p3d_composite_backward", name, dev, mode, go, feats, fst, alphas, points_idx, N, C, P, K, H, W, alphas.stride(),
+                  points_idx.stride(), gf, fst, ga)
     return gf, ga
 
 
@@ -940,14 +899,10 @@ def interp_face_attrs_forward(pix_to_face, barycentric_coords, face_attrs):
     p2f = _c(pix_to_face, torch.int64)
     bary, attrs = barycentric_coords.contiguous(), face_attrs.contiguous()
     F, _, D = attrs.shape
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((P, D), dtype=attrs.dtype, device=dev)
-        if out.numel() == 0:
-            return out
-        rc = lib.p3d_interp_face_attrs_forward(_DTYPES[attrs.dtype], _ptr(p2f), _ptr(bary), _ptr(attrs), P, F, D,
-                                               _ptr(out), _stream(dev))
-        _lib.check(rc, "interp_face_attrs_forward")
+    out = torch.empty((P, D), dtype=attrs.dtype, device=dev)
+    if out.numel() == 0:
+        return out
+    _lib.call("p3d_interp_face_attrs_forward", "interp_face_attrs_forward", dev, _DTYPES[attrs.dtype], p2f, bary, attrs, P, F, D, out)
     return out
 
 
@@ -971,26 +926,20 @@ def interp_face_attrs_backward(pix_to_face, barycentric_coords, face_attrs, grad
     p2f = _c(pix_to_face, torch.int64)
     bary, attrs, g = barycentric_coords.contiguous(), face_attrs.contiguous(), grad_pix_attrs.contiguous()
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        gb = torch.empty((P, 3), dtype=attrs.dtype, device=dev)
-        gf = torch.empty((F, 3, D), dtype=attrs.dtype, device=dev)
-        if _ordered():  # (image-shaped or not: one entry, the same bits)
-            hits = _sorted_hits(p2f)
-            ws = _workspace(lib.p3d_interp_face_attrs_backward_ordered_workspace_bytes(D, hits.numel()), dev)
-            rc = lib.p3d_interp_face_attrs_backward_ordered(_ptr(p2f), _ptr(bary), _ptr(attrs), _ptr(g), _ptr(hits), hits.numel(), P, F, D,
-                                                            _ptr(gb), _ptr(gf), _ptr(ws), ws.numel(), _stream(dev))
-            _lib.check(rc, "interp_face_attrs_backward")
-            return gb, gf
-        if (image_shape is not None and attrs.dtype == torch.float32 and 1 <= D <= 4 and F > 0
-                and image_shape[0] * image_shape[1] * image_shape[2] * image_shape[3] == P):
-            n_, h_, w_, k_ = (int(x) for x in image_shape)
-            rc = lib.p3d_interp_face_attrs_backward_nhwk(_ptr(p2f), _ptr(bary), _ptr(attrs), _ptr(g), n_, h_, w_, k_, F, D,
-                                                         _ptr(gb), _ptr(gf), _stream(dev))
-            _lib.check(rc, "interp_face_attrs_backward")
-            return gb, gf
-        rc = lib.p3d_interp_face_attrs_backward(_DTYPES[attrs.dtype], _ptr(p2f), _ptr(bary), _ptr(attrs), _ptr(g), P, F,
-                                                D, _ptr(gb), _ptr(gf), _stream(dev))
-        _lib.check(rc, "interp_face_attrs_backward")
+    gb = torch.empty((P, 3), dtype=attrs.dtype, device=dev)
+    gf = torch.empty((F, 3, D), dtype=attrs.dtype, device=dev)
+    if _ordered():  # (image-shaped or not: one entry, the same bits)
+        hits = _sorted_hits(p2f)
+        ws = _workspace(lib.p3d_interp_face_attrs_backward_ordered_workspace_bytes(D, hits.numel()), dev)
+        _lib.call("p3d_interp_face_attrs_backward_ordered", "interp_face_attrs_backward", dev, p2f, bary, attrs, g, hits, hits.numel(), P, F, D,
+                  gb, gf, ws, ws.numel())
+        return gb, gf
+    if (image_shape is not None and attrs.dtype == torch.float32 and 1 <= D <= 4 and F > 0
+            and image_shape[0] * image_shape[1] * image_shape[2] * image_shape[3] == P):
+        n_, h_, w_, k_ = (int(x) for x in image_shape)
+        _lib.call("p3d_interp_face_attrs_backward_nhwk", "interp_face_attrs_backward", dev, p2f, bary, attrs, g, n_, h_, w_, k_, F, D, gb, gf)
+        return gb, gf
+    _lib.call("p3d_interp_face_attrs_backward", "interp_face_attrs_backward", dev, _DTYPES[attrs.dtype], p2f, bary, attrs, g, P, F, D, gb, gf)
     return gb, gf
 
 
@@ -1004,13 +953,10 @@ def sigmoid_alpha_blend(distances, pix_to_face, sigma):
         raise RuntimeError("distances and pix_to_face must both have shape (N, H, W, K)")
     d, p2f = _c(distances, torch.float32), _c(pix_to_face, torch.int64)
     N, H, W, K = d.shape
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((N, H, W), dtype=torch.float32, device=dev)
-        if out.numel() == 0:
-            return out
-        rc = lib.p3d_sigmoid_alpha_blend_forward(_ptr(d), _ptr(p2f), float(sigma), N * H * W, K, _ptr(out), _stream(dev))
-        _lib.check(rc, "sigmoid_alpha_blend")
+    out = torch.empty((N, H, W), dtype=torch.float32, device=dev)
+    if out.numel() == 0:
+        return out
+    _lib.call("p3d_sigmoid_alpha_blend_forward", "sigmoid_alpha_blend", dev, d, p2f, float(sigma), N * H * W, K, out)
     return out
 
 
@@ -1021,14 +967,10 @@ def sigmoid_alpha_blend_backward(grad_alphas, alphas, distances, pix_to_face, si
     d, p2f = _c(distances, torch.float32), _c(pix_to_face, torch.int64)
     ga, al = _c(grad_alphas, torch.float32), _c(alphas, torch.float32)
     N, H, W, K = d.shape
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
-        if out.numel() == 0:
-            return out
-        rc = lib.p3d_sigmoid_alpha_blend_backward(_ptr(ga), _ptr(al), _ptr(d), _ptr(p2f), float(sigma), N * H * W, K,
-                                                  _ptr(out), _stream(dev))
-        _lib.check(rc, "sigmoid_alpha_blend_backward")
+    out = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+    if out.numel() == 0:
+        return out
+    _lib.call("p3d_sigmoid_alpha_blend_backward", "sigmoid_alpha_blend_backward", dev, ga, al, d, p2f, float(sigma), N * H * W, K, out)
     return out
 
 
@@ -1063,19 +1005,15 @@ def knn_points_idx(p1, p2, lengths1, lengths2, norm, K, version=-1, _out=None):
     dev, lengths1, lengths2 = _knn_check(p1, p2, lengths1, lengths2, K, "knn_points_idx")
     p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
     N, P1, D = p1.shape
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        if _out is None:
-            idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-            dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-        else:
-            idx, dists = _out
-            if (idx.shape != (N, P1, K) or dists.shape != (N, P1, K) or idx.dtype != torch.int64 or dists.dtype != torch.float32
-                    or not idx.is_contiguous() or not dists.is_contiguous() or idx.device != dev or dists.device != dev):
-                raise RuntimeError("knn_points_idx: _out must be contiguous (N, P1, K) int64 and float32 tensors on the inputs' GPU")
-        rc = lib.p3d_knn_points_forward(_ptr(p1), _ptr(p2), _ptr(lengths1), _ptr(lengths2), N, P1, p2.shape[1], D, K, int(norm),
-                                        _ptr(idx), _ptr(dists), _stream(dev))
-        _lib.check(rc, "knn_points_idx")
+    if _out is None:
+        idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    else:
+        idx, dists = _out
+        if (idx.shape != (N, P1, K) or dists.shape != (N, P1, K) or idx.dtype != torch.int64 or dists.dtype != torch.float32
+                or not idx.is_contiguous() or not dists.is_contiguous() or idx.device != dev or dists.device != dev):
+            raise RuntimeError("knn_points_idx: _out must be contiguous (N, P1, K) int64 and float32 tensors on the inputs' GPU")
+    _lib.call("p3d_knn_points_forward", "knn_points_idx", dev, p1, p2, lengths1, lengths2, N, P1, p2.shape[1], D, K, int(norm), idx, dists)
     return idx, dists
 
 
@@ -1094,12 +1032,11 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _nee
     dev, lengths1, lengths2 = _knn_check(p1, p2, lengths1, lengths2, max(1, min(K, _lib.KNN_MAX_K)), "knn_points_backward")
     p1, p2, idxs = _c(p1, torch.float32), _c(p2, torch.float32), _c(idxs, torch.int64)
     g = grad_dists.to(torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        grad_p1 = torch.empty_like(p1) if _needs[0] else None
-        grad_p2 = torch.empty_like(p2) if _needs[1] else None
-        if K == 0:
-            return (None if grad_p1 is None else grad_p1.zero_()), (None if grad_p2 is None else grad_p2.zero_())
-        _knn.backward_kernels(p1, p2, lengths1, lengths2, idxs, K, int(norm), g, None, grad_p1, grad_p2)
+    grad_p1 = torch.empty_like(p1) if _needs[0] else None
+    grad_p2 = torch.empty_like(p2) if _needs[1] else None
+    if K == 0:
+        return (None if grad_p1 is None else grad_p1.zero_()), (None if grad_p2 is None else grad_p2.zero_())
+    _knn.backward_kernels(p1, p2, lengths1, lengths2, idxs, K, int(norm), g, None, grad_p1, grad_p2)
     return grad_p1, grad_p2
 
 
@@ -1137,15 +1074,12 @@ def sample_farthest_points(points, lengths, K, start_idxs, max_K_known=-1):
     max_K = max(max_K, 0)
     points = _c(points, torch.float32)
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        if N == 0 or P == 0 or max_K == 0:
-            return torch.full((N, max_K), -1, dtype=torch.int64, device=dev)
-        idx = torch.empty((N, max_K), dtype=torch.int64, device=dev)
-        nbytes = lib.p3d_sample_farthest_points_workspace_bytes(N, P)
-        ws = _workspace(nbytes, dev) if nbytes else None
-        rc = lib.p3d_sample_farthest_points(_ptr(points), _ptr(lengths), _ptr(K), _ptr(start_idxs), N, P, D, max_K, _ptr(idx), _ptr(ws),
-                                            nbytes, _stream(dev))
-        _lib.check(rc, who)
+    if N == 0 or P == 0 or max_K == 0:
+        return torch.full((N, max_K), -1, dtype=torch.int64, device=dev)
+    idx = torch.empty((N, max_K), dtype=torch.int64, device=dev)
+    nbytes = lib.p3d_sample_farthest_points_workspace_bytes(N, P)
+    ws = _workspace(nbytes, dev) if nbytes else None
+    _lib.call("p3d_sample_farthest_points", who, dev, points, lengths, K, start_idxs, N, P, D, max_K, idx, ws, nbytes)
     return idx
 
 
@@ -1163,13 +1097,9 @@ def ball_query(p1, p2, lengths1, lengths2, K, radius, skip_points_outside_cube=F
     N, P1, D = p1.shape
     lengths1, lengths2 = _int64_arg(lengths1, N, dev, "lengths1", who), _int64_arg(lengths2, N, dev, "lengths2", who)
     p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
-        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
-        rc = lib.p3d_ball_query(_ptr(p1), _ptr(p2), _ptr(lengths1), _ptr(lengths2), N, P1, p2.shape[1], D, K, float(radius), _ptr(idx),
-                                _ptr(dists), _stream(dev))
-        _lib.check(rc, who)
+    idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    _lib.call("p3d_ball_query", who, dev, p1, p2, lengths1, lengths2, N, P1, p2.shape[1], D, K, float(radius), idx, dists)
     return idx, dists
 
 
@@ -1191,16 +1121,12 @@ def point_frames(points, lengths, K, disambiguate_directions=True, frames=True, 
     N, P, D = points.shape
     lengths = _int64_arg(lengths, N, dev, "lengths", who)
     points = _c(points, torch.float32)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        curv_t = torch.empty((N, P, 3), dtype=torch.float32, device=dev) if frames else None
-        frames_t = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev) if frames else None
-        cov_t = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev) if cov else None
-        idx_t = torch.empty((N, P, K), dtype=torch.int64, device=dev) if idx else None
-        flags = _lib.FRAMES_DISAMBIGUATE if disambiguate_directions else 0
-        rc = lib.p3d_point_frames(_ptr(points), _ptr(lengths), N, P, D, K, flags, _ptr(curv_t), _ptr(frames_t), _ptr(cov_t), _ptr(idx_t),
-                                  _stream(dev))
-        _lib.check(rc, who)
+    curv_t = torch.empty((N, P, 3), dtype=torch.float32, device=dev) if frames else None
+    frames_t = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev) if frames else None
+    cov_t = torch.empty((N, P, 3, 3), dtype=torch.float32, device=dev) if cov else None
+    idx_t = torch.empty((N, P, K), dtype=torch.int64, device=dev) if idx else None
+    flags = _lib.FRAMES_DISAMBIGUATE if disambiguate_directions else 0
+    _lib.call("p3d_point_frames", who, dev, points, lengths, N, P, D, K, flags, curv_t, frames_t, cov_t, idx_t)
     return curv_t, frames_t, cov_t, idx_t
 
 
@@ -1228,17 +1154,15 @@ def iou_box3d(boxes1, boxes2, lds_capacity=None, return_overflow=False):
     cap = _lib.BOX3D_LDS_CAPACITY if lds_capacity is None else int(lds_capacity)
     boxes1, boxes2 = boxes1.contiguous(), boxes2.contiguous()
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        vol = torch.empty((N, M), dtype=torch.float32, device=dev)
-        iou = torch.empty((N, M), dtype=torch.float32, device=dev)
-        if N * M == 0:
-            return (vol, iou, torch.zeros((), dtype=torch.int32, device=dev)) if return_overflow else (vol, iou)
-        nbytes = lib.p3d_iou_box3d_workspace_bytes(N, M)
-        ws = _workspace(nbytes, dev)
-        rc = lib.p3d_iou_box3d(_ptr(boxes1), _ptr(boxes2), N, M, cap, _ptr(vol), _ptr(iou), _ptr(ws), nbytes, _stream(dev))
-        _lib.check(rc, who)
-        if return_overflow:
-            return vol, iou, ws[:4].view(torch.int32)[0].clone()
+    vol = torch.empty((N, M), dtype=torch.float32, device=dev)
+    iou = torch.empty((N, M), dtype=torch.float32, device=dev)
+    if N * M == 0:
+        return (vol, iou, torch.zeros((), dtype=torch.int32, device=dev)) if return_overflow else (vol, iou)
+    nbytes = lib.p3d_iou_box3d_workspace_bytes(N, M)
+    ws = _workspace(nbytes, dev)
+    _lib.call("p3d_iou_box3d", who, dev, boxes1, boxes2, N, M, cap, vol, iou, ws, nbytes)
+    if return_overflow:
+        return vol, iou, ws[:4].view(torch.int32)[0].clone()
     return vol, iou
 
 
@@ -1253,7 +1177,7 @@ def iou_box3d_host(boxes1, boxes2):
     vol = torch.empty((N, M), dtype=torch.float32)
     iou = torch.empty((N, M), dtype=torch.float32)
     if N * M:
-        _lib.check(_lib.load().p3d_iou_box3d_host(_ptr(boxes1), _ptr(boxes2), N, M, _ptr(vol), _ptr(iou)), who)
+        _lib.call("p3d_iou_box3d_host", who, None, boxes1, boxes2, N, M, vol, iou)
     return vol, iou
 
 
@@ -1282,14 +1206,11 @@ def neighbor_sum(rows, offsets, entries, base=None):
     rows = row_view(rows)
     base = row_view(base) if base is not None else None
     offsets, entries = offsets.contiguous(), entries.contiguous()
-    with torch.cuda.device(dev):
-        out = torch.empty((V, D), dtype=torch.float32, device=dev)
-        if V * D == 0:
-            return out
-        rc = _lib.load().p3d_neighbor_sum(_ptr(rows), rows.stride(0) if rows.numel() else 0, n_rows, _ptr(base),
-                                          base.stride(0) if base is not None else 0, _ptr(offsets), _ptr(entries), V,
-                                          entries.numel(), D, _ptr(out), D, _stream(dev))
-        _lib.check(rc, who)
+    out = torch.empty((V, D), dtype=torch.float32, device=dev)
+    if V * D == 0:
+        return out
+    _lib.call("p3d_neighbor_sum", who, dev, rows, rows.stride(0) if rows.numel() else 0, n_rows, base, base.stride(0) if base is not None else 0,
+              offsets, entries, V, entries.numel(), D, out, D)
     return out
 
 
@@ -1327,19 +1248,16 @@ def vert_align_forward(feats, grid, packed_idx, flags):
     who = "vert_align_forward"
     dev, N, V, rows, packed_idx = _vert_align_args(who, feats, grid, packed_idx)
     total = sum(f.shape[1] for f in feats)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        out = torch.empty((rows, total), dtype=torch.float32, device=dev)
-        col = 0
-        for f in feats:
-            C, H, W = f.shape[1:]
-            if H * W == 0 and rows * C:
-                raise RuntimeError(f"{who}: a feature map without pixels")
-            if rows * C:
-                rc = lib.p3d_vert_align_forward(_ptr(f), N, C, H, W, *f.stride(), _ptr(grid), V, *grid.stride(), _ptr(packed_idx), rows,
-                                                flags, ctypes.c_void_p(out.data_ptr() + 4 * col), total, _stream(dev))
-                _lib.check(rc, who)
-            col += C
+    out = torch.empty((rows, total), dtype=torch.float32, device=dev)
+    col = 0
+    for f in feats:
+        C, H, W = f.shape[1:]
+        if H * W == 0 and rows * C:
+            raise RuntimeError(f"{who}: a feature map without pixels")
+        if rows * C:
+            _lib.call("p3d_vert_align_forward", who, dev, f, N, C, H, W, *f.stride(), grid, V, *grid.stride(), packed_idx, rows, flags,
+                      out[:, col:], total)
+        col += C
     return out
 
 
@@ -1358,36 +1276,31 @@ def vert_align_backward(grad_out, feats, grid, packed_idx, flags, need_feats, ne
     if strict and any(nf and N * f.shape[2] * f.shape[3] > MAX_INT for f, nf in zip(feats, need_feats)):
         raise NotImplementedError(f"{who}: the deterministic form keys a pixel by an int32 and N * H * W does not fit")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        grad_verts = torch.zeros((N, V, 3), dtype=torch.float32, device=dev) if need_verts else None
-        grads = []
-        col = 0
-        for f, nf in zip(feats, need_feats):
-            C, H, W = f.shape[1:]
-            gf = torch.zeros_like(f) if nf else None
-            go = ctypes.c_void_p(grad_out.data_ptr() + 4 * col)
-            ordered = strict or (f.stride(1) != 1 and C >= VERT_ALIGN_STRIDED_ORDERED_MIN_C and N * H * W <= MAX_INT)
-            if rows * C and H * W and (nf or need_verts):
-                atomic = nf and not ordered
-                if atomic or need_verts:
-                    rc = lib.p3d_vert_align_backward(go, total, _ptr(f), N, C, H, W, *f.stride(), _ptr(grid), V, *grid.stride(), _ptr(packed_idx),
-                                                     rows, flags, _ptr(gf) if atomic else None, *(gf.stride() if atomic else (0, 0, 0, 0)),
-                                                     _ptr(grad_verts), _stream(dev))
-                    _lib.check(rc, who)
-                if nf and ordered:
-                    keys = torch.empty((rows * 4,), dtype=torch.int32, device=dev)
-                    rc = lib.p3d_vert_align_keys(N, H, W, _ptr(grid), V, *grid.stride(), _ptr(packed_idx), rows, flags, _ptr(keys), _stream(dev))
-                    _lib.check(rc, who)
-                    order = torch.sort(keys, stable=True).indices
-                    nbytes = lib.p3d_vert_align_workspace_bytes(rows, C)
-                    ws = _workspace(nbytes, dev)
-                    rc = lib.p3d_vert_align_ordered_backward(go, total, N, C, H, W, _ptr(grid), V, *grid.stride(), _ptr(packed_idx), rows, flags,
-                                                             _ptr(keys), _ptr(order), _ptr(gf), *gf.stride(), _ptr(ws), nbytes, _stream(dev))
-                    _lib.check(rc, who)
-                if nf:
-                    VERT_ALIGN_CALLS["ordered" if ordered else "atomic"] += 1
-            grads.append(gf)
-            col += C
+    grad_verts = torch.zeros((N, V, 3), dtype=torch.float32, device=dev) if need_verts else None
+    grads = []
+    col = 0
+    for f, nf in zip(feats, need_feats):
+        C, H, W = f.shape[1:]
+        gf = torch.zeros_like(f) if nf else None
+        go = grad_out[:, col:]  # this map's column block; the row stride stays `total`
+        ordered = strict or (f.stride(1) != 1 and C >= VERT_ALIGN_STRIDED_ORDERED_MIN_C and N * H * W <= MAX_INT)
+        if rows * C and H * W and (nf or need_verts):
+            atomic = nf and not ordered
+            if atomic or need_verts:
+                _lib.call("p3d_vert_align_backward", who, dev, go, total, f, N, C, H, W, *f.stride(), grid, V, *grid.stride(), packed_idx, rows,
+                          flags, gf if atomic else None, *(gf.stride() if atomic else (0, 0, 0, 0)), grad_verts)
+            if nf and ordered:
+                keys = torch.empty((rows * 4,), dtype=torch.int32, device=dev)
+                _lib.call("p3d_vert_align_keys", who, dev, N, H, W, grid, V, *grid.stride(), packed_idx, rows, flags, keys)
+                order = torch.sort(keys, stable=True).indices
+                nbytes = lib.p3d_vert_align_workspace_bytes(rows, C)
+                ws = _workspace(nbytes, dev)
+                _lib.call("p3d_vert_align_ordered_backward", who, dev, go, total, N, C, H, W, grid, V, *grid.stride(), packed_idx, rows, flags,
+                          keys, order, gf, *gf.stride(), ws, nbytes)
+            if nf:
+                VERT_ALIGN_CALLS["ordered" if ordered else "atomic"] += 1
+        grads.append(gf)
+        col += C
     return grads, grad_verts
 
 
@@ -1411,7 +1324,8 @@ def _p2v_cloud(who, points_3d, grid_sizes, mask, **others):
 
 
 def _p2v_volume(who, name, t, N, C, DHW, dev):
-    """The five element strides of a float32 (N, C, D, H, W) volume, as the C ABI takes them."""
+    """The five element strides of a float32 (N, C, D, H, W) volume, as the C ABI takes them: a host array behind a `const int64_t*`, so
+    its address goes to _lib.call as a plain int (no tensor view can stand for host memory there)."""
     if t.dtype != torch.float32 or t.device != dev or t.dim() != 5 or t.shape[0] != N or t.shape[1] != C or tuple(t.shape[2:]) != DHW:
         raise RuntimeError(f"{who}: {name} must be a float32 tensor of shape ({N}, {C}, {DHW[0]}, {DHW[1]}, {DHW[2]}) on {dev}")
     return (ctypes.c_int64 * 5)(*t.stride())
@@ -1437,24 +1351,20 @@ def points_to_volumes_forward(points_3d, points_features, volume_densities, volu
     feats = _c(points_features, torch.float32)
     splat, align = int(bool(splat)), int(bool(align_corners))
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        keys = order = ws = None
-        nbytes = 0
-        if _ordered() and N * P > 0 and DHW[0] * DHW[1] * DHW[2] > 0:
-            if N * DHW[0] * DHW[1] * DHW[2] > MAX_INT:
-                raise RuntimeError(f"{who}: the deterministic form keys a voxel by an int32 and N * D * H * W = "
-                                   f"{N * DHW[0] * DHW[1] * DHW[2]} does not fit; add the batch in pieces")
-            keys = torch.empty((N * P * (8 if splat else 1),), dtype=torch.int32, device=dev)
-            rc = lib.p3d_points_to_volumes_keys(_ptr(points), _ptr(grid), _ptr(mask), mask.stride(0), mask.stride(1), N, P, *DHW, align,
-                                                splat, _ptr(keys), _stream(dev))
-            _lib.check(rc, who)
-            order = torch.sort(keys, stable=True).indices
-            nbytes = lib.p3d_points_to_volumes_workspace_bytes(N, P, C, splat)
-            ws = _workspace(nbytes, dev)
-        rc = lib.p3d_points_to_volumes_forward(_ptr(points), _ptr(feats), _ptr(grid), _ptr(mask), mask.stride(0), mask.stride(1), N, P, C,
-                                               *DHW, _ptr(volume_densities), dstr, _ptr(volume_features), fstr, float(point_weight),
-                                               align, splat, _ptr(keys), _ptr(order), _ptr(ws), nbytes, _stream(dev))
-        _lib.check(rc, who)
+    keys = order = ws = None
+    nbytes = 0
+    if _ordered() and N * P > 0 and DHW[0] * DHW[1] * DHW[2] > 0:
+        if N * DHW[0] * DHW[1] * DHW[2] > MAX_INT:
+            raise RuntimeError(f"{who}: the deterministic form keys a voxel by an int32 and N * D * H * W = "
+                               f"{N * DHW[0] * DHW[1] * DHW[2]} does not fit; add the batch in pieces")
+        keys = torch.empty((N * P * (8 if splat else 1),), dtype=torch.int32, device=dev)
+        _lib.call("p3d_points_to_volumes_keys", who, dev, points, grid, mask, mask.stride(0), mask.stride(1), N, P, *DHW, align, splat, keys)
+        order = torch.sort(keys, stable=True).indices
+        nbytes = lib.p3d_points_to_volumes_workspace_bytes(N, P, C, splat)
+        ws = _workspace(nbytes, dev)
+    _lib.call("p3d_points_to_volumes_forward", who, dev, points, feats, grid, mask, mask.stride(0), mask.stride(1), N, P, C, *DHW,
+              volume_densities, ctypes.addressof(dstr), volume_features, ctypes.addressof(fstr), float(point_weight), align, splat, keys, order,
+              ws, nbytes)
     POINTS_TO_VOLUMES_CALLS["ordered" if order is not None else "atomic"] += 1
 
 
@@ -1484,12 +1394,9 @@ def points_to_volumes_backward(points_3d, points_features, grid_sizes, mask, poi
         feats = _c(points_features, torch.float32)
         gp = grad_points_3d.contiguous()  # (a copy only for a strided buffer; written back below)
     gf = grad_points_features.contiguous()
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        rc = lib.p3d_points_to_volumes_backward(_ptr(points), _ptr(feats), _ptr(grid), _ptr(mask), mask.stride(0), mask.stride(1), N, P, C,
-                                                *DHW, _ptr(grad_volume_densities), dstr, _ptr(grad_volume_features), fstr,
-                                                float(point_weight), int(bool(align_corners)), splat, _ptr(gp), _ptr(gf), _stream(dev))
-        _lib.check(rc, who)
+    _lib.call("p3d_points_to_volumes_backward", who, dev, points, feats, grid, mask, mask.stride(0), mask.stride(1), N, P, C, *DHW,
+              grad_volume_densities, ctypes.addressof(dstr), grad_volume_features, ctypes.addressof(fstr), float(point_weight),
+              int(bool(align_corners)), splat, gp, gf)
     if gf is not grad_points_features:
         grad_points_features.copy_(gf)
     if splat and gp is not grad_points_3d:
@@ -1538,17 +1445,15 @@ def point_mesh_forward(direction, points, points_first_idx, prims, prims_first_i
         if weights.shape != (N,):
             raise RuntimeError(f"{who}: weights must have shape (N,)")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        dists = torch.empty((Q,), dtype=torch.float32, device=dev)
-        idxs = torch.empty((Q,), dtype=torch.int64, device=dev)
-        sums, ws, nbytes = None, None, 0
-        if with_sums:
-            sums = torch.empty((N,), dtype=torch.float32, device=dev)
-            nbytes = lib.p3d_point_mesh_forward_workspace_bytes(N, max_queries)
-            ws = _workspace(nbytes, dev)
-        rc = lib.p3d_point_mesh_forward(qk, tk, _ptr(q), _ptr(t), _ptr(qf), _ptr(tf), N, Q, T, max_queries, float(min_triangle_area),
-                                        int(split), _ptr(weights), _ptr(dists), _ptr(idxs), _ptr(sums), _ptr(ws), nbytes, _stream(dev))
-        _lib.check(rc, who)
+    dists = torch.empty((Q,), dtype=torch.float32, device=dev)
+    idxs = torch.empty((Q,), dtype=torch.int64, device=dev)
+    sums, ws, nbytes = None, None, 0
+    if with_sums:
+        sums = torch.empty((N,), dtype=torch.float32, device=dev)
+        nbytes = lib.p3d_point_mesh_forward_workspace_bytes(N, max_queries)
+        ws = _workspace(nbytes, dev)
+    _lib.call("p3d_point_mesh_forward", who, dev, qk, tk, q, t, qf, tf, N, Q, T, max_queries, float(min_triangle_area), int(split), weights,
+              dists, idxs, sums, ws, nbytes)
     return (dists, idxs, sums) if with_sums else (dists, idxs)
 
 
@@ -1577,24 +1482,22 @@ def point_mesh_backward(direction, points, prims, idxs, grad_dists, min_triangle
     g = None if grad_dists is None else grad_dists.to(torch.float32).contiguous()
     scale = None if elem_scale is None else _c(elem_scale, torch.float32)
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        for name, buf, like in (("grad_points", grad_points, points), ("grad_prims", grad_prims, prims)):
-            if buf is not None and (buf.shape != like.shape or buf.dtype != torch.float32 or buf.device != dev or not buf.is_contiguous()):
-                raise RuntimeError(f"{who}: {name} must be a contiguous float32 tensor shaped like its input, on the inputs' GPU")
-        if accumulate and (grad_points is None or grad_prims is None):
-            raise RuntimeError(f"{who}: accumulate needs both gradient buffers")
-        grad_points = torch.empty_like(points) if grad_points is None else grad_points
-        grad_prims = torch.empty_like(prims) if grad_prims is None else grad_prims
-        gq, gt = (grad_points, grad_prims) if point_query else (grad_prims, grad_points)
-        flags = (_lib.POINT_MESH_ACCUMULATE_QUERIES | _lib.POINT_MESH_ACCUMULATE_TARGETS) if accumulate else 0
-        hits, ws, nbytes = None, None, 0
-        if _ordered() and Q > 0 and T > 0:
-            hits = torch.sort(idxs, stable=True).indices.contiguous()
-            nbytes = lib.p3d_point_mesh_backward_workspace_bytes(tk, Q)
-            ws = _workspace(nbytes, dev)
-        rc = lib.p3d_point_mesh_backward(qk, tk, _ptr(q), _ptr(t), _ptr(idxs), _ptr(g), _ptr(scale), _ptr(qf), _ptr(tf), N, Q, T,
-                                         float(min_triangle_area), flags, _ptr(hits), _ptr(gq), _ptr(gt), _ptr(ws), nbytes, _stream(dev))
-        _lib.check(rc, who)
+    for name, buf, like in (("grad_points", grad_points, points), ("grad_prims", grad_prims, prims)):
+        if buf is not None and (buf.shape != like.shape or buf.dtype != torch.float32 or buf.device != dev or not buf.is_contiguous()):
+            raise RuntimeError(f"{who}: {name} must be a contiguous float32 tensor shaped like its input, on the inputs' GPU")
+    if accumulate and (grad_points is None or grad_prims is None):
+        raise RuntimeError(f"{who}: accumulate needs both gradient buffers")
+    grad_points = torch.empty_like(points) if grad_points is None else grad_points
+    grad_prims = torch.empty_like(prims) if grad_prims is None else grad_prims
+    gq, gt = (grad_points, grad_prims) if point_query else (grad_prims, grad_points)
+    flags = (_lib.POINT_MESH_ACCUMULATE_QUERIES | _lib.POINT_MESH_ACCUMULATE_TARGETS) if accumulate else 0
+    hits, ws, nbytes = None, None, 0
+    if _ordered() and Q > 0 and T > 0:
+        hits = torch.sort(idxs, stable=True).indices.contiguous()
+        nbytes = lib.p3d_point_mesh_backward_workspace_bytes(tk, Q)
+        ws = _workspace(nbytes, dev)
+    _lib.call("p3d_point_mesh_backward", who, dev, qk, tk, q, t, idxs, g, scale, qf, tf, N, Q, T, float(min_triangle_area), flags, hits, gq, gt,
+              ws, nbytes)
     return grad_points, grad_prims
 
 

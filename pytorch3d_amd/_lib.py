@@ -3,6 +3,10 @@
 The header is the one description of that ABI: the ctypes signatures and the integer constants of this module are read from it at
 import (parse_header), so an entry or a macro added there needs no second copy here.
 
+The wrappers reach every entry that returns a status through call(entry, where, device, *args), which marshals by the header's
+types: a tensor goes where a pointer is declared only with the declared element type and on `device`, else it raises before anything
+is launched.  The size, count and profile entries are plain calls on load().
+
 There is no fallback: if the HIP library is missing or cannot be loaded, every operator of this
 package raises.  Build it with `python -m pytorch3d_amd.build` (hipcc, gfx950).
 """
@@ -10,6 +14,8 @@ import ctypes
 import os
 import re
 import threading
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # P3D_LIB_PATH selects an ablation build (profiles/ scripts only; see build.py)
@@ -100,8 +106,84 @@ NEIGHBOR_SUM_GROUP_LANES = 256
 _SIGNATURES = {name: ctypes_signature(*decl) for name, decl in DECLARATIONS.items()}  # name: (restype, [argtypes])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
+# the torch dtypes a tensor may have where the header declares a pointer to this element type (None: any)
+_ELEMENTS = {"float": (torch.float32,), "double": (torch.float64,), "int64_t": (torch.int64,), "int32_t": (torch.int32,),
+             "uint8_t": (torch.uint8, torch.bool), "void": None}
+_HOST = torch.device("cpu")
+
+
+def _pointer(entry, pos, ctype):
+    """Converter of a `T*` parameter: None and an empty tensor are null, an int is an address as it stands, any other tensor its
+    data_ptr() after its dtype was checked against T and its device against the call's (None: the host)."""
+    element = ctype[len("const "):-1] if ctype.startswith("const ") else ctype[:-1]
+    if element not in _ELEMENTS:
+        raise ValueError(f"{entry}: no torch dtype for the elements of `{ctype}`")
+    dtypes = _ELEMENTS[element]
+
+    def convert(t, device):
+        if t is None or t.__class__ is int:
+            return t
+        if t.numel() == 0:
+            return None
+        if (dtypes is not None and t.dtype not in dtypes) or t.device != (device or _HOST):
+            raise RuntimeError(f"{entry}: argument {pos} is declared `{ctype}` and the call is for {device or 'the host'}; "
+                               f"got a {t.dtype} tensor on {t.device}")
+        return t.data_ptr()
+
+    return convert
+
+
+def _array(entry, pos, ctype):
+    """Converter of a `const T x[n]` parameter: a sequence of n numbers becomes the ctypes array."""
+    base, n = re.fullmatch(r"(?:const )?(\w+)\[(\d+)\]", ctype).groups()
+    n, kind = int(n), _SCALARS[base] * int(n)
+
+    def convert(seq, device):
+        if len(seq) != n:
+            raise ValueError(f"{entry}: argument {pos} is declared `{ctype}`; got {len(seq)} numbers")
+        return kind(*seq)
+
+    return convert
+
+
+def marshaller(entry, ret, params):
+    """(converters, takes a stream, returns a status) of a parsed declaration.  converters: one per parameter in header order without
+    the stream -- which is the last parameter or absent --, None where the argument goes to ctypes as it is (the scalars).  The entries
+    that return a status are the int ones that take a stream or a pointer."""
+    stream = params[-1:] == ["p3d_stream_t"]
+    taken = params[:-1] if stream else params
+    if "p3d_stream_t" in taken:
+        raise ValueError(f"{entry}: the p3d_stream_t must be the last parameter and occur once")
+    converters = tuple(_array(entry, i, p) if p.endswith("]") else _pointer(entry, i, p) if p.endswith("*") else None
+                       for i, p in enumerate(taken))
+    return converters, stream, ret == "int" and (stream or any(c is not None for c in converters))
+
+
+def bind(fn, entry, ret, params):
+    """invoke(where, device, *args) for call(): marshals args by the declaration, calls fn (with torch's current stream of `device`
+    behind them where the entry takes one, under the device's guard) and hands the code it returns to check(code, where)."""
+    converters, stream, _ = marshaller(entry, ret, params)
+    count = len(converters)
+    device_guard, current_stream = torch.cuda.device, torch.cuda.current_stream
+
+    def invoke(where, device, *args):
+        if len(args) != count:
+            raise TypeError(f"{entry} takes {count} arguments ({', '.join(params[:count])}), got {len(args)}")
+        cargs = [a if c is None else c(a, device) for c, a in zip(converters, args)]
+        if stream:
+            with device_guard(device):
+                code = fn(*cargs, current_stream(device).cuda_stream)
+        else:
+            code = fn(*cargs)
+        if code:
+            check(code, where)
+
+    return invoke
+
+
 _lock = threading.Lock()
 _lib = None
+_CALLS = {}  # status entry: its invoke, bound when load() installs the signatures
 
 
 def load():
@@ -128,8 +210,19 @@ def load():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res
             fn.argtypes = args
+            if marshaller(name, *DECLARATIONS[name])[2]:
+                _CALLS[name] = bind(fn, name, *DECLARATIONS[name])
         _lib = lib
     return _lib
+
+
+def call(entry, where, device, *args):
+    """Call a status entry of the library: args are its parameters in header order without the stream, tensors (or None) where it
+    declares pointers, sequences where it declares arrays.  device: the torch.device of the tensors and of the launch; None for the
+    host entry.  Raises like check(code, where) on a status other than P3D_OK."""
+    if _lib is None:
+        load()
+    _CALLS[entry](where, device, *args)
 
 
 def check(code, where):

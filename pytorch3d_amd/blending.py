@@ -10,7 +10,6 @@ graph in the reference (blending.py:147-244), is ONE kernel forward and ONE back
 `hard_depth_blend` / `soft_depth_blend` are the bodies of HardDepthShader.forward / SoftDepthShader.forward
 (renderer/mesh/shader.py:377-445) after their camera lookup, one kernel each way as well.
 """
-import ctypes
 from typing import NamedTuple, Sequence, Union
 
 import torch
@@ -62,7 +61,7 @@ def _background(blend_params, device, who="softmax_rgb_blend"):
     bg = [float(x) for x in bg]
     if len(bg) != 3:
         raise ValueError("background_color must have 3 elements")
-    return (ctypes.c_float * 3)(*bg)
+    return tuple(bg)
 
 
 def _plane(v, N, device):
@@ -89,14 +88,10 @@ class _SoftmaxRGBBlend(torch.autograd.Function):
         d, z, p2f = dists.contiguous(), zbuf.contiguous(), pix_to_face.contiguous()
         zn, zn_t = _plane(znear, N, dev)
         zf, zf_t = _plane(zfar, N, dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_softmax_rgb_blend_forward(_C._ptr(c), _C._ptr(p2f), _C._ptr(d), _C._ptr(z), float(sigma),
-                                                       float(gamma), bg, zn, zf, _C._ptr(zn_t), _C._ptr(zf_t), N, H * W,
-                                                       K, _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "softmax_rgb_blend")
+        out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_softmax_rgb_blend_forward", "softmax_rgb_blend", dev, c, p2f, d, z, float(sigma), float(gamma), bg, zn, zf, zn_t,
+                      zf_t, N, H * W, K, out)
         ctx.save_for_backward(c, d, z, p2f, zn_t if zn_t is not None else torch.empty(0, device=dev),
                               zf_t if zf_t is not None else torch.empty(0, device=dev))
         ctx.params = (float(sigma), float(gamma), bg, zn, zf, zn_t is not None, zf_t is not None)
@@ -109,17 +104,12 @@ class _SoftmaxRGBBlend(torch.autograd.Function):
         N, H, W, K = p2f.shape
         dev = c.device
         g = grad_out.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            gc = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
-            gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
-            if gd.numel():
-                rc = lib.p3d_softmax_rgb_blend_backward(_C._ptr(g), _C._ptr(c), _C._ptr(p2f), _C._ptr(d), _C._ptr(z),
-                                                        sigma, gamma, bg, zn, zf, _C._ptr(zn_t if has_zn else None),
-                                                        _C._ptr(zf_t if has_zf else None), N, H * W, K, _C._ptr(gc),
-                                                        _C._ptr(gd), _C._ptr(gz), _C._stream(dev))
-                _lib.check(rc, "softmax_rgb_blend_backward")
+        gc = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+        gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+        if gd.numel():
+            _lib.call("p3d_softmax_rgb_blend_backward", "softmax_rgb_blend_backward", dev, g, c, p2f, d, z, sigma, gamma, bg, zn, zf,
+                      zn_t if has_zn else None, zf_t if has_zf else None, N, H * W, K, gc, gd, gz)
         return gc, gd, gz, None, None, None, None, None, None
 
 
@@ -138,12 +128,9 @@ class _HardRGBBlend(torch.autograd.Function):
         N, H, W, K = pix_to_face.shape
         dev = colors.device
         c, p2f = colors.contiguous(), pix_to_face.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_hard_rgb_blend_forward(_C._ptr(c), _C._ptr(p2f), bg, N * H * W, K, _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "hard_rgb_blend")
+        out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_hard_rgb_blend_forward", "hard_rgb_blend", dev, c, p2f, bg, N * H * W, K, out)
         ctx.save_for_backward(p2f)
         return out
 
@@ -153,12 +140,9 @@ class _HardRGBBlend(torch.autograd.Function):
         N, H, W, K = p2f.shape
         dev = p2f.device
         g = grad_out.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            gc = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            if gc.numel():
-                rc = lib.p3d_hard_rgb_blend_backward(_C._ptr(g), _C._ptr(p2f), N * H * W, K, _C._ptr(gc), _C._stream(dev))
-                _lib.check(rc, "hard_rgb_blend_backward")
+        gc = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        if gc.numel():
+            _lib.call("p3d_hard_rgb_blend_backward", "hard_rgb_blend_backward", dev, g, p2f, N * H * W, K, gc)
         return gc, None, None
 
 
@@ -205,12 +189,9 @@ class _SoftDepthBlend(torch.autograd.Function):
         N, H, W, K = pix_to_face.shape
         dev = zbuf.device
         d, z, p2f = dists.contiguous(), zbuf.contiguous(), pix_to_face.contiguous()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = _lib.load().p3d_soft_depth_blend_forward(_C._ptr(d), _C._ptr(z), _C._ptr(p2f), sigma, zfar, N * H * W, K,
-                                                              _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "soft_depth_blend")
+        out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_soft_depth_blend_forward", "soft_depth_blend", dev, d, z, p2f, sigma, zfar, N * H * W, K, out)
         ctx.save_for_backward(d, z, p2f)
         ctx.params = (sigma, zfar)
         ctx.set_materialize_grads(False)
@@ -225,13 +206,10 @@ class _SoftDepthBlend(torch.autograd.Function):
         N, H, W, K = p2f.shape
         dev = z.device
         g = grad_depth.contiguous()
-        with torch.cuda.device(dev):
-            gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-            gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-            if p2f.numel() and (gd is not None or gz is not None):
-                rc = _lib.load().p3d_soft_depth_blend_backward(_C._ptr(g), _C._ptr(d), _C._ptr(z), _C._ptr(p2f), sigma, zfar,
-                                                               N * H * W, K, _C._ptr(gd), _C._ptr(gz), _C._stream(dev))
-                _lib.check(rc, "soft_depth_blend_backward")
+        gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        if p2f.numel() and (gd is not None or gz is not None):
+            _lib.call("p3d_soft_depth_blend_backward", "soft_depth_blend_backward", dev, g, d, z, p2f, sigma, zfar, N * H * W, K, gd, gz)
         return gd, gz, None, None, None
 
 
@@ -254,12 +232,9 @@ class _HardDepthBlend(torch.autograd.Function):
         N, H, W, K = pix_to_face.shape
         dev = zbuf.device
         z, p2f = zbuf.contiguous(), pix_to_face.contiguous()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = _lib.load().p3d_hard_depth_blend_forward(_C._ptr(z), _C._ptr(p2f), zfar, N * H * W, K, _C._ptr(out),
-                                                              _C._stream(dev))
-                _lib.check(rc, "hard_depth_blend")
+        out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_hard_depth_blend_forward", "hard_depth_blend", dev, z, p2f, zfar, N * H * W, K, out)
         ctx.save_for_backward(p2f)
         ctx.set_materialize_grads(False)
         return out
@@ -272,11 +247,9 @@ class _HardDepthBlend(torch.autograd.Function):
         N, H, W, K = p2f.shape
         dev = p2f.device
         g = grad_depth.contiguous()
-        with torch.cuda.device(dev):
-            gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
-            if gz.numel():
-                rc = _lib.load().p3d_hard_depth_blend_backward(_C._ptr(g), _C._ptr(p2f), N * H * W, K, _C._ptr(gz), _C._stream(dev))
-                _lib.check(rc, "hard_depth_blend_backward")
+        gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+        if gz.numel():
+            _lib.call("p3d_hard_depth_blend_backward", "hard_depth_blend_backward", dev, g, p2f, N * H * W, K, gz)
         return gz, None, None
 
 

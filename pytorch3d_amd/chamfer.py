@@ -71,9 +71,8 @@ def _direction_forward(lib, a, b, la, lb, weights, norm, point_mean):
     sums = torch.empty((N,), dtype=torch.float32, device=dev)
     nbytes = lib.p3d_chamfer_forward_workspace_bytes(N, P1)
     ws = _C._workspace(nbytes, dev)
-    rc = lib.p3d_chamfer_forward(_C._ptr(a), _C._ptr(b), _C._ptr(la), _C._ptr(lb), _C._ptr(weights), N, P1, b.shape[1], D, norm,
-                                 1 if point_mean else 0, _C._ptr(idx), _C._ptr(dists), _C._ptr(sums), _C._ptr(ws), nbytes, _C._stream(dev))
-    _lib.check(rc, "chamfer_distance forward")
+    _lib.call("p3d_chamfer_forward", "chamfer_distance forward", dev, a, b, la, lb, weights, N, P1, b.shape[1], D, norm, 1 if point_mean else 0, idx,
+              dists, sums, ws, nbytes)
     return idx, dists, sums
 
 
@@ -85,20 +84,19 @@ class _ChamferFused(torch.autograd.Function):
     def forward(ctx, x, y, x_lengths, y_lengths, weights, norm, point_mean, single_directional, batch_reduction):
         x, y = _C._c(x, torch.float32), _C._c(y, torch.float32)
         lib, dev, N = _lib.load(), x.device, x.shape[0]
-        with torch.cuda.device(dev):
-            idx_x, dists_x, per_cloud = _direction_forward(lib, x, y, x_lengths, y_lengths, weights, norm, point_mean)
-            idx_y = None
-            if not single_directional:
-                idx_y, dists_y, sums_y = _direction_forward(lib, y, x, y_lengths, x_lengths, weights, norm, point_mean)
-                per_cloud = per_cloud + sums_y
-            div = None
-            if batch_reduction is None:
-                out = per_cloud
-            else:
-                out = per_cloud.sum()
-                if batch_reduction == "mean":
-                    div = weights.sum() if weights is not None else float(max(N, 1))
-                    out = out / div
+        idx_x, dists_x, per_cloud = _direction_forward(lib, x, y, x_lengths, y_lengths, weights, norm, point_mean)
+        idx_y = None
+        if not single_directional:
+            idx_y, dists_y, sums_y = _direction_forward(lib, y, x, y_lengths, x_lengths, weights, norm, point_mean)
+            per_cloud = per_cloud + sums_y
+        div = None
+        if batch_reduction is None:
+            out = per_cloud
+        else:
+            out = per_cloud.sum()
+            if batch_reduction == "mean":
+                div = weights.sum() if weights is not None else float(max(N, 1))
+                out = out / div
         ctx.save_for_backward(x, y, idx_x, idx_y)
         ctx.aux = (x_lengths, y_lengths, weights, div)
         ctx.norm, ctx.point_mean, ctx.single, ctx.reduced = norm, point_mean, single_directional, batch_reduction is not None

@@ -6,7 +6,6 @@ reference's names, fields, return conventions, early exits and autograd behaviou
 the data, so one read-back is unavoidable), and the masked gather / bmm / scatter of the conversion is one
 kernel forward and one backward (include/p3d_amd.h: p3d_clip_faces_*, p3d_convert_clipped_*).
 """
-import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -60,20 +59,15 @@ class _ClipEmit(torch.autograd.Function):
         N = mesh_first.shape[0]
         dev = face_verts.device
         T = T3 + 2 * T4
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out_fv = torch.empty((Fc, 3, 3), dtype=torch.float32, device=dev)
-            first_c = torch.empty((N,), dtype=torch.int64, device=dev)
-            count_c = torch.empty((N,), dtype=torch.int64, device=dev)
-            c2u = torch.empty((Fc,), dtype=torch.int64, device=dev)
-            conv = torch.empty((T, 3, 3), dtype=torch.float32, device=dev)
-            conv_idx = torch.empty((Fc if T else 0,), dtype=torch.int64, device=dev)
-            nbr = torch.empty((Fc if T else 0,), dtype=torch.int64, device=dev)
-            rc = lib.p3d_clip_faces_emit(_C._ptr(face_verts), F, _C._ptr(mesh_first), N, _C._ptr(plan), plan.numel(), Fc,
-                                         T3, T4, float(z_clip), int(bool(persp)), _C._ptr(out_fv), _C._ptr(first_c),
-                                         _C._ptr(count_c), _C._ptr(c2u), _C._ptr(conv), _C._ptr(conv_idx), _C._ptr(nbr),
-                                         _C._stream(dev))
-            _lib.check(rc, "clip_faces")
+        out_fv = torch.empty((Fc, 3, 3), dtype=torch.float32, device=dev)
+        first_c = torch.empty((N,), dtype=torch.int64, device=dev)
+        count_c = torch.empty((N,), dtype=torch.int64, device=dev)
+        c2u = torch.empty((Fc,), dtype=torch.int64, device=dev)
+        conv = torch.empty((T, 3, 3), dtype=torch.float32, device=dev)
+        conv_idx = torch.empty((Fc if T else 0,), dtype=torch.int64, device=dev)
+        nbr = torch.empty((Fc if T else 0,), dtype=torch.int64, device=dev)
+        _lib.call("p3d_clip_faces_emit", "clip_faces", dev, face_verts, F, mesh_first, N, plan, plan.numel(), Fc, T3, T4, float(z_clip),
+                  int(bool(persp)), out_fv, first_c, count_c, c2u, conv, conv_idx, nbr)
         ctx.save_for_backward(face_verts, plan)
         ctx.meta = (F, T3, T4, float(z_clip), int(bool(persp)))
         ctx.out_shape = (Fc, 3, 3)
@@ -88,16 +82,13 @@ class _ClipEmit(torch.autograd.Function):
         dev = face_verts.device
         if g_fv is None and g_conv is None:
             return (None,) * 6
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            if g_fv is None:  # only the conversion matrices fed the loss
-                g_fv = torch.zeros(ctx.out_shape, dtype=torch.float32, device=dev)
-            g_fv = g_fv.contiguous()
-            g_conv_c = g_conv.contiguous() if g_conv is not None and g_conv.numel() else None
-            out = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
-            rc = lib.p3d_clip_faces_backward(_C._ptr(face_verts), F, _C._ptr(plan), plan.numel(), T3, T4, z_clip, persp,
-                                             _C._ptr(g_fv), _C._ptr(g_conv_c), _C._ptr(out), _C._stream(dev))
-            _lib.check(rc, "clip_faces_backward")
+        if g_fv is None:  # only the conversion matrices fed the loss
+            g_fv = torch.zeros(ctx.out_shape, dtype=torch.float32, device=dev)
+        g_fv = g_fv.contiguous()
+        g_conv_c = g_conv.contiguous() if g_conv is not None and g_conv.numel() else None
+        out = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+        _lib.call("p3d_clip_faces_backward", "clip_faces_backward", dev, face_verts, F, plan, plan.numel(), T3, T4, z_clip, persp, g_fv,
+                  g_conv_c, out)
         return out, None, None, None, None, None
 
 
@@ -112,15 +103,13 @@ def clip_faces(face_verts_unclipped: torch.Tensor, mesh_to_face_first_idx: torch
     F = fv.shape[0]
     vals = [frustum.left, frustum.right, frustum.top, frustum.bottom, frustum.znear, frustum.zfar]
     mask = sum(1 << i for i, v in enumerate(vals) if v is not None)
-    planes = (ctypes.c_float * 6)(*[0.0 if v is None else float(v) for v in vals])
+    planes = [0.0 if v is None else float(v) for v in vals]
     has_z = frustum.z_clip_value is not None
     z_clip = float(frustum.z_clip_value) if has_z else 0.0
     lib = _lib.load()
     with torch.cuda.device(dev):
         plan = torch.empty((int(lib.p3d_clip_faces_plan_bytes(F)),), dtype=torch.uint8, device=dev)
-        rc = lib.p3d_clip_faces_plan(_C._ptr(fv), F, planes, mask, int(bool(frustum.cull)), int(has_z), z_clip,
-                                     _C._ptr(plan), plan.numel(), _C._stream(dev))
-        _lib.check(rc, "clip_faces")
+        _lib.call("p3d_clip_faces_plan", "clip_faces", dev, fv, F, planes, mask, int(bool(frustum.cull)), int(has_z), z_clip, plan, plan.numel())
         Fc, T3, T4, _ = (int(x) for x in plan[:32].view(torch.int64).tolist())  # the one host sync
     if Fc == F and T3 == 0 and T4 == 0:
         # nothing culled, nothing clipped (clip.py:381-388)
@@ -145,15 +134,10 @@ class _ConvertClipped(torch.autograd.Function):
         bary = bary_clipped.contiguous()
         S = p2f.numel()
         has_conv = conv is not None and conv.numel() > 0
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            p2f_u = torch.empty_like(p2f)
-            bary_u = torch.empty_like(bary)
-            rc = lib.p3d_convert_clipped_forward(_C._ptr(p2f), _C._ptr(bary), _C._ptr(c2u),
-                                                 _C._ptr(conv if has_conv else None),
-                                                 _C._ptr(conv_idx if has_conv else None), S, _C._ptr(p2f_u),
-                                                 _C._ptr(bary_u), _C._stream(dev))
-            _lib.check(rc, "convert_clipped_rasterization_to_original_faces")
+        p2f_u = torch.empty_like(p2f)
+        bary_u = torch.empty_like(bary)
+        _lib.call("p3d_convert_clipped_forward", "convert_clipped_rasterization_to_original_faces", dev, p2f, bary, c2u,
+                  conv if has_conv else None, conv_idx if has_conv else None, S, p2f_u, bary_u)
         ctx.save_for_backward(p2f, bary, conv if has_conv else torch.empty(0, device=dev),
                               conv_idx if has_conv else torch.empty(0, dtype=torch.int64, device=dev))
         ctx.has_conv = has_conv
@@ -169,15 +153,11 @@ class _ConvertClipped(torch.autograd.Function):
         dev = bary.device
         S = p2f.numel()
         g = g_bary_u.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            g_bary = torch.empty_like(bary)
-            T = conv.shape[0] if ctx.has_conv else 0
-            g_conv = torch.empty((T, 3, 3), dtype=torch.float32, device=dev) if ctx.has_conv else None
-            rc = lib.p3d_convert_clipped_backward(_C._ptr(p2f), _C._ptr(bary), _C._ptr(conv if ctx.has_conv else None),
-                                                  _C._ptr(conv_idx if ctx.has_conv else None), _C._ptr(g), S, T,
-                                                  _C._ptr(g_bary), _C._ptr(g_conv), _C._stream(dev))
-            _lib.check(rc, "convert_clipped_rasterization_to_original_faces (backward)")
+        g_bary = torch.empty_like(bary)
+        T = conv.shape[0] if ctx.has_conv else 0
+        g_conv = torch.empty((T, 3, 3), dtype=torch.float32, device=dev) if ctx.has_conv else None
+        _lib.call("p3d_convert_clipped_backward", "convert_clipped_rasterization_to_original_faces (backward)", dev, p2f, bary,
+                  conv if ctx.has_conv else None, conv_idx if ctx.has_conv else None, g, S, T, g_bary, g_conv)
         return g_bary, g_conv, None, None, None
 
 

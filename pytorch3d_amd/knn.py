@@ -124,19 +124,14 @@ def backward_kernels(p1, p2, lengths1, lengths2, idx, K, norm, grad_dists, cloud
     P2 = p2.shape[1]
     flags = _lib.KNN_ACCUMULATE_P2 if accumulate_p2 else 0
     ordered = grad_p2 is not None and _C._ordered()
-    with torch.cuda.device(dev):
-        rc = lib.p3d_knn_points_backward(_C._ptr(p1), _C._ptr(p2), _C._ptr(lengths1), _C._ptr(lengths2), _C._ptr(idx), _C._ptr(grad_dists),
-                                         _C._ptr(cloud_scale), N, P1, P2, D, K, norm, flags, _C._ptr(grad_p1),
-                                         _C._ptr(None if ordered else grad_p2), _C._stream(dev))
-        _lib.check(rc, "knn_points backward")
-        if ordered:
-            hits = _sorted_hits(idx.reshape(N, P1, K), lengths1, lengths2, P2)
-            nbytes = lib.p3d_knn_points_ordered_backward_workspace_bytes(hits.numel())
-            ws = _C._workspace(nbytes, dev)
-            rc = lib.p3d_knn_points_ordered_backward(_C._ptr(p1), _C._ptr(p2), _C._ptr(lengths1), _C._ptr(lengths2), _C._ptr(idx),
-                                                     _C._ptr(grad_dists), _C._ptr(cloud_scale), _C._ptr(hits), hits.numel(), N, P1, P2, D, K,
-                                                     norm, flags, _C._ptr(grad_p2), _C._ptr(ws), nbytes, _C._stream(dev))
-            _lib.check(rc, "knn_points backward (ordered)")
+    _lib.call("p3d_knn_points_backward", "knn_points backward", dev, p1, p2, lengths1, lengths2, idx, grad_dists, cloud_scale, N, P1, P2, D, K,
+              norm, flags, grad_p1, None if ordered else grad_p2)
+    if ordered:
+        hits = _sorted_hits(idx.reshape(N, P1, K), lengths1, lengths2, P2)
+        nbytes = lib.p3d_knn_points_ordered_backward_workspace_bytes(hits.numel())
+        ws = _C._workspace(nbytes, dev)
+        _lib.call("p3d_knn_points_ordered_backward", "knn_points backward (ordered)", dev, p1, p2, lengths1, lengths2, idx, grad_dists,
+                  cloud_scale, hits, hits.numel(), N, P1, P2, D, K, norm, flags, grad_p2, ws, nbytes)
 
 
 class _KnnPoints(torch.autograd.Function):

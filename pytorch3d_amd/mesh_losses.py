@@ -222,13 +222,11 @@ class _EdgeLoss(torch.autograd.Function):
     def forward(ctx, verts, t, target_length):
         v = _C._c(verts, torch.float32)
         lib, dev = _lib.load(), v.device
-        with torch.cuda.device(dev):
-            nbytes = lib.p3d_mesh_edge_loss_forward_workspace_bytes(t.E)
-            ws = _C._workspace(nbytes, dev)
-            loss = torch.empty((1,), dtype=torch.float32, device=dev)
-            rc = lib.p3d_mesh_edge_loss_forward(_C._ptr(v), _C._ptr(t.edges), _C._ptr(t.edge_mesh), _C._ptr(t.num_edges), t.V, t.E, t.N,
-                                                float(target_length), _C._ptr(ws), nbytes, _C._ptr(loss), _C._stream(dev))
-            _lib.check(rc, "mesh_edge_loss forward")
+        nbytes = lib.p3d_mesh_edge_loss_forward_workspace_bytes(t.E)
+        ws = _C._workspace(nbytes, dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        _lib.call("p3d_mesh_edge_loss_forward", "mesh_edge_loss forward", dev, v, t.edges, t.edge_mesh, t.num_edges, t.V, t.E, t.N,
+                  float(target_length), ws, nbytes, loss)
         ctx.save_for_backward(v)
         ctx.topology, ctx.target_length = t, float(target_length)
         return loss.reshape(())
@@ -237,13 +235,11 @@ class _EdgeLoss(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
         (v,), t = ctx.saved_tensors, ctx.topology
-        lib, dev = _lib.load(), v.device
-        with torch.cuda.device(dev):
-            g = _grad_scalar(grad_loss, dev)
-            out = torch.empty_like(v)
-            rc = lib.p3d_mesh_edge_loss_backward(_C._ptr(g), _C._ptr(v), _C._ptr(t.adj_offsets), _C._ptr(t.adj), _C._ptr(t.vert_mesh),
-                                                 _C._ptr(t.num_edges), t.V, t.E, t.N, ctx.target_length, _C._ptr(out), _C._stream(dev))
-            _lib.check(rc, "mesh_edge_loss backward")
+        dev = v.device
+        g = _grad_scalar(grad_loss, dev)
+        out = torch.empty_like(v)
+        _lib.call("p3d_mesh_edge_loss_backward", "mesh_edge_loss backward", dev, g, v, t.adj_offsets, t.adj, t.vert_mesh, t.num_edges, t.V, t.E,
+                  t.N, ctx.target_length, out)
         return out, None, None
 
 
@@ -252,14 +248,12 @@ class _Laplacian(torch.autograd.Function):
     def forward(ctx, verts, t):
         v = _C._c(verts, torch.float32)
         lib, dev = _lib.load(), v.device
-        with torch.cuda.device(dev):
-            nbytes = lib.p3d_mesh_laplacian_forward_workspace_bytes(t.V)
-            ws = _C._workspace(nbytes, dev)
-            q = torch.empty_like(v)
-            loss = torch.empty((1,), dtype=torch.float32, device=dev)
-            rc = lib.p3d_mesh_laplacian_forward(_C._ptr(v), _C._ptr(t.adj_offsets), _C._ptr(t.adj), _C._ptr(t.vert_mesh), _C._ptr(t.num_verts),
-                                                t.V, t.E, t.N, _C._ptr(q), _C._ptr(ws), nbytes, _C._ptr(loss), _C._stream(dev))
-            _lib.check(rc, "mesh_laplacian_smoothing forward")
+        nbytes = lib.p3d_mesh_laplacian_forward_workspace_bytes(t.V)
+        ws = _C._workspace(nbytes, dev)
+        q = torch.empty_like(v)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        _lib.call("p3d_mesh_laplacian_forward", "mesh_laplacian_smoothing forward", dev, v, t.adj_offsets, t.adj, t.vert_mesh, t.num_verts, t.V,
+                  t.E, t.N, q, ws, nbytes, loss)
         ctx.save_for_backward(q)
         ctx.topology = t
         return loss.reshape(())
@@ -268,13 +262,10 @@ class _Laplacian(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_loss):
         (q,), t = ctx.saved_tensors, ctx.topology
-        lib, dev = _lib.load(), q.device
-        with torch.cuda.device(dev):
-            g = _grad_scalar(grad_loss, dev)
-            out = torch.empty_like(q)
-            rc = lib.p3d_mesh_laplacian_backward(_C._ptr(g), _C._ptr(q), _C._ptr(t.adj_offsets), _C._ptr(t.adj), t.V, t.E, t.N, _C._ptr(out),
-                                                 _C._stream(dev))
-            _lib.check(rc, "mesh_laplacian_smoothing backward")
+        dev = q.device
+        g = _grad_scalar(grad_loss, dev)
+        out = torch.empty_like(q)
+        _lib.call("p3d_mesh_laplacian_backward", "mesh_laplacian_smoothing backward", dev, g, q, t.adj_offsets, t.adj, t.V, t.E, t.N, out)
         return out, None
 
 
@@ -283,13 +274,11 @@ class _NormalConsistency(torch.autograd.Function):
     def forward(ctx, verts, t):
         v = _C._c(verts, torch.float32)
         lib, dev = _lib.load(), v.device
-        with torch.cuda.device(dev):
-            nbytes = lib.p3d_mesh_normal_consistency_forward_workspace_bytes(t.P)
-            ws = _C._workspace(nbytes, dev)
-            loss = torch.empty((1,), dtype=torch.float32, device=dev)
-            rc = lib.p3d_mesh_normal_consistency_forward(_C._ptr(v), _C._ptr(t.pairs), _C._ptr(t.pair_mesh), _C._ptr(t.num_pairs), t.V, t.P,
-                                                         t.N, _C._ptr(ws), nbytes, _C._ptr(loss), _C._stream(dev))
-            _lib.check(rc, "mesh_normal_consistency forward")
+        nbytes = lib.p3d_mesh_normal_consistency_forward_workspace_bytes(t.P)
+        ws = _C._workspace(nbytes, dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        _lib.call("p3d_mesh_normal_consistency_forward", "mesh_normal_consistency forward", dev, v, t.pairs, t.pair_mesh, t.num_pairs, t.V, t.P,
+                  t.N, ws, nbytes, loss)
         ctx.save_for_backward(v)
         ctx.topology = t
         return loss.reshape(())
@@ -299,15 +288,12 @@ class _NormalConsistency(torch.autograd.Function):
     def backward(ctx, grad_loss):
         (v,), t = ctx.saved_tensors, ctx.topology
         lib, dev = _lib.load(), v.device
-        with torch.cuda.device(dev):
-            g = _grad_scalar(grad_loss, dev)
-            nbytes = lib.p3d_mesh_normal_consistency_backward_workspace_bytes(t.P)
-            rows = _C._workspace(nbytes, dev)
-            out = torch.empty_like(v)
-            rc = lib.p3d_mesh_normal_consistency_backward(_C._ptr(g), _C._ptr(v), _C._ptr(t.pairs), _C._ptr(t.pair_mesh), _C._ptr(t.num_pairs),
-                                                          _C._ptr(t.pair_offsets), _C._ptr(t.pair_slots), t.V, t.P, t.N, _C._ptr(rows), nbytes,
-                                                          _C._ptr(out), _C._stream(dev))
-            _lib.check(rc, "mesh_normal_consistency backward")
+        g = _grad_scalar(grad_loss, dev)
+        nbytes = lib.p3d_mesh_normal_consistency_backward_workspace_bytes(t.P)
+        rows = _C._workspace(nbytes, dev)
+        out = torch.empty_like(v)
+        _lib.call("p3d_mesh_normal_consistency_backward", "mesh_normal_consistency backward", dev, g, v, t.pairs, t.pair_mesh, t.num_pairs,
+                  t.pair_offsets, t.pair_slots, t.V, t.P, t.N, rows, nbytes, out)
         return out, None
 
 

@@ -34,11 +34,9 @@ def face_areas_normals_forward(verts, faces):
     v, f = _check(verts, faces, "face_areas_normals_forward")
     V, F = v.size(0), f.size(0)
     dev = v.device
-    with torch.cuda.device(dev):
-        areas = torch.empty((F,), dtype=torch.float32, device=dev)
-        normals = torch.empty((F, 3), dtype=torch.float32, device=dev)
-        rc = _lib.load().p3d_face_areas_normals_forward(_C._ptr(v), _C._ptr(f), V, F, _C._ptr(areas), _C._ptr(normals), _C._stream(dev))
-        _lib.check(rc, "face_areas_normals_forward")
+    areas = torch.empty((F,), dtype=torch.float32, device=dev)
+    normals = torch.empty((F, 3), dtype=torch.float32, device=dev)
+    _lib.call("p3d_face_areas_normals_forward", "face_areas_normals_forward", dev, v, f, V, F, areas, normals)
     return areas, normals
 
 
@@ -52,11 +50,8 @@ def face_areas_normals_backward(grad_areas, grad_normals, verts, faces):
     if tuple(ga.shape) != (F,) or tuple(gn.shape) != (F, 3):
         raise RuntimeError("face_areas_normals_backward: grad_areas must have shape (F,) and grad_normals (F, 3)")
     dev = v.device
-    with torch.cuda.device(dev):
-        per_corner = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
-        rc = _lib.load().p3d_face_areas_normals_backward(_C._ptr(ga), _C._ptr(gn), _C._ptr(v), _C._ptr(f), V, F, _C._ptr(per_corner),
-                                                         _C._stream(dev))
-        _lib.check(rc, "face_areas_normals_backward")
+    per_corner = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+    _lib.call("p3d_face_areas_normals_backward", "face_areas_normals_backward", dev, ga, gn, v, f, V, F, per_corner)
     return _C.scatter_face_grads(per_corner, f, V)
 
 
@@ -107,6 +102,14 @@ def _check_incidence(incidence, V, F, dev):
     return offsets, corners
 
 
+def _float_rows(ws):
+    """The float32 view of a contiguous workspace: the byte buffers of _C._workspace go where the header declares `float*`."""
+    if ws.dtype == torch.float32:
+        return ws
+    raw = ws.reshape(-1).view(torch.uint8)
+    return raw[:raw.numel() // 4 * 4].view(torch.float32)
+
+
 def verts_normals_forward(verts, faces, offsets, corners, face_raw=None):
     """(normals (V, 3), sums (V, 3)): sums are the un-normalised area-weighted sums the backward needs.  face_raw: the (F, 3) float32
     workspace, made here when None (every row is written before it is read)."""
@@ -115,16 +118,13 @@ def verts_normals_forward(verts, faces, offsets, corners, face_raw=None):
     dev = v.device
     offsets, corners = _check_incidence((offsets, corners), V, F, dev)
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        if face_raw is None:
-            face_raw = _C._workspace(lib.p3d_verts_normals_forward_workspace_bytes(F), dev)
-        elif face_raw.device != dev or not face_raw.is_contiguous() or face_raw.numel() * face_raw.element_size() < F * 12:
-            raise RuntimeError("verts_normals: face_raw must be a contiguous workspace of F * 3 floats on the device of verts")
-        sums = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        normals = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        rc = lib.p3d_verts_normals_forward(_C._ptr(v), _C._ptr(f), _C._ptr(offsets), _C._ptr(corners), V, F, _C._ptr(face_raw),
-                                           _C._ptr(sums), _C._ptr(normals), _C._stream(dev))
-        _lib.check(rc, "verts_normals_forward")
+    if face_raw is None:
+        face_raw = _C._workspace(lib.p3d_verts_normals_forward_workspace_bytes(F), dev)
+    elif face_raw.device != dev or not face_raw.is_contiguous() or face_raw.numel() * face_raw.element_size() < F * 12:
+        raise RuntimeError("verts_normals: face_raw must be a contiguous workspace of F * 3 floats on the device of verts")
+    sums = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    normals = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    _lib.call("p3d_verts_normals_forward", "verts_normals_forward", dev, v, f, offsets, corners, V, F, _float_rows(face_raw), sums, normals)
     return normals, sums
 
 
@@ -139,15 +139,12 @@ def verts_normals_backward(grad_normals, verts, faces, sums, offsets, corners, f
     if tuple(g.shape) != (V, 3) or tuple(s.shape) != (V, 3):
         raise RuntimeError("verts_normals_backward: grad_normals and sums must have shape (V, 3)")
     lib = _lib.load()
-    with torch.cuda.device(dev):
-        if face_rows is None:
-            face_rows = _C._workspace(lib.p3d_verts_normals_backward_workspace_bytes(F), dev)
-        elif face_rows.device != dev or not face_rows.is_contiguous() or face_rows.numel() * face_rows.element_size() < F * 36:
-            raise RuntimeError("verts_normals_backward: face_rows must be a contiguous workspace of F * 9 floats on the device of verts")
-        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
-        rc = lib.p3d_verts_normals_backward(_C._ptr(g), _C._ptr(v), _C._ptr(f), _C._ptr(s), _C._ptr(offsets), _C._ptr(corners), V, F,
-                                            _C._ptr(face_rows), _C._ptr(out), _C._stream(dev))
-        _lib.check(rc, "verts_normals_backward")
+    if face_rows is None:
+        face_rows = _C._workspace(lib.p3d_verts_normals_backward_workspace_bytes(F), dev)
+    elif face_rows.device != dev or not face_rows.is_contiguous() or face_rows.numel() * face_rows.element_size() < F * 36:
+        raise RuntimeError("verts_normals_backward: face_rows must be a contiguous workspace of F * 9 floats on the device of verts")
+    out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    _lib.call("p3d_verts_normals_backward", "verts_normals_backward", dev, g, v, f, s, offsets, corners, V, F, _float_rows(face_rows), out)
     return out
 
 

@@ -132,19 +132,13 @@ def gather_face_verts(verts_packed, faces_packed):
 class _GatherFaceVerts(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, faces):
-        import ctypes
-
         from . import _lib
 
-        lib = _lib.load()
         verts_c, faces_c = verts.contiguous(), faces.contiguous()
         V, F = verts_c.shape[0], faces_c.shape[0]
-        with torch.cuda.device(verts.device):
-            out = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
-            if F:
-                rc = lib.p3d_gather_face_verts(_C._ptr(verts_c), _C._ptr(faces_c), V, F, _C._ptr(out),
-                                               _C._stream(verts.device))
-                _lib.check(rc, "gather_face_verts")
+        out = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
+        if F:
+            _lib.call("p3d_gather_face_verts", "gather_face_verts", verts.device, verts_c, faces_c, V, F, out)
         ctx.save_for_backward(faces_c)
         ctx.V = V
         return out
@@ -199,29 +193,23 @@ class _RasterizeMeshVerts(torch.autograd.Function):
                 cull_backfaces):
         from . import _lib
 
-        lib = _lib.load()
         verts_c, faces_c = verts.contiguous(), faces.contiguous()
         V, F = verts_c.shape[0], faces_c.shape[0]
-        with torch.cuda.device(verts.device):
-            face_verts = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
-            # per-face reciprocals for the backward (include/p3d_amd.h: p3d_gather_face_verts_pre), written by the gather
-            face_pre = torch.empty((F, 4), dtype=torch.float32, device=verts.device) if (_C.FACE_PRE and ctx.needs_input_grad[0]) else None
-            K, (H, W) = int(faces_per_pixel), image_size
-            fused = (_C.FUSED_GATHER and F > 0 and mesh_to_face_first_idx.shape[0] * H * W * K > 0 and verts_c.dtype == torch.float32
-                     and faces_c.dtype == torch.int64)
-            zeroed = None
-            if fused:
-                # (not under use_deterministic_algorithms: that backward needs no zeros)
-                if _C.PRECLEARED_GRAD and ctx.needs_input_grad[0] and not _C._ordered():
-                    zeroed = torch.empty((V, 3), dtype=torch.float32, device=verts.device)
-            elif F and face_pre is not None:
-                rc = lib.p3d_gather_face_verts_pre(_C._ptr(verts_c), _C._ptr(faces_c), V, F, _C._ptr(face_verts), _C._ptr(face_pre),
-                                                   _C._stream(verts.device))
-                _lib.check(rc, "gather_face_verts_pre")
-            elif F:
-                rc = lib.p3d_gather_face_verts(_C._ptr(verts_c), _C._ptr(faces_c), V, F, _C._ptr(face_verts),
-                                               _C._stream(verts.device))
-                _lib.check(rc, "gather_face_verts")
+        face_verts = torch.empty((F, 3, 3), dtype=torch.float32, device=verts.device)
+        # per-face reciprocals for the backward (include/p3d_amd.h: p3d_gather_face_verts_pre), written by the gather
+        face_pre = torch.empty((F, 4), dtype=torch.float32, device=verts.device) if (_C.FACE_PRE and ctx.needs_input_grad[0]) else None
+        K, (H, W) = int(faces_per_pixel), image_size
+        fused = (_C.FUSED_GATHER and F > 0 and mesh_to_face_first_idx.shape[0] * H * W * K > 0 and verts_c.dtype == torch.float32
+                 and faces_c.dtype == torch.int64)
+        zeroed = None
+        if fused:
+            # (not under use_deterministic_algorithms: that backward needs no zeros)
+            if _C.PRECLEARED_GRAD and ctx.needs_input_grad[0] and not _C._ordered():
+                zeroed = torch.empty((V, 3), dtype=torch.float32, device=verts.device)
+        elif F and face_pre is not None:
+            _lib.call("p3d_gather_face_verts_pre", "gather_face_verts_pre", verts.device, verts_c, faces_c, V, F, face_verts, face_pre)
+        elif F:
+            _lib.call("p3d_gather_face_verts", "gather_face_verts", verts.device, verts_c, faces_c, V, F, face_verts)
         (pix_to_face, zbuf, barycentric_coords, dists), cover = _C._rasterize_meshes_covered(
             face_verts, mesh_to_face_first_idx, num_faces_per_mesh, clipped_faces_neighbor_idx, image_size, blur_radius,
             faces_per_pixel, bin_size, max_faces_per_bin, perspective_correct, clip_barycentric_coords, cull_backfaces,
@@ -325,15 +313,12 @@ class _TransformVerts(torch.autograd.Function):
     def forward(ctx, verts, vert_first, mats):
         from . import _lib
 
-        lib = _lib.load()
         v = verts.contiguous()
         dev = v.device
-        with torch.cuda.device(dev):
-            out = torch.empty_like(v)
-            if v.shape[0]:
-                rc = lib.p3d_transform_verts_forward(_C._ptr(v), _C._ptr(vert_first), _C._ptr(mats), v.shape[0], vert_first.shape[0],
-                                                     mats.shape[0], _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "transform_verts_forward")
+        out = torch.empty_like(v)
+        if v.shape[0]:
+            _lib.call("p3d_transform_verts_forward", "transform_verts_forward", dev, v, vert_first, mats, v.shape[0], vert_first.shape[0],
+                      mats.shape[0], out)
         ctx.save_for_backward(v, vert_first, mats)
         return out
 
@@ -360,21 +345,17 @@ def _transform_backward(verts, vert_first, mats, g_ndc, want_verts, want_mats):
     lib = _lib.load()
     dev = verts.device
     V, N, num = verts.shape[0], vert_first.shape[0], mats.shape[0]
-    with torch.cuda.device(dev):
-        if not want_mats:
-            out = torch.empty((V, 3), dtype=torch.float32, device=dev)
-            if V:
-                rc = lib.p3d_transform_verts_backward(_C._ptr(verts), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g_ndc), V, N, num,
-                                                      _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "transform_verts_backward")
-            return out, None
-        out = torch.empty((V, 3), dtype=torch.float32, device=dev) if want_verts else None
-        g_mats = torch.empty((num, 2, 4, 4), dtype=torch.float32, device=dev)
-        nbytes = lib.p3d_transform_backward_workspace_bytes(V, N, num)
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        rc = lib.p3d_transform_backward_cameras(_C._ptr(verts), _C._ptr(vert_first), _C._ptr(mats), _C._ptr(g_ndc), V, N, num,
-                                                _C._ptr(out), _C._ptr(g_mats), _C._ptr(ws), nbytes, _C._stream(dev))
-        _lib.check(rc, "transform_backward_cameras")
+    if not want_mats:
+        out = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        if V:
+            _lib.call("p3d_transform_verts_backward", "transform_verts_backward", dev, verts, vert_first, mats, g_ndc, V, N, num, out)
+        return out, None
+    out = torch.empty((V, 3), dtype=torch.float32, device=dev) if want_verts else None
+    g_mats = torch.empty((num, 2, 4, 4), dtype=torch.float32, device=dev)
+    nbytes = lib.p3d_transform_backward_workspace_bytes(V, N, num)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _lib.call("p3d_transform_backward_cameras", "transform_backward_cameras", dev, verts, vert_first, mats, g_ndc, V, N, num, out, g_mats, ws,
+              nbytes)
     return out, g_mats
 
 
@@ -422,16 +403,13 @@ class _RasterizeMeshWorld(torch.autograd.Function):
         from . import _lib
 
         im_size, blur, K, bin_size, cap, persp, clip, cull = static
-        lib = _lib.load()
         verts_c, faces_c = verts.contiguous(), faces.contiguous()
         V, F, N = verts_c.shape[0], faces_c.shape[0], face_first.shape[0]
         dev = verts.device
-        with torch.cuda.device(dev):
-            face_verts = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
-            if F:
-                rc = lib.p3d_transform_gather_face_verts(_C._ptr(verts_c), _C._ptr(faces_c), _C._ptr(face_first), _C._ptr(mats), V, F,
-                                                         N, mats.shape[0], _C._ptr(face_verts), _C._stream(dev))
-                _lib.check(rc, "transform_gather_face_verts")
+        face_verts = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+        if F:
+            _lib.call("p3d_transform_gather_face_verts", "transform_gather_face_verts", dev, verts_c, faces_c, face_first, mats, V, F, N,
+                      mats.shape[0], face_verts)
         out, cover = _C._rasterize_meshes_covered(face_verts, face_first, num_faces, nbr, im_size, blur, K, bin_size, cap, persp, clip,
                                                   cull)
         ctx.save_for_backward(verts_c, faces_c, vert_first, mats, face_verts, out[0], cover)

@@ -136,49 +136,43 @@ def _forward(verts, faces, first, nf, uniforms, S, return_normals, table_out=Non
     V, F, N = verts.shape[0], faces.shape[0], first.numel()
     if F > 2 ** 31 - 1:
         raise RuntimeError("sample_points: F must fit an int32")
-    with torch.cuda.device(dev):
-        if out is not None:  # tests: outputs that hold poison, to show that every entry is written
-            samples, normals, idx, bary = out
-            for t, shape, dt in ((samples, (N, S, 3), torch.float32), (normals, (N, S, 3), torch.float32), (idx, (N, S), torch.int64),
-                                 (bary, (N, S, 3), torch.float32)):
-                if t is not None and (tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous()):
-                    raise RuntimeError("sample_points: _out must hold contiguous (samples, normals, sample_face_idxs, bary) of the call's shapes")
-            normals = normals if return_normals else None
-        else:
-            samples = torch.empty((N, S, 3), dtype=torch.float32, device=dev)
-            normals = torch.empty((N, S, 3), dtype=torch.float32, device=dev) if return_normals else None
-            idx = torch.empty((N, S), dtype=torch.int64, device=dev)
-            bary = torch.empty((N, S, 3), dtype=torch.float32, device=dev)
-        nbytes = lib.p3d_sample_points_forward_workspace_bytes(F)
-        ws = _C._workspace(nbytes, dev)
-        rc = lib.p3d_sample_points_forward(_C._ptr(verts), _C._ptr(faces), _C._ptr(first), _C._ptr(nf), _C._ptr(uniforms), V, F, N, S,
-                                           _C._ptr(samples), _C._ptr(normals), _C._ptr(idx), _C._ptr(bary), _C._ptr(ws), nbytes,
-                                           _C._stream(dev))
-        _lib.check(rc, "sample_points_from_meshes forward")
-        if table_out is not None:  # tests: the table is the workspace's first F floats
-            table_out.append(ws[:F * 4].view(torch.float32).clone())
+    if out is not None:  # tests: outputs that hold poison, to show that every entry is written
+        samples, normals, idx, bary = out
+        for t, shape, dt in ((samples, (N, S, 3), torch.float32), (normals, (N, S, 3), torch.float32), (idx, (N, S), torch.int64),
+                             (bary, (N, S, 3), torch.float32)):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dt or t.device != dev or not t.is_contiguous()):
+                raise RuntimeError("sample_points: _out must hold contiguous (samples, normals, sample_face_idxs, bary) of the call's shapes")
+        normals = normals if return_normals else None
+    else:
+        samples = torch.empty((N, S, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((N, S, 3), dtype=torch.float32, device=dev) if return_normals else None
+        idx = torch.empty((N, S), dtype=torch.int64, device=dev)
+        bary = torch.empty((N, S, 3), dtype=torch.float32, device=dev)
+    nbytes = lib.p3d_sample_points_forward_workspace_bytes(F)
+    ws = _C._workspace(nbytes, dev)
+    _lib.call("p3d_sample_points_forward", "sample_points_from_meshes forward", dev, verts, faces, first, nf, uniforms, V, F, N, S, samples,
+              normals, idx, bary, ws, nbytes)
+    if table_out is not None:  # tests: the table is the workspace's first F floats
+        table_out.append(ws[:F * 4].view(torch.float32).clone())
     return samples, normals, idx, bary
 
 
 def _backward(grad_samples, grad_normals, verts, faces, idx, bary):
     lib, dev = _lib.load(), verts.device
     V, F, NS = verts.shape[0], faces.shape[0], idx.numel()
-    with torch.cuda.device(dev):
-        if F == 0 or V == 0:
-            return torch.zeros_like(verts)
-        gs = torch.zeros_like(bary) if grad_samples is None else _C._c(grad_samples, torch.float32)
-        gn = None if grad_normals is None else _C._c(grad_normals, torch.float32)
-        sorted_samples = _C._sorted_hits(idx) if _C._ordered() else None
-        num_sorted = 0 if sorted_samples is None else sorted_samples.numel()
-        if sorted_samples is not None and num_sorted == 0:  # (a NULL pointer would select the atomic path)
-            return torch.zeros_like(verts)
-        nbytes = lib.p3d_sample_points_backward_workspace_bytes(F, 0 if gn is None else 1, num_sorted)
-        ws = _C._workspace(nbytes, dev)
-        per_corner = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
-        rc = lib.p3d_sample_points_backward(_C._ptr(gs), _C._ptr(gn), _C._ptr(verts), _C._ptr(faces), _C._ptr(idx), _C._ptr(bary),
-                                            _C._ptr(sorted_samples), num_sorted, V, F, NS, _C._ptr(per_corner), _C._ptr(ws), nbytes,
-                                            _C._stream(dev))
-        _lib.check(rc, "sample_points_from_meshes backward")
+    if F == 0 or V == 0:
+        return torch.zeros_like(verts)
+    gs = torch.zeros_like(bary) if grad_samples is None else _C._c(grad_samples, torch.float32)
+    gn = None if grad_normals is None else _C._c(grad_normals, torch.float32)
+    sorted_samples = _C._sorted_hits(idx) if _C._ordered() else None
+    num_sorted = 0 if sorted_samples is None else sorted_samples.numel()
+    if sorted_samples is not None and num_sorted == 0:  # (a NULL pointer would select the atomic path)
+        return torch.zeros_like(verts)
+    nbytes = lib.p3d_sample_points_backward_workspace_bytes(F, 0 if gn is None else 1, num_sorted)
+    ws = _C._workspace(nbytes, dev)
+    per_corner = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+    _lib.call("p3d_sample_points_backward", "sample_points_from_meshes backward", dev, gs, gn, verts, faces, idx, bary, sorted_samples,
+              num_sorted, V, F, NS, per_corner, ws, nbytes)
     return _C.scatter_face_grads(per_corner, faces, V)
 
 

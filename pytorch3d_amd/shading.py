@@ -99,13 +99,9 @@ class _PhongShade(torch.autograd.Function):
         tx = texels.contiguous() if texels is not None else None
         params = params.contiguous()
         F, _, D = fa.shape
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            colors = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            if colors.numel():
-                rc = lib.p3d_phong_shade_forward(_C._ptr(p2f), _C._ptr(b), _C._ptr(fa), D, _C._ptr(tx), _C._ptr(params),
-                                                 kind, N, H, W, K, F, _C._ptr(colors), _C._stream(dev))
-                _lib.check(rc, "phong_shading")
+        colors = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        if colors.numel():
+            _lib.call("p3d_phong_shade_forward", "phong_shading", dev, p2f, b, fa, D, tx, params, kind, N, H, W, K, F, colors)
         ctx.save_for_backward(p2f, b, fa, tx if tx is not None else torch.empty(0, device=dev), params)
         ctx.kind = kind
         ctx.has_texels = tx is not None
@@ -119,16 +115,12 @@ class _PhongShade(torch.autograd.Function):
         F, _, D = fa.shape
         dev = b.device
         g = grad_colors.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            gfa = torch.empty((F, 3, D), dtype=torch.float32, device=dev)
-            gt = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev) if ctx.has_texels else None
-            gp = torch.empty((N, PARAM_FLOATS), dtype=torch.float32, device=dev) if ctx.needs_input_grad[4] else None
-            rc = lib.p3d_phong_shade_backward(_C._ptr(g), _C._ptr(p2f), _C._ptr(b), _C._ptr(fa), D,
-                                              _C._ptr(tx if ctx.has_texels else None), _C._ptr(params), ctx.kind, N, H, W,
-                                              K, F, _C._ptr(gb), _C._ptr(gfa), _C._ptr(gt), _C._ptr(gp), _C._stream(dev))
-            _lib.check(rc, "phong_shading_backward")
+        gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        gfa = torch.empty((F, 3, D), dtype=torch.float32, device=dev)
+        gt = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev) if ctx.has_texels else None
+        gp = torch.empty((N, PARAM_FLOATS), dtype=torch.float32, device=dev) if ctx.needs_input_grad[4] else None
+        _lib.call("p3d_phong_shade_backward", "phong_shading_backward", dev, g, p2f, b, fa, D, tx if ctx.has_texels else None, params, ctx.kind,
+                  N, H, W, K, F, gb, gfa, gt, gp)
         return None, gb, gfa, gt, gp, None
 
 
@@ -242,14 +234,10 @@ class _SoftPhong(torch.autograd.Function):
         F, _, D = fa.shape
         zn, zn_t = _plane(znear, N, dev)
         zf, zf_t = _plane(zfar, N, dev)
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_soft_phong_forward(_C._ptr(p2f), _C._ptr(b), _C._ptr(d), _C._ptr(z), _C._ptr(fa), D, _C._ptr(tx),
-                                                _C._ptr(params), kind, float(sigma), float(gamma), bg, zn, zf, _C._ptr(zn_t),
-                                                _C._ptr(zf_t), N, H, W, K, F, _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "soft_phong_shading")
+        out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_soft_phong_forward", "soft_phong_shading", dev, p2f, b, d, z, fa, D, tx, params, kind, float(sigma), float(gamma), bg,
+                      zn, zf, zn_t, zf_t, N, H, W, K, F, out)
         empty = torch.empty(0, device=dev)
         ctx.save_for_backward(p2f, b, d, z, fa, tx if tx is not None else empty, params, zn_t if zn_t is not None else empty,
                               zf_t if zf_t is not None else empty)
@@ -265,20 +253,14 @@ class _SoftPhong(torch.autograd.Function):
         F, _, D = fa.shape
         dev = b.device
         g = grad_out.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
-            gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
-            gfa = torch.empty((F, 3, D), dtype=torch.float32, device=dev)
-            gt = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev) if has_tx else None
-            gp = torch.empty((N, PARAM_FLOATS), dtype=torch.float32, device=dev) if ctx.needs_input_grad[6] else None
-            rc = lib.p3d_soft_phong_backward(_C._ptr(g), _C._ptr(p2f), _C._ptr(b), _C._ptr(d), _C._ptr(z), _C._ptr(fa), D,
-                                             _C._ptr(tx if has_tx else None), _C._ptr(params), kind, sigma, gamma, bg, zn, zf,
-                                             _C._ptr(zn_t if has_zn else None), _C._ptr(zf_t if has_zf else None), N, H, W, K, F,
-                                             _C._ptr(gb), _C._ptr(gd), _C._ptr(gz), _C._ptr(gfa), _C._ptr(gt), _C._ptr(gp),
-                                             _C._stream(dev))
-            _lib.check(rc, "soft_phong_shading_backward")
+        gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+        gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
+        gfa = torch.empty((F, 3, D), dtype=torch.float32, device=dev)
+        gt = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev) if has_tx else None
+        gp = torch.empty((N, PARAM_FLOATS), dtype=torch.float32, device=dev) if ctx.needs_input_grad[6] else None
+        _lib.call("p3d_soft_phong_backward", "soft_phong_shading_backward", dev, g, p2f, b, d, z, fa, D, tx if has_tx else None, params, kind,
+                  sigma, gamma, bg, zn, zf, zn_t if has_zn else None, zf_t if has_zf else None, N, H, W, K, F, gb, gd, gz, gfa, gt, gp)
         return None, gb, gd, gz, gfa, gt, gp, None, None, None, None, None, None
 
 

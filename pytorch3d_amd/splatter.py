@@ -28,13 +28,9 @@ class _SplatterBlend(torch.autograd.Function):
         N, H, W, K, _ = colors.shape
         dev = colors.device
         c, x, m = colors.contiguous(), coords.contiguous(), mask.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_splatter_blend_forward(_C._ptr(c), _C._ptr(x), _C._ptr(m), sigma, bg, N, H, W, K, _C._ptr(out),
-                                                    _C._stream(dev))
-                _lib.check(rc, "splatter_blend")
+        out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_splatter_blend_forward", "splatter_blend", dev, c, x, m, sigma, bg, N, H, W, K, out)
         ctx.save_for_backward(c, x, m)
         ctx.meta = (sigma, bg)
         return out
@@ -47,15 +43,12 @@ class _SplatterBlend(torch.autograd.Function):
         dev = c.device
         g = grad_out.contiguous()
         lib = _lib.load()
-        with torch.cuda.device(dev):
-            gc = torch.empty_like(c)
-            gx = torch.empty_like(x)
-            if gc.numel():
-                nbytes = lib.p3d_splatter_blend_backward_workspace_bytes(N, H, W)
-                ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-                rc = lib.p3d_splatter_blend_backward(_C._ptr(g), _C._ptr(c), _C._ptr(x), _C._ptr(m), sigma, bg, N, H, W, K,
-                                                     _C._ptr(gc), _C._ptr(gx), _C._ptr(ws), nbytes, _C._stream(dev))
-                _lib.check(rc, "splatter_blend_backward")
+        gc = torch.empty_like(c)
+        gx = torch.empty_like(x)
+        if gc.numel():
+            nbytes = lib.p3d_splatter_blend_backward_workspace_bytes(N, H, W)
+            ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+            _lib.call("p3d_splatter_blend_backward", "splatter_blend_backward", dev, g, c, x, m, sigma, bg, N, H, W, K, gc, gx, ws, nbytes)
         return gc, gx, None, None, None
 
 

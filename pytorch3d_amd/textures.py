@@ -25,13 +25,9 @@ class _SampleUV(torch.autograd.Function):
         p2f, b, fu, mp = pix_to_face.contiguous(), bary.contiguous(), face_uvs.contiguous(), maps.contiguous()
         Nm, Hm, Wm, C = mp.shape
         F = fu.shape[0]
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, K, C), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_sample_uv_forward(_C._ptr(p2f), _C._ptr(b), _C._ptr(fu), _C._ptr(mp), N, H, W, K, F, Hm, Wm, C,
-                                               align, pad, mode, _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "sample_textures")
+        out = torch.empty((N, H, W, K, C), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_sample_uv_forward", "sample_textures", dev, p2f, b, fu, mp, N, H, W, K, F, Hm, Wm, C, align, pad, mode, out)
         ctx.save_for_backward(p2f, b, fu, mp)
         ctx.cfg = (align, pad, mode)
         return out
@@ -45,14 +41,11 @@ class _SampleUV(torch.autograd.Function):
         F = fu.shape[0]
         dev = b.device
         g = grad_texels.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            gfu = torch.empty((F, 3, 2), dtype=torch.float32, device=dev)
-            gm = torch.empty((Nm, Hm, Wm, C), dtype=torch.float32, device=dev)
-            rc = lib.p3d_sample_uv_backward(_C._ptr(g), _C._ptr(p2f), _C._ptr(b), _C._ptr(fu), _C._ptr(mp), N, H, W, K, F, Hm,
-                                            Wm, C, align, pad, mode, _C._ptr(gb), _C._ptr(gfu), _C._ptr(gm), _C._stream(dev))
-            _lib.check(rc, "sample_textures_backward")
+        gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        gfu = torch.empty((F, 3, 2), dtype=torch.float32, device=dev)
+        gm = torch.empty((Nm, Hm, Wm, C), dtype=torch.float32, device=dev)
+        _lib.call("p3d_sample_uv_backward", "sample_textures_backward", dev, g, p2f, b, fu, mp, N, H, W, K, F, Hm, Wm, C, align, pad, mode, gb,
+                  gfu, gm)
         return None, gb, gfu, gm, None, None, None
 
 
@@ -66,13 +59,10 @@ class _SampleUVMulti(torch.autograd.Function):
         p2f, b, fu, mp, idv = pix_to_face.contiguous(), bary.contiguous(), face_uvs.contiguous(), maps.contiguous(), ids.contiguous()
         _, M, Hm, Wm, C = mp.shape
         F, L = fu.shape[0], idv.numel()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty((N, H, W, K, C), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_sample_uv_multi_forward(_C._ptr(p2f), _C._ptr(b), _C._ptr(fu), _C._ptr(mp), _C._ptr(idv), L, N, H, W,
-                                                     K, F, M, Hm, Wm, C, align, pad, mode, _C._ptr(out), _C._stream(dev))
-                _lib.check(rc, "sample_textures (maps_ids)")
+        out = torch.empty((N, H, W, K, C), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_sample_uv_multi_forward", "sample_textures (maps_ids)", dev, p2f, b, fu, mp, idv, L, N, H, W, K, F, M, Hm, Wm, C,
+                      align, pad, mode, out)
         ctx.save_for_backward(p2f, b, fu, mp, idv)
         ctx.cfg = (align, pad, mode)
         return out
@@ -86,15 +76,11 @@ class _SampleUVMulti(torch.autograd.Function):
         F, L = fu.shape[0], idv.numel()
         dev = b.device
         g = grad_texels.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
-            gfu = torch.empty((F, 3, 2), dtype=torch.float32, device=dev)
-            gm = torch.empty_like(mp)
-            rc = lib.p3d_sample_uv_multi_backward(_C._ptr(g), _C._ptr(p2f), _C._ptr(b), _C._ptr(fu), _C._ptr(mp), _C._ptr(idv), L,
-                                                  N, H, W, K, F, M, Hm, Wm, C, align, pad, mode, _C._ptr(gb), _C._ptr(gfu),
-                                                  _C._ptr(gm), _C._stream(dev))
-            _lib.check(rc, "sample_textures_backward (maps_ids)")
+        gb = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
+        gfu = torch.empty((F, 3, 2), dtype=torch.float32, device=dev)
+        gm = torch.empty_like(mp)
+        _lib.call("p3d_sample_uv_multi_backward", "sample_textures_backward (maps_ids)", dev, g, p2f, b, fu, mp, idv, L, N, H, W, K, F, M, Hm,
+                  Wm, C, align, pad, mode, gb, gfu, gm)
         return None, gb, gfu, gm, None, None, None, None
 
 
@@ -158,13 +144,9 @@ class _SampleAtlas(torch.autograd.Function):
         dev = atlas.device
         p2f, b, at = pix_to_face.contiguous(), bary.contiguous(), atlas.contiguous()
         F, R, _, C = at.shape
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            out = torch.empty(tuple(p2f.shape) + (C,), dtype=torch.float32, device=dev)
-            if out.numel():
-                rc = lib.p3d_sample_atlas_forward(_C._ptr(p2f), _C._ptr(b), _C._ptr(at), p2f.numel(), F, R, C, _C._ptr(out),
-                                                  _C._stream(dev))
-                _lib.check(rc, "sample_textures_atlas")
+        out = torch.empty(tuple(p2f.shape) + (C,), dtype=torch.float32, device=dev)
+        if out.numel():
+            _lib.call("p3d_sample_atlas_forward", "sample_textures_atlas", dev, p2f, b, at, p2f.numel(), F, R, C, out)
         ctx.save_for_backward(p2f, b)
         ctx.atlas_shape = (F, R, C)
         return out
@@ -175,13 +157,9 @@ class _SampleAtlas(torch.autograd.Function):
         F, R, C = ctx.atlas_shape
         dev = b.device
         g = grad_texels.contiguous()
-        lib = _lib.load()
-        with torch.cuda.device(dev):
-            ga = torch.empty((F, R, R, C), dtype=torch.float32, device=dev)
-            if ga.numel():
-                rc = lib.p3d_sample_atlas_backward(_C._ptr(g), _C._ptr(p2f), _C._ptr(b), p2f.numel(), F, R, C, _C._ptr(ga),
-                                                   _C._stream(dev))
-                _lib.check(rc, "sample_textures_atlas_backward")
+        ga = torch.empty((F, R, R, C), dtype=torch.float32, device=dev)
+        if ga.numel():
+            _lib.call("p3d_sample_atlas_backward", "sample_textures_atlas_backward", dev, g, p2f, b, p2f.numel(), F, R, C, ga)
         return None, None, ga
 
 

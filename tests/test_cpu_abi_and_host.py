@@ -748,6 +748,137 @@ def test_header_parser_on_synthetic_text():
         _lib.parse_header("int p3d_twice(void); int p3d_twice(int n);")
 
 
+def test_a_marshaller_builds_for_every_declaration():
+    """_lib.marshaller: one converter per parameter without the stream; the status entries are the 91 that take a stream and the
+    host entry, and those are what load() binds for _lib.call."""
+    from pytorch3d_amd import _lib
+
+    assert len(_lib.DECLARATIONS) == 136
+    status, streamed = [], []
+    for name, (ret, params) in _lib.DECLARATIONS.items():
+        converters, stream, is_status = _lib.marshaller(name, ret, params)
+        assert len(converters) == len(params) - int(stream), name
+        assert all((c is None) == (p in _lib._SCALARS) for c, p in zip(converters, params)), name
+        status += [name] if is_status else []
+        streamed += [name] if stream else []
+    assert len(status) == 92 and len(streamed) == 91
+    assert sorted(set(status) - set(streamed)) == ["p3d_iou_box3d_host"] and set(streamed) <= set(status)
+    _lib.load()
+    assert sorted(_lib._CALLS) == sorted(status)
+    with pytest.raises(ValueError, match="p3d_stream_t"):  # anywhere but last
+        _lib.marshaller("p3d_x", "int", ["p3d_stream_t", "int"])
+    with pytest.raises(ValueError, match=re.escape("size_t*")):  # no torch dtype stands for it: never guessed
+        _lib.marshaller("p3d_x", "int", ["size_t*"])
+
+
+_CALL_HEADER = """
+typedef void* p3d_stream_t;
+int p3d_host(const float* a, float* out, const int64_t* idx, int32_t* small, const uint8_t* mask, void* ws, const int64_t strides[4],
+             int n, float x);
+int p3d_launch(const float* a, int n, p3d_stream_t stream);
+"""
+
+
+def _stand_in(entry, code=0):
+    """(invoke of _lib.bind over a Python callable that records what arrives, the list of recorded argument tuples)"""
+    from pytorch3d_amd import _lib
+
+    seen = []
+
+    def fn(*args):
+        seen.append(args)
+        return code
+
+    return _lib.bind(fn, entry, *_lib.parse_header(_CALL_HEADER)[0][entry]), seen
+
+
+def test_call_marshals_by_the_declaration():
+    invoke, seen = _stand_in("p3d_host")
+    t = torch.arange(15, dtype=torch.float32).reshape(3, 5)
+    idx, small = torch.zeros(2, dtype=torch.int64), torch.zeros(2, dtype=torch.int32)
+    invoke("where", None, t[:, 2:], None, torch.empty(0, dtype=torch.int64), small, None, idx, (20, 1, 5, 4), 7, 0.5)
+    (a, out, empty, sm, mask, ws, strides, n, x), = seen
+    assert a == t.data_ptr() + 8 and out is None and empty is None and sm == small.data_ptr() and mask is None and ws == idx.data_ptr()
+    assert isinstance(strides, ctypes.c_int64 * 4) and list(strides) == [20, 1, 5, 4]
+    assert (n, x) == (7, 0.5) and type(n) is int and type(x) is float
+    invoke("where", None, 4096, None, None, None, None, None, [0, 0, 0, 0], 0, 0.0)  # a plain int is an address
+    assert seen[1][0] == 4096
+    del seen[:]
+    with pytest.raises(ValueError, match=re.escape("p3d_host: argument 6 is declared `const int64_t[4]`; got 3 numbers")):
+        invoke("where", None, t, None, None, None, None, None, (1, 2, 3), 7, 0.5)
+    for args in ((t, None, None, None, None, None, (1, 2, 3, 4), 7), (t, None, None, None, None, None, (1, 2, 3, 4), 7, 0.5, 1)):
+        with pytest.raises(TypeError, match=re.escape("p3d_host takes 9 arguments (const float*, float*, const int64_t*, int32_t*, "
+                                                      "const uint8_t*, void*, const int64_t[4], int, float), got %d" % len(args))):
+            invoke("where", None, *args)
+    # the stream slot is not an argument: handing one over is one argument too many
+    launch, launched = _stand_in("p3d_launch")
+    with pytest.raises(TypeError, match=re.escape("p3d_launch takes 2 arguments (const float*, int), got 3")):
+        launch("where", None, t, 3, None)
+    assert seen == [] and launched == []
+    # a status other than P3D_OK goes through check(code, where)
+    failing, _ = _stand_in("p3d_host", code=-1)
+    with pytest.raises(RuntimeError, match=r"^where: .* \(p3d error -1\)$"):
+        failing("where", None, t, None, None, None, None, None, (1, 2, 3, 4), 7, 0.5)
+
+
+def test_call_rejects_a_tensor_of_another_dtype_or_device():
+    invoke, seen = _stand_in("p3d_host")
+    ok = [torch.zeros(2), torch.zeros(2), torch.zeros(2, dtype=torch.int64), torch.zeros(2, dtype=torch.int32),
+          torch.zeros(2, dtype=torch.uint8), torch.zeros(2, dtype=torch.uint8), (0, 0, 0, 0), 0, 0.0]
+    for pos, ctype, bad in ((0, "const float*", torch.float64), (2, "const int64_t*", torch.int32), (3, "int32_t*", torch.int64),
+                            (4, "const uint8_t*", torch.int8)):
+        args = list(ok)
+        args[pos] = torch.zeros(2, dtype=bad)
+        with pytest.raises(RuntimeError, match=re.escape(f"p3d_host: argument {pos} is declared `{ctype}`") + ".*" + re.escape(str(bad))):
+            invoke("where", None, *args)
+    assert seen == []
+    for pos, dtype in ((4, torch.bool), (5, torch.float64), (5, torch.int16), (5, torch.bool)):  # bool for uint8_t, anything for void
+        args = list(ok)
+        args[pos] = torch.zeros(2, dtype=dtype)
+        invoke("where", None, *args)
+        assert seen.pop()[pos] == args[pos].data_ptr()
+    meta = torch.zeros(2, device="meta")  # not the host's memory
+    with pytest.raises(RuntimeError, match=re.escape("p3d_host: argument 0 is declared `const float*` and the call is for the host") + ".*meta"):
+        invoke("where", None, meta, *ok[1:])
+    assert seen == []
+
+
+def test_call_on_the_host_entry_of_the_library():
+    import box3d_case
+    from pytorch3d_amd import _C, _lib
+
+    gen = torch.Generator().manual_seed(5)
+    b1, b2 = (box3d_case.random_boxes(2, gen).to(torch.float32) for _ in range(2))
+    want = _C.iou_box3d_host(b1, b2)
+    vol, iou = torch.full((2, 2), -7.0), torch.full((2, 2), -7.0)
+    _lib.call("p3d_iou_box3d_host", "iou_box3d_host", None, b1, b2, 2, 2, vol, iou)
+    assert torch.equal(vol, want[0]) and torch.equal(iou, want[1]) and bool((want[0] >= 0).all())
+    vol.fill_(-7.0), iou.fill_(-7.0)
+    with pytest.raises(RuntimeError, match=re.escape("p3d_iou_box3d_host: argument 0 is declared `const float*`") + ".*float64"):
+        _lib.call("p3d_iou_box3d_host", "iou_box3d_host", None, b1.double(), b2.double(), 2, 2, vol, iou)
+    assert bool((vol == -7.0).all()) and bool((iou == -7.0).all())  # the library was not entered
+
+
+def test_the_package_marshals_through_call_alone():
+    """No module of the package builds a pointer, a stream or a status check by hand: _lib.py does, and _C.py keeps _ptr, _stream and
+    cover_ptr for the raw calls of the tests and the profile scripts."""
+    import ast
+
+    pkg = os.path.join(U.ROOT, "pytorch3d_amd")
+    for f in sorted(os.listdir(pkg)):
+        if not f.endswith(".py") or f == "_lib.py":
+            continue
+        src = open(os.path.join(pkg, f)).read()
+        if f == "_C.py":
+            helpers = [ast.get_source_segment(src, n) for n in ast.parse(src).body
+                       if isinstance(n, ast.FunctionDef) and n.name in ("_ptr", "_stream", "cover_ptr")]
+            assert len(helpers) == 3
+            for text in helpers:
+                src = src.replace(text, "")
+        found = re.findall(r"(?<![A-Za-z0-9])_ptr\(|(?<![A-Za-z0-9])_stream\(|_lib\.check\(|c_void_p", src)  # (data_ptr() is not meant)
+        assert found == [], (f, found)
+
+
 def test_every_integer_macro_of_the_header_is_a_constant_of_lib():
     from pytorch3d_amd import _lib
 

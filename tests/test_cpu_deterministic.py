@@ -185,8 +185,10 @@ def test_host_switch(monkeypatch):
     rec = _Recorder()
     monkeypatch.setattr(_lib, "load", lambda: rec)
     monkeypatch.setattr(_C, "_need_gpu", lambda t, name: None)
-    monkeypatch.setattr(_C, "_stream", lambda device: None)
     monkeypatch.setattr(torch.cuda, "device", lambda device: contextlib.nullcontext())
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda device: types.SimpleNamespace(cuda_stream=0))
+    # _lib.call with the recorder behind the real marshallers: the CPU stand-ins still have to fit every entry's declaration
+    monkeypatch.setattr(_lib, "_CALLS", {n: _lib.bind(getattr(rec, n), n, *d) for n, d in _lib.DECLARATIONS.items() if _lib.marshaller(n, *d)[2]})
     for name, (call, atomic, ordered) in _host_calls().items():
         for tag, ctx, want in (("flag off", _mode(False), atomic), ("warn only", _mode(True, warn_only=True), atomic),
                                ("strict", _mode(True), ordered)):
