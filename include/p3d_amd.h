@@ -511,9 +511,17 @@ int p3d_convert_clipped_backward(const int64_t* pix_to_face_clipped, const float
 
 /* ---- fragment blending (the step right after rasterization) --------------------------- */
 
+/* Alignment, for every entry of this section and the depth entries below: the kernels move a pixel's K-row with 16-byte
+ * accesses when the row is a multiple of 16 bytes, so the base of such a row must be 16-byte aligned -- pix_to_face (i64) when
+ * K % 2 == 0; dists, zbuf, grad_dists, grad_zbuf (f32) and colors, grad_colors (3 f32 per slot) when K % 4 == 0.  The RGBA
+ * images out / grad_out of the softmax entries and out of the hard entry are moved as one float4 per pixel: 16-byte aligned
+ * for every K.  A base that is not: P3D_ERR_INVALID_ARG, nothing is launched.  (A contiguous torch view at a storage
+ * offset is such a base; the Python wrappers copy it first.)  Negative npix / N / pix_per_image / K and a missing pointer
+ * are P3D_ERR_INVALID_ARG as well; npix == 0 is P3D_OK without a launch. */
+
 /* replaces SigmoidAlphaBlend / SigmoidAlphaBlendBackward, pytorch3d/csrc/blending/sigmoid_alpha_blend.h:73-103
  * (_C.sigmoid_alpha_blend[_backward]).  dists, pix_to_face (npix,K); alphas, grad_alphas (npix); grad_dists
- * (npix,K) fully written.  npix = N*H*W. */
+ * (npix,K) fully written.  npix = N*H*W.  K == 0: the forward writes alphas = 0, the backward is P3D_OK without a launch. */
 int p3d_sigmoid_alpha_blend_forward(const float* dists, const int64_t* pix_to_face, float sigma, int64_t npix, int K,
                                     float* alphas, p3d_stream_t stream);
 int p3d_sigmoid_alpha_blend_backward(const float* grad_alphas, const float* alphas, const float* dists,

@@ -72,6 +72,14 @@ def _c(t, dtype):
     return t.contiguous()
 
 
+def _aligned(t):
+    """`t` contiguous with its first element on a 16-byte boundary, as the blend entries want their rows (include/p3d_amd.h,
+    "Alignment"): `t` itself when it already is, else a copy.  A contiguous view at a storage offset -- buf[1:1 + n].view(N, H, W, K)
+    -- is the case .contiguous() leaves where it is; fresh allocations are aligned."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _hw(image_size):
     h, w = image_size
     return int(h), int(w)
@@ -951,7 +959,7 @@ def sigmoid_alpha_blend(distances, pix_to_face, sigma):
     dev = _same_device(("distances", distances), ("pix_to_face", pix_to_face))
     if distances.dim() != 4 or pix_to_face.shape != distances.shape:
         raise RuntimeError("distances and pix_to_face must both have shape (N, H, W, K)")
-    d, p2f = _c(distances, torch.float32), _c(pix_to_face, torch.int64)
+    d, p2f = _aligned(_c(distances, torch.float32)), _aligned(_c(pix_to_face, torch.int64))
     N, H, W, K = d.shape
     out = torch.empty((N, H, W), dtype=torch.float32, device=dev)
     if out.numel() == 0:
@@ -964,7 +972,7 @@ def sigmoid_alpha_blend_backward(grad_alphas, alphas, distances, pix_to_face, si
     """SigmoidAlphaBlendBackward, sigmoid_alpha_blend.h:86-103.  Returns grad_distances (N,H,W,K)."""
     dev = _same_device(("distances", distances), ("pix_to_face", pix_to_face), ("alphas", alphas),
                        ("grad_alphas", grad_alphas))
-    d, p2f = _c(distances, torch.float32), _c(pix_to_face, torch.int64)
+    d, p2f = _aligned(_c(distances, torch.float32)), _aligned(_c(pix_to_face, torch.int64))
     ga, al = _c(grad_alphas, torch.float32), _c(alphas, torch.float32)
     N, H, W, K = d.shape
     out = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)

@@ -84,8 +84,8 @@ class _SoftmaxRGBBlend(torch.autograd.Function):
     def forward(ctx, colors, dists, zbuf, pix_to_face, sigma, gamma, bg, znear, zfar):
         N, H, W, K = pix_to_face.shape
         dev = colors.device
-        c = colors.contiguous()
-        d, z, p2f = dists.contiguous(), zbuf.contiguous(), pix_to_face.contiguous()
+        c = _C._aligned(colors)
+        d, z, p2f = _C._aligned(dists), _C._aligned(zbuf), _C._aligned(pix_to_face)
         zn, zn_t = _plane(znear, N, dev)
         zf, zf_t = _plane(zfar, N, dev)
         out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
@@ -103,7 +103,7 @@ class _SoftmaxRGBBlend(torch.autograd.Function):
         sigma, gamma, bg, zn, zf, has_zn, has_zf = ctx.params
         N, H, W, K = p2f.shape
         dev = c.device
-        g = grad_out.contiguous()
+        g = _C._aligned(grad_out)
         gc = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
         gd = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
         gz = torch.empty((N, H, W, K), dtype=torch.float32, device=dev)
@@ -127,7 +127,7 @@ class _HardRGBBlend(torch.autograd.Function):
     def forward(ctx, colors, pix_to_face, bg):
         N, H, W, K = pix_to_face.shape
         dev = colors.device
-        c, p2f = colors.contiguous(), pix_to_face.contiguous()
+        c, p2f = _C._aligned(colors), _C._aligned(pix_to_face)
         out = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
         if out.numel():
             _lib.call("p3d_hard_rgb_blend_forward", "hard_rgb_blend", dev, c, p2f, bg, N * H * W, K, out)
@@ -139,7 +139,7 @@ class _HardRGBBlend(torch.autograd.Function):
         (p2f,) = ctx.saved_tensors
         N, H, W, K = p2f.shape
         dev = p2f.device
-        g = grad_out.contiguous()
+        g = _C._aligned(grad_out)
         gc = torch.empty((N, H, W, K, 3), dtype=torch.float32, device=dev)
         if gc.numel():
             _lib.call("p3d_hard_rgb_blend_backward", "hard_rgb_blend_backward", dev, g, p2f, N * H * W, K, gc)
@@ -188,7 +188,7 @@ class _SoftDepthBlend(torch.autograd.Function):
     def forward(ctx, dists, zbuf, pix_to_face, sigma, zfar):
         N, H, W, K = pix_to_face.shape
         dev = zbuf.device
-        d, z, p2f = dists.contiguous(), zbuf.contiguous(), pix_to_face.contiguous()
+        d, z, p2f = _C._aligned(dists), _C._aligned(zbuf), _C._aligned(pix_to_face)
         out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
         if out.numel():
             _lib.call("p3d_soft_depth_blend_forward", "soft_depth_blend", dev, d, z, p2f, sigma, zfar, N * H * W, K, out)
@@ -231,7 +231,7 @@ class _HardDepthBlend(torch.autograd.Function):
     def forward(ctx, zbuf, pix_to_face, zfar):
         N, H, W, K = pix_to_face.shape
         dev = zbuf.device
-        z, p2f = zbuf.contiguous(), pix_to_face.contiguous()
+        z, p2f = _C._aligned(zbuf), _C._aligned(pix_to_face)
         out = torch.empty((N, H, W, 1), dtype=torch.float32, device=dev)
         if out.numel():
             _lib.call("p3d_hard_depth_blend_forward", "hard_depth_blend", dev, z, p2f, zfar, N * H * W, K, out)

@@ -421,12 +421,18 @@ std::tuple<Tensor, Tensor> interp_face_attrs_backward(const Tensor& pix_to_face,
 }
 
 // ---- sigmoid alpha blend ----------------------------------------------------------------------------------------------------
+// contiguous with the first element on a 16-byte boundary (include/p3d_amd.h, "Alignment"): a contiguous view at a storage offset is copied
+Tensor aligned(const Tensor& t) {
+  auto c = t.contiguous();
+  return reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0 ? c : c.clone();
+}
+
 Tensor sigmoid_alpha_blend(const Tensor& distances, const Tensor& pix_to_face, double sigma) {
   check_gpu({{&distances, "distances"}, {&pix_to_face, "pix_to_face"}});
   TORCH_CHECK(distances.dim() == 4 && pix_to_face.sizes() == distances.sizes(), "distances and pix_to_face must both have shape (N, H, W, K)");
   DeviceGuard guard(distances.device());
-  auto d = distances.contiguous().to(at::kFloat);
-  auto p2f = pix_to_face.contiguous().to(at::kLong);
+  auto d = aligned(distances.to(at::kFloat));
+  auto p2f = aligned(pix_to_face.to(at::kLong));
   const int64_t N = d.size(0), H = d.size(1), W = d.size(2);
   const int K = (int)d.size(3);
   auto out = at::empty({N, H, W}, d.options());
@@ -440,8 +446,8 @@ Tensor sigmoid_alpha_blend_backward(const Tensor& grad_alphas, const Tensor& alp
                                     double sigma) {
   check_gpu({{&distances, "distances"}, {&pix_to_face, "pix_to_face"}, {&alphas, "alphas"}, {&grad_alphas, "grad_alphas"}});
   DeviceGuard guard(distances.device());
-  auto d = distances.contiguous().to(at::kFloat);
-  auto p2f = pix_to_face.contiguous().to(at::kLong);
+  auto d = aligned(distances.to(at::kFloat));
+  auto p2f = aligned(pix_to_face.to(at::kLong));
   auto ga = grad_alphas.contiguous().to(at::kFloat), al = alphas.contiguous().to(at::kFloat);
   const int64_t N = d.size(0), H = d.size(1), W = d.size(2);
   const int K = (int)d.size(3);

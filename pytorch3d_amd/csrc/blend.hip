@@ -653,13 +653,19 @@ __global__ __launch_bounds__(kBlendBlock) void hard_depth_bwd_generic(const floa
   }
 }
 
-// the K-rows are read and written with 16-byte accesses when they are a multiple of 16 bytes: their bases must be aligned
-bool rows_aligned(int K, const int64_t* p2f, const float* a, const float* b, const float* c, const float* d) {
+// the K-rows are read and written with 16-byte accesses when they are a multiple of 16 bytes: their bases must be aligned.
+// pix_to_face rows (8 B per slot) from K % 2 == 0; float rows (4 B per slot) and colour rows (12 B per slot, `colors`) from
+// K % 4 == 0.  A null pointer passes: whether it may be null is the entry's own check.
+bool rows_aligned(int K, const int64_t* p2f, const float* a, const float* b, const float* c, const float* d,
+                  const float* colors = nullptr, const float* colors2 = nullptr) {
   uintptr_t bits = 0;
   if (K % 2 == 0) bits |= (uintptr_t)p2f;
-  if (K % 4 == 0) bits |= (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d;
+  if (K % 4 == 0) bits |= (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)colors | (uintptr_t)colors2;
   return (bits & 15) == 0;
 }
+
+// the softmax kernels, generic ones included, move a pixel's RGBA as one float4 whatever K is
+bool rgba_aligned(const float* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 }  // namespace p3d
@@ -671,6 +677,7 @@ P3D_API int p3d_sigmoid_alpha_blend_forward(const float* dists, const int64_t* p
   if (npix < 0 || K < 0) return P3D_ERR_INVALID_ARG;
   if (npix == 0) return P3D_OK;
   if (!alphas || (K > 0 && (!dists || !pix_to_face))) return P3D_ERR_INVALID_ARG;
+  if (!rows_aligned(K, pix_to_face, dists, nullptr, nullptr, nullptr)) return P3D_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = blend_grid(npix);
   LaunchScope ls("sigmoid_alpha_fwd", s);
@@ -684,6 +691,7 @@ P3D_API int p3d_sigmoid_alpha_blend_backward(const float* grad_alphas, const flo
   if (npix < 0 || K < 0) return P3D_ERR_INVALID_ARG;
   if (npix * K == 0) return P3D_OK;
   if (!grad_alphas || !alphas || !dists || !pix_to_face || !grad_dists) return P3D_ERR_INVALID_ARG;
+  if (!rows_aligned(K, pix_to_face, dists, grad_dists, nullptr, nullptr)) return P3D_ERR_INVALID_ARG;
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = blend_grid(npix);
   LaunchScope ls("sigmoid_alpha_bwd", s);
@@ -725,6 +733,7 @@ P3D_API int p3d_softmax_rgb_blend_forward(const float* colors, const int64_t* pi
   if (rc != P3D_OK) return rc;
   if (a.npix == 0) return P3D_OK;
   if (!out || (K > 0 && (!colors || !pix_to_face || !dists || !zbuf))) return P3D_ERR_INVALID_ARG;
+  if (!rgba_aligned(out) || !rows_aligned(K, pix_to_face, dists, zbuf, nullptr, nullptr, colors)) return P3D_ERR_INVALID_ARG;
   a.out = out;
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = blend_grid(a.npix);
@@ -745,6 +754,8 @@ P3D_API int p3d_softmax_rgb_blend_backward(const float* grad_out, const float* c
   if (rc != P3D_OK) return rc;
   if (a.npix * K == 0) return P3D_OK;
   if (!grad_out || !colors || !pix_to_face || !dists || !zbuf || !grad_colors || !grad_dists || !grad_zbuf)
+    return P3D_ERR_INVALID_ARG;
+  if (!rgba_aligned(grad_out) || !rows_aligned(K, pix_to_face, dists, zbuf, grad_dists, grad_zbuf, colors, grad_colors))
     return P3D_ERR_INVALID_ARG;
   a.grad_out = grad_out;
   a.g_colors = grad_colors;

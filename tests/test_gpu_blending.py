@@ -3,6 +3,9 @@ fused softmax_rgb_blend, against the reference-generated fixture (tests/golden/b
 C++ CPU kernels and its Python function + autograd), the oracle on random inputs, and -- at the bench
 workload's full size -- a dense torch re-derivation of blending.py:147-244 with torch autograd.
 Tolerances: outputs 1e-5 (north_star), gradients rtol 1e-3.
+
+Per capacity, per branch (ties, faces beyond zfar, saturated sigmoids, empty pixels, equal planes), the second grid-stride round, the
+argument and alignment checks of the C entries, all against a float64 chain through a per-class gate: tests/test_gpu_blend_edges.py.
 """
 import os
 from collections import namedtuple
@@ -61,7 +64,7 @@ def test_softmax_rgb_blend_vs_reference_python(tag):
 # registers in AGPRs -- pytorch3d_amd/build.py: AGPR_KERNELS_TESTED points here); `dense`: every slot of every pixel holds a face,
 # i.e. every register row of the kernels is live (the round-4 miscompile showed only on inputs that fill the queues)
 @pytest.mark.parametrize("dense", [False, True])
-@pytest.mark.parametrize("K", [1, 3, 4, 8, 10, 16, 17, 24, 32, 40])
+@pytest.mark.parametrize("K", [1, 2, 3, 4, 8, 10, 16, 17, 24, 32, 33, 40, 150])
 def test_blend_kernels_vs_oracle_all_capacities(K, dense):
     import pytorch3d_amd as p3d
     from pytorch3d_amd import _C
