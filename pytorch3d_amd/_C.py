@@ -1190,6 +1190,101 @@ def iou_box3d_host(boxes1, boxes2):
 
 
 # ----------------------------------------------------------------------------------------------
+# implicit rendering (csrc/implicit.hip), behind pytorch3d_amd.implicit (shim.EXPORTS: sample_pdf -> implicit.sample_pdf_op).
+def _check_pdf(bins, weights, outputs, who):
+    for name, t in (("bins", bins), ("weights", weights), ("outputs", outputs)):
+        if t.dim() != 2:
+            raise RuntimeError(f"{who}: {name} must have 2 dimensions, got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name} must be float32, got {t.dtype}")
+        if t.device != bins.device:
+            raise RuntimeError(f"Expected all tensors to be on the same device, but {name} is on {t.device} and bins is on {bins.device}")
+    B, n_bins = weights.shape
+    if tuple(bins.shape) != (B, n_bins + 1) or outputs.shape[0] != B:
+        raise RuntimeError(f"{who}: bins (B, n_bins + 1), weights (B, n_bins), outputs (B, S) expected, got {tuple(bins.shape)}, "
+                           f"{tuple(weights.shape)}, {tuple(outputs.shape)}")
+    if n_bins < 1:
+        raise RuntimeError(f"{who}: n_bins must be at least 1")
+    if not outputs.is_contiguous():
+        raise RuntimeError(f"{who}: outputs must be contiguous")
+    return B, n_bins, outputs.shape[1]
+
+
+def sample_pdf(bins, weights, outputs, eps):
+    """SamplePdf (sample_pdf/sample_pdf.h) on GPU tensors: p3di_sample_pdf (csrc/implicit_abi.h) in place over outputs (B, S), whose
+    version counter is bumped.  bins and weights are made contiguous here.  Returns None, as the reference's operator does."""
+    who = "sample_pdf"
+    B, n_bins, S = _check_pdf(bins, weights, outputs, who)
+    dev = _same_device(("bins", bins), ("weights", weights), ("outputs", outputs))
+    if B * S:
+        nbytes = _lib.load().p3di_sample_pdf_workspace_bytes(B, n_bins)
+        with torch.cuda.device(dev):
+            ws = _workspace(nbytes, dev) if nbytes else None
+        _lib.call("p3di_sample_pdf", who, dev, bins.contiguous(), weights.contiguous(), outputs, B, n_bins, S, float(eps), ws, nbytes)
+    torch.autograd.graph.increment_version(outputs)
+
+
+def sample_pdf_host(bins, weights, outputs, eps):
+    """The same contract on CPU tensors: p3di_sample_pdf_host, a serial loop over the rows."""
+    who = "sample_pdf_host"
+    B, n_bins, S = _check_pdf(bins, weights, outputs, who)
+    if bins.is_cuda:
+        raise RuntimeError(f"{who}: the host loop takes CPU tensors")
+    if B * S:
+        _lib.call("p3di_sample_pdf_host", who, None, bins.contiguous(), weights.contiguous(), outputs, B, n_bins, S, float(eps))
+    torch.autograd.graph.increment_version(outputs)
+
+
+def _check_rays(who, densities, features):
+    _need_gpu(densities, "densities")
+    if densities.dim() != 2 or densities.dtype != torch.float32 or densities.shape[1] < 1:
+        raise RuntimeError(f"{who}: densities must be float32 (N, P) with P >= 1, got {densities.dtype} {tuple(densities.shape)}")
+    N, P = densities.shape
+    if features is None:
+        return N, P, 0
+    if features.dtype != torch.float32 or features.dim() != 3 or tuple(features.shape[:2]) != (N, P) or features.device != densities.device:
+        raise RuntimeError(f"{who}: features must be float32 (N, P, C) on the densities' device, got {features.dtype} "
+                           f"{tuple(features.shape)} on {features.device}")
+    return N, P, features.shape[2]
+
+
+def ea_raymarch_forward(densities, features, shift, one_plus_eps, return_weights=False):
+    """p3di_ea_raymarch_forward (csrc/implicit_abi.h): densities (N, P), features (N, P, C) or None (absorption only) -> out (N, C + 1)
+    and the weights (N, P) or None."""
+    who = "ea_raymarch_forward"
+    N, P, C = _check_rays(who, densities, features)
+    dev = densities.device
+    with torch.cuda.device(dev):
+        out = torch.empty((N, C + 1), dtype=torch.float32, device=dev)
+        weights = torch.empty((N, P), dtype=torch.float32, device=dev) if return_weights else None
+    if N:
+        _lib.call("p3di_ea_raymarch_forward", who, dev, densities.contiguous(), None if features is None else features.contiguous(), N, P, C,
+                  int(shift), float(one_plus_eps), out, weights)
+    return out, weights
+
+
+def ea_raymarch_backward(densities, features, grad_out, grad_weights, shift, one_plus_eps):
+    """p3di_ea_raymarch_backward: (grad_densities (N, P), grad_features (N, P, C) or None)."""
+    who = "ea_raymarch_backward"
+    N, P, C = _check_rays(who, densities, features)
+    dev = densities.device
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (N, C + 1):
+        raise RuntimeError(f"{who}: grad_out must be float32 (N, C + 1), got {grad_out.dtype} {tuple(grad_out.shape)}")
+    if grad_weights is not None and (grad_weights.dtype != torch.float32 or tuple(grad_weights.shape) != (N, P)):
+        raise RuntimeError(f"{who}: grad_weights must be float32 (N, P), got {grad_weights.dtype} {tuple(grad_weights.shape)}")
+    with torch.cuda.device(dev):
+        gd = torch.empty((N, P), dtype=torch.float32, device=dev)
+        gf = torch.empty((N, P, C), dtype=torch.float32, device=dev) if features is not None else None
+        nbytes = _lib.load().p3di_ea_raymarch_backward_workspace_bytes(N, P)
+        ws = _workspace(nbytes, dev) if nbytes else None
+    if N:
+        _lib.call("p3di_ea_raymarch_backward", who, dev, densities.contiguous(), None if features is None else features.contiguous(),
+                  grad_out.contiguous(), None if grad_weights is None else grad_weights.contiguous(), N, P, C, int(shift),
+                  float(one_plus_eps), gd, gf, ws, nbytes)
+    return gd, gf
+
+
+# ----------------------------------------------------------------------------------------------
 # GraphConv / gather_scatter neighbour sums (csrc/graph_conv.hip), behind pytorch3d_amd.graph_conv.gather_scatter_op (shim.EXPORTS),
 # which builds (or recalls) the table and comes here.
 def neighbor_sum(rows, offsets, entries, base=None):
@@ -1551,6 +1646,7 @@ POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "fa
 POINT_CLOUD_EXPORTS = ("sample_farthest_points", "ball_query")
 BOX3D_EXPORTS = ("iou_box3d",)
 GRAPH_EXPORTS = ("gather_scatter",)
+IMPLICIT_EXPORTS = ("sample_pdf",)
 
 # the reference's hot path: what each flavour implements itself (the pybind flavour reads this list)
 HOT_PATH_EXPORTS = (

@@ -21,6 +21,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # P3D_LIB_PATH selects an ablation build (profiles/ scripts only; see build.py)
 LIB_PATH = os.environ.get("P3D_LIB_PATH") or os.path.join(_HERE, "libp3d_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "p3d_amd.h")
+# the extension ABI of csrc/implicit.hip: entries p3di_*, declared in a header of their own (see its head)
+EXTENSION_HEADER_PATH = os.path.join(_HERE, "csrc", "implicit_abi.h")
+EXTENSION_PREFIX = "p3di_"
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -41,11 +44,12 @@ _WORDS = set(_SCALARS) | {"void", "char", "long", "short", "signed", "const", "s
 _PARAM = re.compile(r"(const )?(\w+)(?: ?(\*))?(?: ?\b(\w+))?(?: ?(\[\d+\]))?")  # const, type, *, name, [n]
 
 
-def parse_header(text):
+def parse_header(text, prefix="p3d_"):
     """({entry: (return type, [parameter types])}, {macro name without P3D_: integer}) of a header in the style of include/p3d_amd.h.
     The types are C spellings without the parameter names: "const float*", "int64_t", "const int64_t[2]", "p3d_stream_t".  Comments
     go first (some hold text of the form p3d_x(...)), then preprocessor lines; every statement left must be the stream typedef or a
-    `RET p3d_name(PARAMS)` whose types ctypes_signature knows: anything else raises with the statement's text."""
+    `RET p3d_name(PARAMS)` whose types ctypes_signature knows: anything else raises with the statement's text.  prefix: what the
+    entries' names begin with (the extension header's: EXTENSION_PREFIX)."""
     text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
     constants = {m.group(1): int(m.group(2)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+P3D_(\w+)[ \t]+\(?(-?\d+)u?\)?[ \t]*$", text, re.M)}
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
@@ -55,7 +59,7 @@ def parse_header(text):
         statement = " ".join(statement.split())
         if statement in ("", "typedef void* p3d_stream_t"):
             continue
-        m = re.fullmatch(r"(.+?) ?\b(p3d_\w+) ?\((.*)\)", statement)
+        m = re.fullmatch(r"(.+?) ?\b(%s\w+) ?\((.*)\)" % re.escape(prefix), statement)
         if m is None:
             raise ValueError(f"cannot parse the declaration `{statement}`")
         if m.group(2) in declarations:
@@ -95,6 +99,14 @@ try:
 except OSError as e:
     raise ExtensionMissing(f"{HEADER_PATH} not found ({e}): the package reads the C ABI of libp3d_amd.so from this header") from e
 
+try:
+    with open(EXTENSION_HEADER_PATH) as _f:
+        EXTENSION_DECLARATIONS, EXTENSION_CONSTANTS = parse_header(_f.read(), EXTENSION_PREFIX)
+except OSError as e:
+    raise ExtensionMissing(f"{EXTENSION_HEADER_PATH} not found ({e}): the package reads the ABI of csrc/implicit.hip from this header") from e
+assert not set(EXTENSION_CONSTANTS) & (set(CONSTANTS) | set(globals())), sorted(set(EXTENSION_CONSTANTS) & (set(CONSTANTS) | set(globals())))
+globals().update(EXTENSION_CONSTANTS)  # SAMPLE_PDF_ROWS, SAMPLE_PDF_LDS_FLOATS
+
 # every `#define P3D_<NAME> <integer>` of the header as <NAME>: ABI_VERSION, MAX_K, OK, ERR_*, the flags (RASTER_*, BWD_*, ...) and the
 # launch constants the wrappers and tests size their inputs by (KNN_TILE, BOX3D_MAX_GROUPS, ...)
 assert not set(CONSTANTS) & set(globals()), sorted(set(CONSTANTS) & set(globals()))
@@ -105,6 +117,8 @@ NEIGHBOR_SUM_GROUP_LANES = 256
 
 _SIGNATURES = {name: ctypes_signature(*decl) for name, decl in DECLARATIONS.items()}  # name: (restype, [argtypes])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+_EXTENSION_SIGNATURES = {name: ctypes_signature(*decl) for name, decl in EXTENSION_DECLARATIONS.items()}
+EXTENSION_SYMBOLS = tuple(_EXTENSION_SIGNATURES)
 
 # the torch dtypes a tensor may have where the header declares a pointer to this element type (None: any)
 _ELEMENTS = {"float": (torch.float32,), "double": (torch.float64,), "int64_t": (torch.int64,), "int32_t": (torch.int32,),
@@ -184,6 +198,7 @@ def bind(fn, entry, ret, params):
 _lock = threading.Lock()
 _lib = None
 _CALLS = {}  # status entry: its invoke, bound when load() installs the signatures
+_EXTENSION_CALLS = {}  # the same for the entries of the extension header
 
 
 def load():
@@ -212,6 +227,12 @@ def load():
             fn.argtypes = args
             if marshaller(name, *DECLARATIONS[name])[2]:
                 _CALLS[name] = bind(fn, name, *DECLARATIONS[name])
+        for name, (res, args) in _EXTENSION_SIGNATURES.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+            if marshaller(name, *EXTENSION_DECLARATIONS[name])[2]:
+                _EXTENSION_CALLS[name] = bind(fn, name, *EXTENSION_DECLARATIONS[name])
         _lib = lib
     return _lib
 
@@ -222,7 +243,7 @@ def call(entry, where, device, *args):
     host entry.  Raises like check(code, where) on a status other than P3D_OK."""
     if _lib is None:
         load()
-    _CALLS[entry](where, device, *args)
+    (_CALLS.get(entry) or _EXTENSION_CALLS[entry])(where, device, *args)
 
 
 def check(code, where):

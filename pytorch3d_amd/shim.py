@@ -17,7 +17,9 @@ unmodified `pytorch3d.ops.sample_farthest_points` runs, and so does the forward 
 `_backward` (csrc/points_to_volumes.hip): the unmodified `pytorch3d.ops.add_pointclouds_to_volumes` runs, forward and backward.
 And `_C.iou_box3d` (csrc/box3d.hip: the kernels for GPU tensors, the library's host loop for CPU tensors): the unmodified
 `pytorch3d.ops.box3d_overlap` runs on both.  And `_C.gather_scatter` (csrc/graph_conv.hip): the unmodified `pytorch3d.ops.GraphConv`
-runs on the GPU, forward and backward, its neighbour sums added in list order instead of by float atomics.
+runs on the GPU, forward and backward, its neighbour sums added in list order instead of by float atomics.  And `_C.sample_pdf`
+(csrc/implicit.hip: the kernel for GPU tensors, the library's host loop for CPU tensors, the same bits from both): the unmodified
+`pytorch3d.renderer.implicit.sample_pdf` runs on both.
 
     shim.install(patch_python=True)
 
@@ -90,6 +92,13 @@ reference classes runs on them end to end:
                                                                  (csrc/vert_align.hip); an ordered grad_feats under
                                                                  torch.use_deterministic_algorithms(True)
 
+    renderer.implicit.raymarching.EmissionAbsorptionRaymarcher.forward / AbsorptionOnlyRaymarcher.forward
+                                                              -> pytorch3d_amd.implicit: one autograd node over csrc/implicit.hip's
+                                                                 forward and backward kernels (scans along the ray, no division, no
+                                                                 atomics, no cat); the reference's input checks and its density
+                                                                 bounds warning stay; CPU tensors, float64 and surface_thickness < 1
+                                                                 go to this package's torch formulation of the same chain
+
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
 the kernels do not).  Cameras that require grad are NOT such an input: MeshRasterizer, PointsRasterizer and the fused
@@ -125,6 +134,7 @@ EXPORTS = {
     "points_to_volumes_backward": ("points_to_volumes", "points_to_volumes_backward_op"),
     "iou_box3d": ("iou_box3d", "iou_box3d_op"),  # csrc/box3d.hip; the library's host loop for CPU boxes
     "gather_scatter": ("graph_conv", "gather_scatter_op"),  # csrc/graph_conv.hip; the table of an edge tensor is cached
+    "sample_pdf": ("implicit", "sample_pdf_op"),  # csrc/implicit.hip; the library's host loop for CPU tensors; in place
 }
 
 
@@ -623,6 +633,34 @@ def _graph_conv(ref):
     return {"gather_scatter": gather_scatter}
 
 
+def _raymarchers(ref):
+    """EmissionAbsorptionRaymarcher.forward / AbsorptionOnlyRaymarcher.forward -> pytorch3d_amd.implicit behind the reference's own
+    _check_raymarcher_inputs and _check_density_bounds (the warning and its two host syncs stay).  The methods are patched directly, as
+    GraphConv.forward is; PATCH_CALLS counts kernel calls as fused and the torch formulation as fallbacks."""
+    ours = _our("implicit")
+    ea_orig, ao_orig = ref.EmissionAbsorptionRaymarcher.forward, ref.AbsorptionOnlyRaymarcher.forward
+
+    def ea_forward(self, rays_densities, rays_features, eps=1e-10, **kwargs):
+        ref._check_raymarcher_inputs(rays_densities, rays_features, None, z_can_be_none=True, features_can_be_none=False, density_1d=True)
+        ref._check_density_bounds(rays_densities)
+        out = ours.ea_raymarch_unchecked(rays_densities, rays_features, eps, self.surface_thickness)
+        _count("EmissionAbsorptionRaymarcher.forward", ours.kernel_path(rays_densities, rays_features, self.surface_thickness))
+        return out
+
+    def ao_forward(self, rays_densities, **kwargs):
+        ref._check_raymarcher_inputs(rays_densities, None, None, features_can_be_none=True, z_can_be_none=True, density_1d=True)
+        ref._check_density_bounds(rays_densities[..., 0])
+        out = ours.absorption_only_raymarch_unchecked(rays_densities)
+        _count("AbsorptionOnlyRaymarcher.forward", ours.kernel_path(rays_densities))
+        return out
+
+    for cls, orig, new in ((ref.EmissionAbsorptionRaymarcher, ea_orig, ea_forward), (ref.AbsorptionOnlyRaymarcher, ao_orig, ao_forward)):
+        new.__name__, new.__doc__, new.__wrapped__, new.__p3d_amd__ = "forward", orig.__doc__, orig, True
+        cls.forward = new
+        _PATCHED.append((cls, "forward", orig, new))
+    return {}
+
+
 def _vert_align(ref):
     """There is no `_C` operator under the reference's function (it is F.grid_sample and copies), so plain install() leaves it alone.
     csrc/vert_align.hip for float32 GPU calls in a mode the kernels cover, the reference's chain restated for the rest."""
@@ -652,6 +690,7 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.iou_box3d", ("pytorch3d.ops",), _box3d_overlap),
     ("pytorch3d.ops.graph_conv", ("pytorch3d.ops",), _graph_conv),
     ("pytorch3d.ops.vert_align", ("pytorch3d.ops",), _vert_align),
+    ("pytorch3d.renderer.implicit.raymarching", (), _raymarchers),
 )
 
 
