@@ -1640,6 +1640,56 @@ def edge_point_dist_backward(points, segms, idxs, grad_dists):
     return point_mesh_backward("edge_point", points, segms, idxs, grad_dists)
 
 
+# ----------------------------------------------------------------------------------------------
+# cubify (csrc/cubify.hip, csrc/implicit_abi.h), behind pytorch3d_amd.cubify.  No `_C` operator of the reference: nothing in shim.EXPORTS.
+def cubify_fits(N, D, H, W):
+    """Whether the kernels' int32 indices cover the sizes (else p3di_cubify_count refuses them)."""
+    return min(D, H, W) >= 1 and N * (D + 1) * (H + 1) * (W + 1) <= 2**31 - 1 and 12 * N * D * H * W <= 2**31 - 1
+
+
+def cubify_count(voxels, thresh):
+    """p3di_cubify_count: voxels (N, D, H, W) float32 on a GPU, any strides -> (workspace, counts (N, 2) int64 = (V_n, F_n)), both on
+    the device and not synchronised.  The workspace goes to cubify_emit unchanged."""
+    who = "cubify_count"
+    _need_gpu(voxels, "voxels")
+    if voxels.dim() != 4 or voxels.dtype != torch.float32:
+        raise RuntimeError(f"{who}: voxels must be float32 (N, D, H, W), got {voxels.dtype} {tuple(voxels.shape)}")
+    N, D, H, W = voxels.shape
+    if not cubify_fits(N, D, H, W):
+        raise RuntimeError(f"{who}: {tuple(voxels.shape)} is beyond the kernels' int32 indices")
+    dev = voxels.device
+    nbytes = _lib.load().p3di_cubify_workspace_bytes(N, D, H, W)
+    with torch.cuda.device(dev):
+        ws = _workspace(nbytes, dev)
+        counts = torch.empty((N, 2), dtype=torch.int64, device=dev)
+    _lib.call("p3di_cubify_count", who, dev, voxels, voxels.stride(), N, D, H, W, float(thresh), ws, nbytes, counts)
+    return ws, counts
+
+
+def cubify_emit(workspace, shape, coords, feats, total_verts, total_faces):
+    """p3di_cubify_emit from cubify_count's workspace: shape = (N, D, H, W), coords the (W + 1) + (H + 1) + (D + 1) float32 axis values,
+    feats (N, K, D, H, W) float32 with any strides or None, the totals summed from the counts -> (verts (total_verts, 3) float32,
+    faces (total_faces, 3) int64 with per-mesh indices, face_feats (total_faces, K) or None)."""
+    who = "cubify_emit"
+    N, D, H, W = shape
+    dev = _same_device(("workspace", workspace), ("coords", coords), *([("feats", feats)] if feats is not None else []))
+    if coords.dtype != torch.float32 or coords.numel() != D + H + W + 3 or not coords.is_contiguous():
+        raise RuntimeError(f"{who}: coords must be {D + H + W + 3} contiguous float32 values, got {coords.dtype} {tuple(coords.shape)}")
+    K = 0
+    if feats is not None:
+        if feats.dtype != torch.float32 or feats.dim() != 5 or (feats.shape[0],) + tuple(feats.shape[2:]) != (N, D, H, W):
+            raise RuntimeError(f"{who}: feats must be float32 (N, K, D, H, W) over the voxels' grid, got {feats.dtype} {tuple(feats.shape)}")
+        K = feats.shape[1]
+    with torch.cuda.device(dev):
+        verts = torch.empty((total_verts, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((total_faces, 3), dtype=torch.int64, device=dev)
+        face_feats = torch.empty((total_faces, K), dtype=torch.float32, device=dev) if feats is not None else None
+    if total_faces:
+        _lib.call("p3di_cubify_emit", who, dev, coords, feats if K else None, feats.stride() if K else (0,) * 5, K, N, D, H, W,
+                  int(total_verts), int(total_faces), workspace, workspace.numel(), verts, faces, face_feats)
+    return verts, faces, face_feats
+
+
 POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
 # operators both flavours serve through Python wrappers of their own modules (shim.EXPORTS holds the whole table)

@@ -22,6 +22,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     box3d_overlap                    exact intersection volume and IoU of oriented 3D boxes, one wave per pair, no list cap
     gather_scatter, graph_conv, graph_topology  GraphConv's neighbour sums through an inverted index: list order, no atomics, one node
     vert_align                       image features pooled at the vertices: one launch per map, strided maps, packed rows direct
+    cubify, cubify_packed            voxel occupancy grids to merged cube meshes: five launches and one host read, no atomics
     sample_pdf, ea_raymarch, absorption_only_raymarch  hierarchical ray sampling and emission-absorption raymarching, fused, fwd + bwd
 
 Importing the package does not load the HIP library; the first operator call does, and raises
@@ -32,6 +33,7 @@ from .ball_query import ball_query  # noqa: F401
 from .blending import (BlendParams, hard_depth_blend, hard_rgb_blend, sigmoid_alpha_blend, soft_depth_blend,  # noqa: F401
                        softmax_rgb_blend)
 from .chamfer import chamfer_distance  # noqa: F401
+from .cubify import cubify, cubify_packed  # noqa: F401
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .implicit import absorption_only_raymarch, ea_raymarch, sample_pdf  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401

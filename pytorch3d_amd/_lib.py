@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # P3D_LIB_PATH selects an ablation build (profiles/ scripts only; see build.py)
 LIB_PATH = os.environ.get("P3D_LIB_PATH") or os.path.join(_HERE, "libp3d_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "p3d_amd.h")
-# the extension ABI of csrc/implicit.hip: entries p3di_*, declared in a header of their own (see its head)
+# the extension ABI of csrc/implicit.hip and csrc/cubify.hip: entries p3di_*, declared in a header of their own (see its head)
 EXTENSION_HEADER_PATH = os.path.join(_HERE, "csrc", "implicit_abi.h")
 EXTENSION_PREFIX = "p3di_"
 
@@ -103,9 +103,9 @@ try:
     with open(EXTENSION_HEADER_PATH) as _f:
         EXTENSION_DECLARATIONS, EXTENSION_CONSTANTS = parse_header(_f.read(), EXTENSION_PREFIX)
 except OSError as e:
-    raise ExtensionMissing(f"{EXTENSION_HEADER_PATH} not found ({e}): the package reads the ABI of csrc/implicit.hip from this header") from e
+    raise ExtensionMissing(f"{EXTENSION_HEADER_PATH} not found ({e}): the package reads the ABI of csrc/implicit.hip and csrc/cubify.hip from this header") from e
 assert not set(EXTENSION_CONSTANTS) & (set(CONSTANTS) | set(globals())), sorted(set(EXTENSION_CONSTANTS) & (set(CONSTANTS) | set(globals())))
-globals().update(EXTENSION_CONSTANTS)  # SAMPLE_PDF_ROWS, SAMPLE_PDF_LDS_FLOATS
+globals().update(EXTENSION_CONSTANTS)  # SAMPLE_PDF_ROWS, SAMPLE_PDF_LDS_FLOATS, CUBIFY_BLOCK, CUBIFY_ITEMS, CUBIFY_CARRY_BLOCK
 
 # every `#define P3D_<NAME> <integer>` of the header as <NAME>: ABI_VERSION, MAX_K, OK, ERR_*, the flags (RASTER_*, BWD_*, ...) and the
 # launch constants the wrappers and tests size their inputs by (KNN_TILE, BOX3D_MAX_GROUPS, ...)

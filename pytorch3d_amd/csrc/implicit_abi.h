@@ -1,4 +1,4 @@
-/* implicit_abi.h -- the C ABI of csrc/implicit.hip: sample_pdf and emission-absorption raymarching.
+/* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching) and of csrc/cubify.hip.
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -53,6 +53,37 @@ size_t p3di_ea_raymarch_backward_workspace_bytes(int64_t N, int64_t P);
 int p3di_ea_raymarch_backward(const float* densities, const float* features, const float* grad_out, const float* grad_weights,
                              int64_t N, int64_t P, int64_t C, int64_t shift, float one_plus_eps, float* grad_densities,
                              float* grad_features, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+
+/* cubify (csrc/cubify.hip): occupancy grids voxels (N, D, H, W), float32 read through voxel_strides (in elements: a slice, a squeeze or
+ * a permuted view is read in place), to the merged cube meshes of the reference's pytorch3d/ops/cubify.py:
+ *   occupied iff voxels[n, d, h, w] >= thresh (NaN and everything outside the grid: not);  x runs along W, y along H, z along D;
+ *   voxels in (n, h, w, d) order, d fastest, each with the directions -x +y -z -y +x +z, a direction's two triangles iff the neighbour
+ *   there is not occupied:  (0,1,2) (1,3,2) | (2,3,6) (3,7,6) | (0,2,6) (0,6,4) | (0,5,1) (0,4,5) | (6,7,5) (6,5,4) | (1,7,3) (1,5,7),
+ *   corner c = 4x + 2y + z of voxel (h, w, d) being lattice point g = ((h + y)(W + 1) + (w + x))(D + 1) + (d + z);
+ *   a lattice point is kept iff a triangle of its mesh names it; the kept ones of a mesh keep ascending g, a face stores their ranks.
+ * Two entries around the caller's one host read:
+ * p3di_cubify_count: fills the workspace (a byte of exposure bits per voxel, the block-local rank of every lattice point, and the
+ *   exclusive scans of the totals of every scan block of P3D_CUBIFY_ITEMS items; a scan block never spans two meshes) and writes
+ *   counts (N, 2) int64 = (V_n, F_n).  Three launches: a lane per voxel, a lane per lattice point, and two workgroups of
+ *   P3D_CUBIFY_CARRY_BLOCK lanes over the block totals in rounds.  No workgroup waits for another.
+ * p3di_cubify_emit: from that workspace, unchanged, on the same stream: verts (total_verts, 3) float32 with row first_vert[n] + rank =
+ *   (coords[x], coords[W + 1 + y], coords[W + 1 + H + 1 + z]) -- coords: the (W + 1) + (H + 1) + (D + 1) coordinate values of the
+ *   three axes, made by the caller --, faces (total_faces, 3) int64 with per-mesh ranks, and, where feats is not NULL and K > 0,
+ *   face_feats (total_faces, K) = feats[n, :, d, h, w] of the face's voxel, feats (N, K, D, H, W) float32 read through feat_strides.
+ *   total_verts and total_faces must be the sums of the counts: the outputs are written by those, not by these two numbers.
+ * workspace: p3di_cubify_workspace_bytes(N, D, H, W) bytes for both (smaller: P3D_ERR_WORKSPACE), about 1 byte per voxel and 4 per
+ * lattice point.  0 for sizes the entries refuse.
+ * No atomic; the same bits on every run and stream.  N == 0 (count) and total_faces == 0 (emit): P3D_OK without a launch.  A dimension
+ * below 1, negative sizes, missing pointers, and N (D+1)(H+1)(W+1) or 12 N D H W beyond INT32_MAX: P3D_ERR_INVALID_ARG.  No host sync. */
+#define P3D_CUBIFY_BLOCK 256
+#define P3D_CUBIFY_ITEMS 1024
+#define P3D_CUBIFY_CARRY_BLOCK 1024
+size_t p3di_cubify_workspace_bytes(int64_t N, int64_t D, int64_t H, int64_t W);
+int p3di_cubify_count(const float* voxels, const int64_t voxel_strides[4], int64_t N, int64_t D, int64_t H, int64_t W, float thresh,
+                      void* workspace, size_t workspace_bytes, int64_t* counts, p3d_stream_t stream);
+int p3di_cubify_emit(const float* coords, const float* feats, const int64_t feat_strides[5], int64_t K, int64_t N, int64_t D, int64_t H,
+                     int64_t W, int64_t total_verts, int64_t total_faces, const void* workspace, size_t workspace_bytes, float* verts,
+                     int64_t* faces, float* face_feats, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -674,6 +674,21 @@ def _vert_align(ref):
     return {"vert_align": vert_align}
 
 
+def _cubify(ref):
+    """pytorch3d.ops.cubify (a torch chain of dozens of launches and N + 2 host syncs; no `_C` operator stands under it, so plain
+    install() leaves it alone) -> pytorch3d_amd.cubify: csrc/cubify.hip for float32 GPU grids, our torch formulation of the same
+    contract for the rest.  `pytorch3d.ops.cubify` names the module and, on the package, the function: _rebind takes the module from
+    importlib and _replace_everywhere rebinds the function in both holders."""
+    ours = _our("cubify")
+
+    def cubify(voxels, thresh, *, feats=None, device=None, align="topleft"):
+        out = ours.cubify(voxels, thresh, feats=feats, device=device, align=align)
+        _count("cubify", ours.kernel_path(voxels, feats, device, align))
+        return out
+
+    return {"cubify": cubify}
+
+
 # (reference module, the packages that copied its names, its replacements), in the order they are applied
 _FUNCTION_PATCHES = (
     ("pytorch3d.loss.mesh_edge_loss", ("pytorch3d.loss",), _mesh_loss),
@@ -690,6 +705,7 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.iou_box3d", ("pytorch3d.ops",), _box3d_overlap),
     ("pytorch3d.ops.graph_conv", ("pytorch3d.ops",), _graph_conv),
     ("pytorch3d.ops.vert_align", ("pytorch3d.ops",), _vert_align),
+    ("pytorch3d.ops.cubify", ("pytorch3d.ops",), _cubify),
     ("pytorch3d.renderer.implicit.raymarching", (), _raymarchers),
 )
 
