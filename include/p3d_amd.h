@@ -605,7 +605,7 @@ int p3d_soft_phong_backward(const float* grad_out, const int64_t* pix_to_face, c
  * NCHW copies of the maps + permutes, and their autograd graph, with one kernel each way reading the maps in their
  * own (N, Hm, Wm, C) layout.  face_uvs (F,3,2) = verts_uvs[faces_uvs]; texels (N,H,W,K,C) fully written.
  * Backward: grad_bary (N,H,W,K,3) fully written; grad_face_uvs (F,3,2) and grad_maps (N,Hm,Wm,C) zeroed and
- * accumulated.  padding "reflection" is not provided. */
+ * accumulated.  A sample with pix_to_face >= F reads as zero and has no gradient.  padding "reflection" is not provided. */
 #define P3D_PAD_ZEROS 0
 #define P3D_PAD_BORDER 1
 #define P3D_SAMPLE_BILINEAR 0

@@ -295,7 +295,7 @@ def sample_uv(pix_to_face, bary, face_uvs, maps, align_corners=True, padding_mod
     N, H, W, K = p2f.shape
     _, Hm, Wm, C = mp.shape
     out = torch.zeros((N, H, W, K, C), dtype=torch.float32)
-    lib().orc_sample_uv_forward(_p(p2f), _p(b), _p(fu), _p(mp), N, ctypes.c_int64(H * W * K), Hm, Wm, C, int(align_corners),
+    lib().orc_sample_uv_forward(_p(p2f), _p(b), _p(fu), _p(mp), N, ctypes.c_int64(H * W * K), ctypes.c_int64(fu.shape[0]), Hm, Wm, C, int(align_corners),
                                 _PAD[padding_mode], _SMODE[sampling_mode], _p(out))
     return out
 
@@ -323,8 +323,8 @@ def sample_uv_multi(pix_to_face, bary, face_uvs, maps, maps_ids, align_corners=T
     _, M, Hm, Wm, C = mp.shape
     out = torch.zeros((N, H, W, K, C), dtype=torch.float32)
     lib().orc_sample_uv_multi_forward(_p(p2f), _p(b), _p(fu), _p(mp), _p(ids), ctypes.c_int64(ids.numel()), N,
-                                      ctypes.c_int64(H * W * K), M, Hm, Wm, C, int(align_corners), _PAD[padding_mode],
-                                      _SMODE[sampling_mode], _p(out))
+                                      ctypes.c_int64(H * W * K), ctypes.c_int64(fu.shape[0]), M, Hm, Wm, C, int(align_corners),
+                                      _PAD[padding_mode], _SMODE[sampling_mode], _p(out))
     return out
 
 

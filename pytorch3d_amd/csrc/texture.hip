@@ -30,6 +30,7 @@ struct TexArgs {
   int N, Hm, Wm, C;
   int align, border, nearest;
   int64_t HWK;
+  int64_t F;           // faces: a sample with pix_to_face >= F reads as zero and has no gradient, as in texture_multi.hip and atlas.hip
 };
 
 // torch.lerp(start, end, w) (ATen/native/Lerp.h): start + w * (end - start) where |w| < 0.5, end - (end - start) * (1 - w) elsewhere
@@ -96,7 +97,12 @@ __global__ __launch_bounds__(256) void sample_uv_fwd_kernel(TexArgs a) {
   const int64_t img = (int64_t)n * a.HWK;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.HWK; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t p = img + i;
-    const int f = (int)a.p2f[p];
+    const int64_t fr = a.p2f[p];
+    if (fr >= a.F) {  // no such face: nothing of face_uvs or the maps is read
+      for (int ch = 0; ch < C; ++ch) a.texels[p * C + ch] = 0.0f;
+      continue;
+    }
+    const int f = (int)fr;
     float u = 0.0f, v = 0.0f;
     if (f >= 0) {
       const float b0 = a.bary[p * 3], b1 = a.bary[p * 3 + 1], b2 = a.bary[p * 3 + 2];
@@ -166,9 +172,11 @@ __global__ __launch_bounds__(256) void sample_uv_bwd_kernel(TexArgs a, int64_t s
   float bgacc[kBgCh] = {0.f, 0.f, 0.f, 0.f};
   for (int64_t base = begin; base < end; base += 64) {
     const int64_t i = base + lane;
-    const bool ok = i < end;
+    const bool live = i < end;
     const int64_t p = img + i;
-    const int f = ok ? (int)a.p2f[p] : -1;
+    const int64_t fr = live ? a.p2f[p] : -1;
+    const bool ok = live && fr < a.F;  // pix_to_face >= F: no such face, grad_bary = 0 and nothing else
+    const int f = ok ? (int)fr : -1;
     float b[3] = {0.f, 0.f, 0.f}, r[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float u = 0.0f, v = 0.0f;
     if (f >= 0) {
@@ -221,31 +229,29 @@ __global__ __launch_bounds__(256) void sample_uv_bwd_kernel(TexArgs a, int64_t s
         }
         for (int ch = ch0; ch < C; ++ch) {
           const float gc = g[ch];
-          // grid_sampler_2d_backward: scatter g * weight, and d out / d (ix, iy) from the corner values
+          // grid_sampler_2d_backward: scatter g * weight, and d out / d (ix, iy) from the corner values.  The derivative takes the
+          // DIFFERENCES of neighbouring corners first (a corner outside the map counts as 0), as ATen's vectorised CPU kernel does
+          // (GridSamplerKernel.cpp): four products summed one by one, as its CUDA kernel does, round at the size of a product, not of
+          // the difference, and came to 1.0 - 1.15 of the suite's bound on grad_bary (4 x the float32 chain's own error) on 8 x 1 maps.
+          float val[4] = {0.0f, 0.0f, 0.0f, 0.0f};
           if (in[0]) {
             if (!merge) unsafeAtomicAdd(gmap + o0 + ch, c.w[0] * gc);
-            const float val = map[o0 + ch];
-            gix -= val * (y1 - c.iy) * gc;
-            giy -= val * (x1 - c.ix) * gc;
+            val[0] = map[o0 + ch];
           }
           if (in[1]) {
             if (!merge) unsafeAtomicAdd(gmap + o0 + C + ch, c.w[1] * gc);
-            const float val = map[o0 + C + ch];
-            gix += val * (y1 - c.iy) * gc;
-            giy -= val * (c.ix - fx) * gc;
+            val[1] = map[o0 + C + ch];
           }
           if (in[2]) {
             if (!merge) unsafeAtomicAdd(gmap + o2 + ch, c.w[2] * gc);
-            const float val = map[o2 + ch];
-            gix -= val * (c.iy - fy) * gc;
-            giy += val * (x1 - c.ix) * gc;
+            val[2] = map[o2 + ch];
           }
           if (in[3]) {
             if (!merge) unsafeAtomicAdd(gmap + o2 + C + ch, c.w[3] * gc);
-            const float val = map[o2 + C + ch];
-            gix += val * (c.iy - fy) * gc;
-            giy += val * (c.ix - fx) * gc;
+            val[3] = map[o2 + C + ch];
           }
+          gix += ((val[1] - val[0]) * (y1 - c.iy) + (val[3] - val[2]) * (c.iy - fy)) * gc;
+          giy += ((val[2] - val[0]) * (x1 - c.ix) + (val[3] - val[1]) * (c.ix - fx)) * gc;
         }
       }
     }
@@ -262,7 +268,7 @@ __global__ __launch_bounds__(256) void sample_uv_bwd_kernel(TexArgs a, int64_t s
         gb[j] = r[2 * j] * du + r[2 * j + 1] * dv;
       }
     }
-    if (ok) {
+    if (live) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) a.gbary[p * 3 + j] = gb[j];
     }
@@ -334,6 +340,7 @@ P3D_API int p3d_sample_uv_forward(const int64_t* pix_to_face, const float* bary,
   a.align = align_corners;
   a.border = padding_mode == P3D_PAD_BORDER;
   a.HWK = HWK;
+  a.F = F;
   hipStream_t s = (hipStream_t)stream;
   int64_t bx = ceil_div(HWK, 256 * 4);
   if (bx > 65535) bx = 65535;
@@ -380,6 +387,7 @@ P3D_API int p3d_sample_uv_backward(const float* grad_texels, const int64_t* pix_
   a.align = align_corners;
   a.border = padding_mode == P3D_PAD_BORDER;
   a.HWK = HWK;
+  a.F = F;
   int64_t waves = ceil_div(HWK, 4096);  // >= 4096 samples per wave amortise the final flush
   if (waves > 4 * 16384) waves = 4 * 16384;
   const int64_t bx = ceil_div(waves, 4);
