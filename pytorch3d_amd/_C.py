@@ -1690,6 +1690,110 @@ def cubify_emit(workspace, shape, coords, feats, total_verts, total_faces):
     return verts, faces, face_feats
 
 
+# ----------------------------------------------------------------------------------------------
+# VolumeSampler (csrc/volume_sample.hip, csrc/implicit_abi.h), behind pytorch3d_amd.volume_sampler.  No `_C` operator of the reference.
+VOLUME_SAMPLE_CALLS = {"atomic": 0, "ordered": 0}  # backwards of the volume gradients by path (tests read it)
+
+
+def _volume_sample_args(who, densities, features, origins, directions, lengths):
+    """(device, Cd, Cf, (D, H, W), N, R, P, shared, contiguous rays) of volumes (Nv, C, D, H, W) with Nv in (1, N) read through
+    their strides (Nv == 1 against N > 1, or a batch stride of 0: one shared grid) and rays (N, R, 3), (N, R, 3), (N, R, P) or None."""
+    named = [("densities", densities), ("origins", origins)] + [(k, v) for k, v in (("features", features), ("directions", directions),
+                                                                                     ("lengths", lengths)) if v is not None]
+    dev = _same_device(*named)
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{who}: {name} must be float32, got {t.dtype}")
+    if origins.dim() != 3 or origins.shape[2] != 3:
+        raise RuntimeError(f"{who}: origins must be (N, R, 3), got {tuple(origins.shape)}")
+    N, R = origins.shape[:2]
+    P = 1
+    if lengths is not None:
+        if directions is None or tuple(directions.shape) != (N, R, 3) or lengths.dim() != 3 or tuple(lengths.shape[:2]) != (N, R):
+            raise RuntimeError(f"{who}: directions (N, R, 3) and lengths (N, R, P) expected with the origins' N and R")
+        P = lengths.shape[2]
+    if densities.dim() != 5 or densities.shape[0] not in (1, N) or densities.shape[1] < 1 or min(densities.shape[2:]) < 1:
+        raise RuntimeError(f"{who}: densities must be (N or 1, Cd >= 1, D, H, W), got {tuple(densities.shape)}")
+    if features is not None and (features.dim() != 5 or features.shape[0] != densities.shape[0] or features.shape[2:] != densities.shape[2:]):
+        raise RuntimeError(f"{who}: features must be (Nv, Cf, D, H, W) over the densities' batch and grid, got {tuple(features.shape)}")
+    shared = N > 1 and densities.shape[0] == 1
+    Cf = 0 if features is None else features.shape[1]
+    rays = (origins.contiguous(), None if lengths is None else directions.contiguous(), None if lengths is None else lengths.contiguous())
+    return dev, densities.shape[1], Cf, tuple(densities.shape[2:]), N, R, P, shared, rays
+
+
+def _volume_strides(t, shared):
+    if t is None or t.numel() == 0:
+        return (0,) * 5
+    return ((0,) if shared or t.shape[0] == 1 else (t.stride(0),)) + tuple(t.stride()[1:])
+
+
+def volume_sample_fits(Nv, D, H, W, N, R, P):
+    """Whether the ordered form's int32 keys cover the sizes (else volume_sample_backward raises NotImplementedError under _ordered())."""
+    return Nv * D * H * W <= MAX_INT and N * R * P <= MAX_INT // 8
+
+
+def volume_sample_forward(densities, features, origins, directions, lengths, flags):
+    """p3di_volume_sample_forward: (rays_densities (N, R, P, Cd), rays_features (N, R, P, Cf)).  lengths None: P = 1, the points are
+    the origins.  The volumes are read in place through their strides."""
+    who = "volume_sample_forward"
+    dev, Cd, Cf, (D, H, W), N, R, P, shared, (o, d, l) = _volume_sample_args(who, densities, features, origins, directions, lengths)
+    with torch.cuda.device(dev):
+        out_d = torch.empty((N, R, P, Cd), dtype=torch.float32, device=dev)
+        out_f = torch.empty((N, R, P, Cf), dtype=torch.float32, device=dev)
+    if N * R * P:
+        _lib.call("p3di_volume_sample_forward", who, dev, densities, _volume_strides(densities, shared), features if Cf else None,
+                  _volume_strides(features, shared), Cd, Cf, D, H, W, o, d, l, N, R, P, flags, out_d, out_f)
+    return out_d, out_f
+
+
+def volume_sample_backward(grad_d, grad_f, densities, features, origins, directions, lengths, flags, need_volumes, need_rays):
+    """(grad_densities, grad_features, grad_origins, grad_directions, grad_lengths), None where not needed: need_volumes = (densities,
+    features), need_rays = (origins, directions, lengths).  grad_d (N, R, P, Cd) / grad_f (N, R, P, Cf) or None (zero).  The volume
+    gradients have the volumes' own shapes ((1, C, D, H, W) for a shared grid) and are float atomics, or under _ordered() the keys /
+    stable sort / segmented sum form, the same bits on every run; there sizes beyond an int32 key raise NotImplementedError and the
+    caller falls back.  The ray gradients are shuffle trees without atomics in both modes."""
+    who = "volume_sample_backward"
+    dev, Cd, Cf, (D, H, W), N, R, P, shared, (o, d, l) = _volume_sample_args(who, densities, features, origins, directions, lengths)
+    for name, g, C in (("grad_rays_densities", grad_d, Cd), ("grad_rays_features", grad_f, Cf)):
+        if g is not None and (g.dtype != torch.float32 or tuple(g.shape) != (N, R, P, C) or g.device != dev):
+            raise RuntimeError(f"{who}: {name} must be float32 ({N}, {R}, {P}, {C}) on {dev}")
+    grad_d = None if grad_d is None else grad_d.contiguous()
+    grad_f = None if grad_f is None or Cf == 0 else grad_f.contiguous()
+    need_d, need_f = bool(need_volumes[0]), bool(need_volumes[1]) and Cf > 0
+    need_o, need_dir, need_l = (bool(x) for x in need_rays)
+    if lengths is None:
+        need_dir = need_l = False
+    strict = _ordered() and (need_d or need_f)
+    if strict and not volume_sample_fits(densities.shape[0], D, H, W, N, R, P):
+        raise NotImplementedError(f"{who}: the deterministic form keys a voxel and a sample by an int32 and the sizes do not fit")
+    with torch.cuda.device(dev):
+        gd = torch.zeros(densities.shape, dtype=torch.float32, device=dev) if need_d else None
+        gf = torch.zeros(features.shape, dtype=torch.float32, device=dev) if need_f else None
+        go = torch.zeros((N, R, 3), dtype=torch.float32, device=dev) if need_o else None
+        gdir = torch.zeros((N, R, 3), dtype=torch.float32, device=dev) if need_dir else None
+        gl = torch.zeros((N, R, P), dtype=torch.float32, device=dev) if need_l else None
+    nothing = grad_d is None and grad_f is None
+    if N * R * P and not nothing and (need_d or need_f or need_o or need_dir or need_l):
+        atomic = not strict
+        vols = (densities, _volume_strides(densities, shared), features if Cf else None, _volume_strides(features, shared))
+        if (atomic and (need_d or need_f)) or need_o or need_dir or need_l:
+            _lib.call("p3di_volume_sample_backward", who, dev, grad_d, grad_f, *vols, Cd, Cf, D, H, W, o, d, l, N, R, P, flags,
+                      gd if atomic else None, _volume_strides(gd, shared), gf if atomic else None, _volume_strides(gf, shared), go, gdir, gl)
+        if strict:
+            with torch.cuda.device(dev):
+                keys = torch.empty((N * R * P * 8,), dtype=torch.int32, device=dev)
+                _lib.call("p3di_volume_sample_keys", who, dev, D, H, W, int(shared), o, d, l, N, R, P, flags, keys)
+                order = _sorted_hits(keys)  # the samples that have a voxel, sorted stably by it (one host sync: the count)
+                nbytes = _lib.load().p3di_volume_sample_workspace_bytes(N, R, P, Cd, Cf)
+                ws = _workspace(nbytes, dev)
+            _lib.call("p3di_volume_sample_ordered_backward", who, dev, grad_d, grad_f, Cd, Cf, D, H, W, int(shared), o, d, l, N, R, P, flags,
+                      keys, order, order.numel(), gd, _volume_strides(gd, shared), gf, _volume_strides(gf, shared), ws, nbytes)
+        if need_d or need_f:
+            VOLUME_SAMPLE_CALLS["ordered" if strict else "atomic"] += 1
+    return gd, gf, go, gdir, gl
+
+
 POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
 # operators both flavours serve through Python wrappers of their own modules (shim.EXPORTS holds the whole table)

@@ -24,6 +24,7 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     vert_align                       image features pooled at the vertices: one launch per map, strided maps, packed rows direct
     cubify, cubify_packed            voxel occupancy grids to merged cube meshes: five launches and one host read, no atomics
     sample_pdf, ea_raymarch, absorption_only_raymarch  hierarchical ray sampling and emission-absorption raymarching, fused, fwd + bwd
+    sample_volumes, volume_sampler_forward  voxel grids sampled along rays (VolumeSampler): one node, both grids in one pass, fwd + bwd
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -48,6 +49,7 @@ from .point_mesh import (edge_point_distance, face_point_distance, point_edge_di
 from .points_normals import (estimate_pointcloud_local_coord_frames, estimate_pointcloud_normals,  # noqa: F401
                              point_covariances)
 from .points_to_volumes import add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  # noqa: F401
+from .volume_sampler import sample_volumes, volume_sampler_forward  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401

@@ -85,6 +85,60 @@ int p3di_cubify_emit(const float* coords, const float* feats, const int64_t feat
                      int64_t W, int64_t total_verts, int64_t total_faces, const void* workspace, size_t workspace_bytes, float* verts,
                      int64_t* faces, float* face_feats, p3d_stream_t stream);
 
+/* VolumeSampler (csrc/volume_sample.hip): steps 2 and 3 of the reference's VolumeSampler.forward (renderer/implicit/renderer.py) in
+ * float32.  densities (N, Cd, D, H, W) and features (N, Cf, D, H, W) -- NULL: Cf = 0 -- are read through five element strides each
+ * (a channel slice or an expand is read in place; a batch stride of 0 is ONE grid shared by the N ray batches).  origins (N, R, 3),
+ * directions (N, R, 3), lengths (N, R, P) contiguous; lengths == NULL: P = 1 and the point is the origin itself, no arithmetic.
+ *   point_k = o + l_k * d, one multiply then one add, no FMA; nothing of shape (N, R, P, 3) is stored.
+ *   F.grid_sample on a 5-D input as ATen defines it: x indexes W, y indexes H, z indexes D; source index of c on an axis of S voxels
+ *   ((c + 1) / 2) * (S - 1) with P3D_VOLUME_SAMPLE_CORNERS, ((c + 1) * S - 1) / 2 without; P3D_VOLUME_SAMPLE_BORDER clamps it to
+ *   [0, S - 1] (NaN -> 0) with a zero coordinate gradient where clamped; bilinear: the corners tnw tne tsw tse bnw bne bsw bse with
+ *   the weights (wx wy) wz, the in-range ones summed in that order from +0; P3D_VOLUME_SAMPLE_NEAREST: round half to even, no
+ *   coordinate gradient.  Under zeros padding a source coordinate that is not finite or does not fit an int32 gives an empty sample.
+ * forward -> rays_densities (N, R, P, Cd), rays_features (N, R, P, Cf) contiguous, every entry written; corners and weights once per
+ *   point for all Cd + Cf channels.
+ * backward: the two output gradients (either may be NULL: zero) -> grad_densities / grad_features through their own strides, ADDED by
+ *   float atomics without return value (the caller zero-fills; a batch stride of 0: every ray batch adds into the one grid), two
+ *   lanes per point so that the voxels of an x pair leave from adjacent lanes; and, each where its pointer is not NULL,
+ *   grad_origins (N, R, 3) = sum_k g_k, grad_directions (N, R, 3) = sum_k l_k g_k, grad_lengths (N, R, P) = g_k . d with g_k the
+ *   coordinate gradient of point k: shuffle trees along the ray with a carry over chunks of 32 points, no atomic, the same bits on
+ *   every run.  With the three NULL the launch reads no volume (a compile-time switch); with both volume gradients NULL it is the
+ *   ray gradients alone.
+ * ordered form: p3di_volume_sample_keys writes keys (N R P 8) int32, sample 8 pt + k -> ((n D + z) H + y) W + x of corner k (n = 0
+ *   for shared != 0) or -1; the caller sorts stably (sorted_samples: n_sorted int64 sample indices in key order; the samples
+ *   with key -1 are best left out, or they form one long segment that a single lane walks) and
+ *   p3di_volume_sample_ordered_backward adds the rows by ordered_sum.h, channels (densities, then features) in chunks of 4, and
+ *   stores every voxel's sum once: the same bits on every run and stream.  workspace: p3di_volume_sample_workspace_bytes (smaller:
+ *   P3D_ERR_WORKSPACE).  (shared ? 1 : N) D H W beyond an int32 or N R P beyond INT32_MAX / 8: P3D_ERR_UNSUPPORTED.
+ * N, R or P of 0: P3D_OK without a launch.  D, H or W below 1, Cd < 1, negative sizes or strides, unknown flags, missing pointers:
+ * P3D_ERR_INVALID_ARG.  No host sync.  The forward and the backward are grid-stride loops of at most P3D_VOLUME_SAMPLE_MAX_GROUPS
+ * workgroups of 256 lanes (the forward over points, the backward over rounds of one wave: 32 / next_pow2(P) rays of P <=
+ * P3D_VOLUME_SAMPLE_CHUNK points, or one longer ray in chunks of that many points). */
+#define P3D_VOLUME_SAMPLE_NEAREST 1
+#define P3D_VOLUME_SAMPLE_BORDER 2
+#define P3D_VOLUME_SAMPLE_CORNERS 4
+#define P3D_VOLUME_SAMPLE_MAX_GROUPS 8192
+#define P3D_VOLUME_SAMPLE_CHUNK 32
+int p3di_volume_sample_forward(const float* densities, const int64_t d_strides[5], const float* features, const int64_t f_strides[5],
+                               int64_t Cd, int64_t Cf, int64_t D, int64_t H, int64_t W, const float* origins, const float* directions,
+                               const float* lengths, int64_t N, int64_t R, int64_t P, unsigned flags, float* rays_densities,
+                               float* rays_features, p3d_stream_t stream);
+int p3di_volume_sample_backward(const float* grad_rays_densities, const float* grad_rays_features, const float* densities,
+                                const int64_t d_strides[5], const float* features, const int64_t f_strides[5], int64_t Cd, int64_t Cf,
+                                int64_t D, int64_t H, int64_t W, const float* origins, const float* directions, const float* lengths,
+                                int64_t N, int64_t R, int64_t P, unsigned flags, float* grad_densities, const int64_t gd_strides[5],
+                                float* grad_features, const int64_t gf_strides[5], float* grad_origins, float* grad_directions,
+                                float* grad_lengths, p3d_stream_t stream);
+size_t p3di_volume_sample_workspace_bytes(int64_t N, int64_t R, int64_t P, int64_t Cd, int64_t Cf);
+int p3di_volume_sample_keys(int64_t D, int64_t H, int64_t W, int64_t shared, const float* origins, const float* directions,
+                            const float* lengths, int64_t N, int64_t R, int64_t P, unsigned flags, int32_t* keys, p3d_stream_t stream);
+int p3di_volume_sample_ordered_backward(const float* grad_rays_densities, const float* grad_rays_features, int64_t Cd, int64_t Cf,
+                                        int64_t D, int64_t H, int64_t W, int64_t shared, const float* origins, const float* directions,
+                                        const float* lengths, int64_t N, int64_t R, int64_t P, unsigned flags, const int32_t* keys,
+                                        const int64_t* sorted_samples, int64_t n_sorted, float* grad_densities, const int64_t gd_strides[5],
+                                        float* grad_features, const int64_t gf_strides[5], void* workspace, size_t workspace_bytes,
+                                        p3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,13 @@ reference classes runs on them end to end:
                                                                  atomics, no cat); the reference's input checks and its density
                                                                  bounds warning stay; CPU tensors, float64 and surface_thickness < 1
                                                                  go to this package's torch formulation of the same chain
+    renderer.implicit.renderer.VolumeSampler.forward          -> pytorch3d_amd.volume_sampler: the reference's checks and its own
+                                                                 world-to-local calls on the Volumes (gradients to translation and
+                                                                 voxel size stay with autograd), then one autograd node over
+                                                                 csrc/volume_sample.hip: ray points in registers, both grids in one
+                                                                 pass, an ordered volume gradient under
+                                                                 torch.use_deterministic_algorithms(True); CPU tensors, float64,
+                                                                 reflection and bicubic go to the reference's chain restated
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -661,6 +668,34 @@ def _raymarchers(ref):
     return {}
 
 
+def _volume_sampler(ref):
+    """VolumeSampler.forward (renderer/implicit/renderer.py) -> pytorch3d_amd.volume_sampler behind the reference's own checks and its
+    own step 1 (Volumes.world_to_local_coords and the module's _get_ray_directions_transform).  There is no `_C` operator under it, so
+    plain install() leaves it alone.  The method is patched directly, as the raymarchers' are; PATCH_CALLS counts kernel calls as fused
+    and the restated chain as fallbacks."""
+    ours = _our("volume_sampler")
+    orig = ref.VolumeSampler.forward
+
+    def forward(self, ray_bundle, **kwargs):
+        origins_world, directions_world, lengths = ray_bundle.origins, ray_bundle.directions, ray_bundle.lengths
+        ref._validate_ray_bundle_variables(origins_world, directions_world, lengths)
+        if self._volumes.densities().shape[0] != origins_world.shape[0]:
+            raise ValueError("Input volumes have to have the same batch size as rays.")
+        origins = self._volumes.world_to_local_coords(origins_world)
+        directions = self._get_ray_directions_transform().transform_points(
+            directions_world.view(lengths.shape[0], -1, 3)).view(directions_world.shape)
+        args = (self._volumes.densities(), self._volumes.features(), origins, directions, lengths)
+        out = ours.sample_volumes(*args, sample_mode=self._sample_mode, padding_mode=self._padding_mode,
+                                  align_corners=self._volumes.get_align_corners())
+        _count("VolumeSampler.forward", ours.kernel_path(*args, self._sample_mode, self._padding_mode))
+        return out
+
+    forward.__name__, forward.__doc__, forward.__wrapped__, forward.__p3d_amd__ = "forward", orig.__doc__, orig, True
+    ref.VolumeSampler.forward = forward
+    _PATCHED.append((ref.VolumeSampler, "forward", orig, forward))
+    return {}
+
+
 def _vert_align(ref):
     """There is no `_C` operator under the reference's function (it is F.grid_sample and copies), so plain install() leaves it alone.
     csrc/vert_align.hip for float32 GPU calls in a mode the kernels cover, the reference's chain restated for the rest."""
@@ -707,6 +742,7 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.vert_align", ("pytorch3d.ops",), _vert_align),
     ("pytorch3d.ops.cubify", ("pytorch3d.ops",), _cubify),
     ("pytorch3d.renderer.implicit.raymarching", (), _raymarchers),
+    ("pytorch3d.renderer.implicit.renderer", (), _volume_sampler),
 )
 
 
