@@ -82,6 +82,8 @@ class _ClipEmit(torch.autograd.Function):
         dev = face_verts.device
         if g_fv is None and g_conv is None:
             return (None,) * 6
+        if ctx.out_shape[0] == 0:  # every face was removed: the output gradients are empty (no pointer to hand to the kernel)
+            return torch.zeros((F, 3, 3), dtype=torch.float32, device=dev), None, None, None, None, None
         if g_fv is None:  # only the conversion matrices fed the loss
             g_fv = torch.zeros(ctx.out_shape, dtype=torch.float32, device=dev)
         g_fv = g_fv.contiguous()
