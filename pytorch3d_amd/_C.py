@@ -1794,6 +1794,87 @@ def volume_sample_backward(grad_d, grad_f, densities, features, origins, directi
     return gd, gf, go, gdir, gl
 
 
+# ----------------------------------------------------------------------------------------------
+# HarmonicEmbedding and the stratified ray depths (csrc/harmonic.hip, csrc/implicit_abi.h), behind pytorch3d_amd.harmonic_embedding and
+# pytorch3d_amd.raysampling.  No `_C` operator of the reference.
+def harmonic_embedding_width(dim, n, append_input):
+    return dim * (2 * n + int(bool(append_input)))
+
+
+def harmonic_embedding_fits(rows, dim, n, append_input):
+    """Whether the entries take the sizes: a row that fits the backward's LDS tile, 32-bit element indices."""
+    W = harmonic_embedding_width(dim, n, append_input)
+    return dim >= 1 and n >= 1 and W <= _lib.HARMONIC_MAX_WIDTH and rows * W <= MAX_INT
+
+
+def harmonic_embedding_backward_tile_rows(W):
+    """Rows of one backward tile at the output width W (implicit_abi.h)."""
+    return min(_lib.HARMONIC_BWD_ROWS, _lib.HARMONIC_BWD_LDS_FLOATS // (W | 1))
+
+
+def _harmonic_args(who, x, diag_cov, frequencies):
+    _need_gpu(x, "x")
+    dev = _same_device(("x", x), ("frequencies", frequencies), *([("diag_cov", diag_cov)] if diag_cov is not None else []))
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous() or x.shape[1] < 1:
+        raise RuntimeError(f"{who}: x must be contiguous float32 (rows, dim) with dim >= 1, got {x.dtype} {tuple(x.shape)}")
+    if frequencies.dim() != 1 or frequencies.dtype != torch.float32 or frequencies.shape[0] < 1 or not frequencies.is_contiguous():
+        raise RuntimeError(f"{who}: frequencies must be contiguous float32 (n,) with n >= 1, got {frequencies.dtype} {tuple(frequencies.shape)}")
+    if diag_cov is not None and (diag_cov.dtype != torch.float32 or diag_cov.shape != x.shape or not diag_cov.is_contiguous()):
+        raise RuntimeError(f"{who}: diag_cov must be contiguous float32 of x's shape, got {diag_cov.dtype} {tuple(diag_cov.shape)}")
+    return dev, x.shape[0], x.shape[1], frequencies.shape[0]
+
+
+def harmonic_embedding_forward(x, diag_cov, frequencies, append_input):
+    """p3di_harmonic_embedding_forward: x (rows, dim), diag_cov of the same shape or None, frequencies (n,) -> (rows, dim (2 n + append))."""
+    who = "harmonic_embedding_forward"
+    dev, rows, dim, n = _harmonic_args(who, x, diag_cov, frequencies)
+    if not harmonic_embedding_fits(rows, dim, n, append_input):
+        raise RuntimeError(f"{who}: {rows} rows of width {harmonic_embedding_width(dim, n, append_input)} are beyond the kernels' sizes")
+    with torch.cuda.device(dev):
+        out = torch.empty((rows, harmonic_embedding_width(dim, n, append_input)), dtype=torch.float32, device=dev)
+    if rows:
+        _lib.call("p3di_harmonic_embedding_forward", who, dev, x, diag_cov, frequencies, rows, dim, n, int(bool(append_input)), out)
+    return out
+
+
+def harmonic_embedding_backward(x, diag_cov, frequencies, grad_out, append_input, need_x=True, need_cov=False):
+    """p3di_harmonic_embedding_backward: (grad_x or None, grad_cov or None), each of x's shape; what is not needed is not computed."""
+    who = "harmonic_embedding_backward"
+    dev, rows, dim, n = _harmonic_args(who, x, diag_cov, frequencies)
+    W = harmonic_embedding_width(dim, n, append_input)
+    if grad_out.dtype != torch.float32 or tuple(grad_out.shape) != (rows, W) or grad_out.device != dev:
+        raise RuntimeError(f"{who}: grad_out must be float32 ({rows}, {W}) on {dev}, got {grad_out.dtype} {tuple(grad_out.shape)} on {grad_out.device}")
+    if not harmonic_embedding_fits(rows, dim, n, append_input):
+        raise RuntimeError(f"{who}: {rows} rows of width {W} are beyond the kernels' sizes")
+    need_cov = bool(need_cov) and diag_cov is not None
+    with torch.cuda.device(dev):
+        gx = torch.empty_like(x) if need_x else None
+        gc = torch.empty_like(x) if need_cov else None
+    if rows and (need_x or need_cov):
+        _lib.call("p3di_harmonic_embedding_backward", who, dev, x, diag_cov, frequencies, grad_out.contiguous(), rows, dim, n,
+                  int(bool(append_input)), gx, gc)
+    return gx, gc
+
+
+def stratified_depths(centers, uniforms):
+    """p3di_stratified_depths: centers (rows, n) float32 with any two strides (an expand is read in place), uniforms (rows, n) -> the
+    jiggled depths (rows, n), contiguous.  uniforms is only read."""
+    who = "stratified_depths"
+    _need_gpu(centers, "centers")
+    dev = _same_device(("centers", centers), ("uniforms", uniforms))
+    if centers.dim() != 2 or centers.dtype != torch.float32 or uniforms.dtype != torch.float32 or uniforms.shape != centers.shape:
+        raise RuntimeError(f"{who}: centers and uniforms must be float32 (rows, n), got {centers.dtype} {tuple(centers.shape)} and "
+                           f"{uniforms.dtype} {tuple(uniforms.shape)}")
+    rows, n = centers.shape
+    if rows * n > MAX_INT:
+        raise RuntimeError(f"{who}: {rows} x {n} is beyond the kernel's int32 indices")
+    with torch.cuda.device(dev):
+        out = torch.empty((rows, n), dtype=torch.float32, device=dev)
+    if rows * n:
+        _lib.call("p3di_stratified_depths", who, dev, centers, centers.stride(), rows, n, uniforms.contiguous(), out)
+    return out
+
+
 POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
 # operators both flavours serve through Python wrappers of their own modules (shim.EXPORTS holds the whole table)

@@ -25,6 +25,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     cubify, cubify_packed            voxel occupancy grids to merged cube meshes: five launches and one host read, no atomics
     sample_pdf, ea_raymarch, absorption_only_raymarch  hierarchical ray sampling and emission-absorption raymarching, fused, fwd + bwd
     sample_volumes, volume_sampler_forward  voxel grids sampled along rays (VolumeSampler): one node, both grids in one pass, fwd + bwd
+    harmonic_embedding, HarmonicEmbedding  the positional encoding of NeRF-style MLPs: one read of x, one write of the embedding, fwd + bwd
+    stratified_depths                one jiggled depth per bin along every ray, the centres read in place (an expand stays an expand)
 
 Importing the package does not load the HIP library; the first operator call does, and raises
 if it is missing (no CPU / eager fallback exists).
@@ -38,6 +40,7 @@ from .cubify import cubify, cubify_packed  # noqa: F401
 from .compositing import alpha_composite, norm_weighted_sum, weighted_sum  # noqa: F401
 from .implicit import absorption_only_raymarch, ea_raymarch, sample_pdf  # noqa: F401
 from .interp_face_attrs import interpolate_face_attributes  # noqa: F401
+from .harmonic_embedding import HarmonicEmbedding, harmonic_embedding, harmonic_embedding_torch  # noqa: F401
 from .graph_conv import gather_scatter, graph_conv, graph_topology, topology_of_edges  # noqa: F401
 from .iou_box3d import box3d_overlap  # noqa: F401
 from .knn import knn_gather, knn_points  # noqa: F401
@@ -50,6 +53,7 @@ from .points_normals import (estimate_pointcloud_local_coord_frames, estimate_po
                              point_covariances)
 from .points_to_volumes import add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  # noqa: F401
 from .volume_sampler import sample_volumes, volume_sampler_forward  # noqa: F401
+from .raysampling import stratified_depths, stratified_depths_torch  # noqa: F401
 from .rasterize_meshes import rasterize_meshes, rasterize_meshes_world  # noqa: F401
 from .rasterize_points import rasterize_points  # noqa: F401
 from .render_points import render_points_alpha  # noqa: F401

@@ -1,4 +1,5 @@
-/* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching) and of csrc/cubify.hip.
+/* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching), csrc/cubify.hip,
+ * csrc/volume_sample.hip and csrc/harmonic.hip (harmonic embedding, stratified ray depths).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -138,6 +139,44 @@ int p3di_volume_sample_ordered_backward(const float* grad_rays_densities, const 
                                         const int64_t* sorted_samples, int64_t n_sorted, float* grad_densities, const int64_t gd_strides[5],
                                         float* grad_features, const int64_t gf_strides[5], void* workspace, size_t workspace_bytes,
                                         p3d_stream_t stream);
+
+/* HarmonicEmbedding (csrc/harmonic.hip): the reference's renderer/implicit/harmonic_embedding.py in float32, formula for formula.
+ * x (rows, dim), diag_cov (rows, dim) or NULL, out (rows, W) with W = dim (2 n + append_input), all contiguous; freqs (n): the module's
+ * _frequencies buffer (omega_0 already in it), any values.  -ffp-contract=off keeps every operation below a rounding of its own:
+ *   t = x[r,i] * f[k];   a_s = t + c_s,  c_0 = 0.0f,  c_1 = float32(0.5 pi) (the reference's _zero_half_pi);
+ *   out[r, (s dim + i) n + k] = sinf(a_s) * e     -- s = 0 the "sin" block, s = 1 the "cos" block = sin(t + pi/2), never cosf(t);
+ *   e = 1 without diag_cov, else expf(-0.5f * (diag_cov[r,i] * (f[k] * f[k])));
+ *   out[r, 2 dim n + i] = x[r,i], append_input only: a copy, bit for bit.
+ * sinf, cosf and expf are the device library's full-range functions.
+ * backward: grad_out (rows, W) -> each where its pointer is not NULL, every entry written,
+ *   grad_x[r,i]   = sum g e f[k] cosf(a_s)   (terms ((g e) f) cos, without diag_cov (g f) cos), then + g of the appended slot;
+ *   grad_cov[r,i] = sum (g sinf(a_s)) (e (-0.5f (f[k] f[k])));
+ * float32 sums from +0 in the fixed order s = 0 then 1, k ascending, the appended slot last; no atomic: the same bits on every run and
+ * stream.  grad_cov without diag_cov: P3D_ERR_INVALID_ARG.
+ * Launches: workgroups of 256 lanes, grid-stride over row tiles, at most P3D_HARMONIC_MAX_GROUPS workgroups.  A forward tile is
+ * P3D_HARMONIC_FWD_ROWS rows, a lane per output element.  A backward tile is min(P3D_HARMONIC_BWD_ROWS, P3D_HARMONIC_BWD_LDS_FLOATS /
+ * (W | 1)) rows of grad_out staged in LDS at the odd row stride W | 1, then a lane per (row, i).
+ * rows == 0: P3D_OK without a launch.  dim < 1, n < 1, append_input outside {0, 1}, W > P3D_HARMONIC_MAX_WIDTH (the widest row of that
+ * LDS tile), rows W > INT32_MAX (the kernels index in 32 bits), missing pointers: P3D_ERR_INVALID_ARG.  No host sync. */
+#define P3D_HARMONIC_FWD_ROWS 64
+#define P3D_HARMONIC_BWD_ROWS 64
+#define P3D_HARMONIC_BWD_LDS_FLOATS 8192
+#define P3D_HARMONIC_MAX_WIDTH 8191
+#define P3D_HARMONIC_MAX_GROUPS 8192
+int p3di_harmonic_embedding_forward(const float* x, const float* diag_cov, const float* freqs, int64_t rows, int64_t dim, int64_t n,
+                                    int64_t append_input, float* out, p3d_stream_t stream);
+int p3di_harmonic_embedding_backward(const float* x, const float* diag_cov, const float* freqs, const float* grad_out, int64_t rows,
+                                     int64_t dim, int64_t n, int64_t append_input, float* grad_x, float* grad_cov, p3d_stream_t stream);
+
+/* Stratified depths (csrc/harmonic.hip): _jiggle_within_stratas of the reference's renderer/implicit/raysampling.py.  centers (rows, n)
+ * float32 read through its two element strides (a stride-0 expand of one linspace is read in place), uniforms and out (rows, n)
+ * contiguous:
+ *   lower = k == 0 ? c[0] : 0.5f * (c[k] + c[k-1]);   upper = k == n - 1 ? c[n-1] : 0.5f * (c[k+1] + c[k]);
+ *   out[r,k] = lower + (upper - lower) * uniforms[r,k]
+ * in IEEE float32 without FMA: given the same uniforms, the bits of the reference's chain on the CPU and on the GPU.  n == 1: c[0] + 0 u.
+ * rows or n of 0: P3D_OK without a launch.  Negative sizes or strides, rows n > INT32_MAX, missing pointers: P3D_ERR_INVALID_ARG. */
+int p3di_stratified_depths(const float* centers, const int64_t strides[2], int64_t rows, int64_t n, const float* uniforms, float* out,
+                           p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

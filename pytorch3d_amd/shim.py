@@ -105,6 +105,13 @@ reference classes runs on them end to end:
                                                                  pass, an ordered volume gradient under
                                                                  torch.use_deterministic_algorithms(True); CPU tensors, float64,
                                                                  reflection and bicubic go to the reference's chain restated
+    renderer.implicit.harmonic_embedding.HarmonicEmbedding.forward -> pytorch3d_amd.harmonic_embedding: one autograd node over
+                                                                 csrc/harmonic.hip on the instance's own buffers (one read of x, one
+                                                                 write of the embedding, a backward without atomics); CPU tensors,
+                                                                 float64 / half and a broadcast diag_cov go to the chain restated
+    renderer.implicit.raysampling._jiggle_within_stratas      -> pytorch3d_amd.raysampling.stratified_depths: the stratified depths of
+                                                                 the three ray samplers in one launch from the reference's own draw
+                                                                 (the same depths under a seed), the expanded linspace read in place
 
 Every replacement falls back to the reference's own function for inputs the fused kernels do not cover (CPU tensors,
 colour widths other than 3, light classes other than Point / Directional / Ambient, padding modes grid_sample has and
@@ -696,6 +703,38 @@ def _volume_sampler(ref):
     return {}
 
 
+def _harmonic_embedding(ref):
+    """HarmonicEmbedding.forward (renderer/implicit/harmonic_embedding.py) -> pytorch3d_amd.harmonic_embedding.module_forward on the
+    instance's own buffers, so implicitron's and the NeRF project's instances are covered.  The method is patched directly, as the
+    raymarchers' are; PATCH_CALLS counts kernel calls as fused and the restated chain as fallbacks."""
+    ours = _our("harmonic_embedding")
+    orig = ref.HarmonicEmbedding.forward
+
+    def forward(self, x, diag_cov=None, **kwargs):
+        out = ours.module_forward(self, x, diag_cov)
+        _count("HarmonicEmbedding.forward", ours.module_path(self, x, diag_cov))
+        return out
+
+    forward.__name__, forward.__doc__, forward.__wrapped__, forward.__p3d_amd__ = "forward", orig.__doc__, orig, True
+    ref.HarmonicEmbedding.forward = forward
+    _PATCHED.append((ref.HarmonicEmbedding, "forward", orig, forward))
+    return {}
+
+
+def _stratified_depths(ref):
+    """_jiggle_within_stratas of renderer/implicit/raysampling.py, the stratified depths of the three ray samplers ->
+    pytorch3d_amd.raysampling.stratified_depths: the expanded linspace is read in place and the depths are written once, from the
+    same draw as the reference's.  The samplers resolve the name in their module at call time."""
+    ours = _our("raysampling")
+
+    def _jiggle_within_stratas(bin_centers):
+        out = ours.stratified_depths(bin_centers)
+        _count("_jiggle_within_stratas", ours.kernel_path(bin_centers))
+        return out
+
+    return {"_jiggle_within_stratas": _jiggle_within_stratas}
+
+
 def _vert_align(ref):
     """There is no `_C` operator under the reference's function (it is F.grid_sample and copies), so plain install() leaves it alone.
     csrc/vert_align.hip for float32 GPU calls in a mode the kernels cover, the reference's chain restated for the rest."""
@@ -743,6 +782,8 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.cubify", ("pytorch3d.ops",), _cubify),
     ("pytorch3d.renderer.implicit.raymarching", (), _raymarchers),
     ("pytorch3d.renderer.implicit.renderer", (), _volume_sampler),
+    ("pytorch3d.renderer.implicit.harmonic_embedding", (), _harmonic_embedding),
+    ("pytorch3d.renderer.implicit.raysampling", (), _stratified_depths),
 )
 
 
