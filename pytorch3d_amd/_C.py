@@ -1691,6 +1691,69 @@ def cubify_emit(workspace, shape, coords, feats, total_verts, total_faces):
 
 
 # ----------------------------------------------------------------------------------------------
+# marching cubes (csrc/marching_cubes.hip, csrc/implicit_abi.h), behind pytorch3d_amd.marching_cubes; the reference's `_C.marching_cubes`
+# is pytorch3d_amd.marching_cubes.marching_cubes_op over these (shim.EXPORTS).
+def marching_cubes_fits(N, D, H, W):
+    """Whether the kernels' int32 indices cover the sizes (else p3di_marching_cubes_count refuses them)."""
+    return min(D, H, W) >= 1 and 15 * max(N, 1) * D * H * W <= 2**31 - 1
+
+
+def marching_cubes_count(vol, isolevels):
+    """p3di_marching_cubes_count: vol (N, D, H, W) float32 on a GPU, any strides, isolevels (N,) float32 -> (workspace, counts (N, 2)
+    int64 = (V_n, F_n)), both on the device and not synchronised.  The workspace goes to marching_cubes_emit unchanged."""
+    who = "marching_cubes_count"
+    dev = _same_device(("vol", vol), ("isolevels", isolevels))
+    if vol.dim() != 4 or vol.dtype != torch.float32:
+        raise RuntimeError(f"{who}: vol must be float32 (N, D, H, W), got {vol.dtype} {tuple(vol.shape)}")
+    N, D, H, W = vol.shape
+    if isolevels.dtype != torch.float32 or isolevels.shape != (N,) or not isolevels.is_contiguous():
+        raise RuntimeError(f"{who}: isolevels must be {N} contiguous float32 values, got {isolevels.dtype} {tuple(isolevels.shape)}")
+    if not marching_cubes_fits(N, D, H, W):
+        raise RuntimeError(f"{who}: {tuple(vol.shape)} is beyond the kernels' int32 indices")
+    nbytes = _lib.load().p3di_marching_cubes_workspace_bytes(N, D, H, W)
+    with torch.cuda.device(dev):
+        ws = _workspace(nbytes, dev)
+        counts = torch.empty((N, 2), dtype=torch.int64, device=dev)
+    _lib.call("p3di_marching_cubes_count", who, dev, vol, vol.stride(), N, D, H, W, isolevels, ws, nbytes, counts)
+    return ws, counts
+
+
+def marching_cubes_emit(workspace, vol, isolevels, local, total_verts, total_faces):
+    """p3di_marching_cubes_emit from marching_cubes_count's workspace and the same vol and isolevels, the totals summed from the counts
+    -> (verts (total_verts, 3) float32, ids (total_verts,) int64, faces (total_faces, 3) int64 with per-volume indices)."""
+    who = "marching_cubes_emit"
+    dev = _same_device(("workspace", workspace), ("vol", vol), ("isolevels", isolevels))
+    N, D, H, W = vol.shape
+    with torch.cuda.device(dev):
+        verts = torch.empty((total_verts, 3), dtype=torch.float32, device=dev)
+        ids = torch.empty((total_verts,), dtype=torch.int64, device=dev)
+        faces = torch.empty((total_faces, 3), dtype=torch.int64, device=dev)
+    if total_faces:
+        _lib.call("p3di_marching_cubes_emit", who, dev, vol, vol.stride(), N, D, H, W, isolevels, int(bool(local)), int(total_verts),
+                  int(total_faces), workspace, workspace.numel(), verts, ids, faces)
+    return verts, ids, faces
+
+
+def marching_cubes_host(vol, isolevel):
+    """p3di_marching_cubes_host: ONE volume (D, H, W) float32 on the CPU, any strides -> (verts (V, 3) float32 in world coordinates,
+    faces (F, 3) int64) by the reference's CPU contract: a counting call, then a writing one."""
+    who = "marching_cubes_host"
+    if vol.is_cuda or vol.dim() != 3 or vol.dtype != torch.float32:
+        raise RuntimeError(f"{who}: vol must be a float32 (D, H, W) CPU tensor, got {vol.dtype} {tuple(vol.shape)} on {vol.device}")
+    D, H, W = vol.shape
+    counts = torch.zeros((2,), dtype=torch.int64)
+    none = torch.empty((0,), dtype=torch.int64)
+    _lib.call("p3di_marching_cubes_host", who, None, vol, vol.stride(), D, H, W, float(isolevel),
+              torch.full((3 * vol.numel(),), -1, dtype=torch.int64), None, 0, none, 0, counts)
+    V, F = (int(c) for c in counts)
+    verts, faces = torch.empty((V, 3), dtype=torch.float32), torch.empty((F, 3), dtype=torch.int64)
+    if F:
+        _lib.call("p3di_marching_cubes_host", who, None, vol, vol.stride(), D, H, W, float(isolevel),
+                  torch.full((3 * vol.numel(),), -1, dtype=torch.int64), verts, V, faces, F, counts)
+    return verts, faces
+
+
+# ----------------------------------------------------------------------------------------------
 # VolumeSampler (csrc/volume_sample.hip, csrc/implicit_abi.h), behind pytorch3d_amd.volume_sampler.  No `_C` operator of the reference.
 VOLUME_SAMPLE_CALLS = {"atomic": 0, "ordered": 0}  # backwards of the volume gradients by path (tests read it)
 

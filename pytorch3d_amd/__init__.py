@@ -23,6 +23,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     gather_scatter, graph_conv, graph_topology  GraphConv's neighbour sums through an inverted index: list order, no atomics, one node
     vert_align                       image features pooled at the vertices: one launch per map, strided maps, packed rows direct
     cubify, cubify_packed            voxel occupancy grids to merged cube meshes: five launches and one host read, no atomics
+    marching_cubes, marching_cubes_packed, marching_cubes_torch  scalar fields to isosurface meshes: four launches and one host read per
+                                     batch, every vertex computed once in the order of the reference's sorted edge ids, no sort, no atomics
     sample_pdf, ea_raymarch, absorption_only_raymarch  hierarchical ray sampling and emission-absorption raymarching, fused, fwd + bwd
     sample_volumes, volume_sampler_forward  voxel grids sampled along rays (VolumeSampler): one node, both grids in one pass, fwd + bwd
     harmonic_embedding, HarmonicEmbedding  the positional encoding of NeRF-style MLPs: one read of x, one write of the embedding, fwd + bwd
@@ -44,6 +46,7 @@ from .harmonic_embedding import HarmonicEmbedding, harmonic_embedding, harmonic_
 from .graph_conv import gather_scatter, graph_conv, graph_topology, topology_of_edges  # noqa: F401
 from .iou_box3d import box3d_overlap  # noqa: F401
 from .knn import knn_gather, knn_points  # noqa: F401
+from .marching_cubes import marching_cubes, marching_cubes_packed, marching_cubes_torch  # noqa: F401
 from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
                           mesh_normal_consistency)
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401

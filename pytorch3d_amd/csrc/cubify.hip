@@ -23,6 +23,7 @@
 // The host reads the (N, 2) counts between the two entries, sizes the outputs and calls emit: the one sync of a call.
 #include "implicit_abi.h"
 #include "p3d_common.h"
+#include "scan_blocks.h"
 
 namespace p3d {
 namespace {
@@ -70,35 +71,6 @@ Workspace carve(void* workspace, int64_t N, const Sizes& s) {
   w.carry_v = a.take<int>((size_t)(N * s.bpm_v + 1));
   w.bytes = a.off;
   return w;
-}
-
-// The exclusive scan of x over the workgroup's WAVES waves, and its total.  wsum: WAVES ints of LDS, free again on return.
-template <int WAVES>
-__device__ __forceinline__ int block_exclusive(int wave_exclusive, int wave_total, int* wsum, int* total) {
-  const int wave = (int)threadIdx.x / kWave;
-  if (lane_id() == 0) wsum[wave] = wave_total;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int i = 0; i < WAVES; ++i) {
-    const int t = wsum[i];
-    before += i < wave ? t : 0;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + wave_exclusive;
-}
-
-// inclusive Hillis-Steele scan over the wave
-__device__ __forceinline__ int wave_inclusive(int x) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const int y = __shfl_up(x, o);
-    if (lane >= o) x += y;
-  }
-  return x;
 }
 
 __device__ __forceinline__ bool occupied(const float* p, float thresh) { return *p >= thresh; }  // NaN: false
@@ -161,27 +133,6 @@ __global__ __launch_bounds__(kLanes) void vertex_kernel(const uint8_t* __restric
     running += total;
   }
   if (threadIdx.x == 0) sums[blockIdx.x] = running;
-}
-
-// grid: 2 blocks.  Block 0 scans the face table (column 1 of counts), block 1 the vertex table (column 0).
-__global__ __launch_bounds__(kCarryLanes) void carry_kernel(int* carry_f, int nb_f, int bpm_f, int* carry_v, int nb_v, int bpm_v, int N,
-                                                            int64_t* __restrict__ counts) {
-  __shared__ int wsum[kCarryLanes / kWave];
-  int* a = blockIdx.x ? carry_v : carry_f;
-  const int nb = blockIdx.x ? nb_v : nb_f, bpm = blockIdx.x ? bpm_v : bpm_f, col = blockIdx.x ? 0 : 1;
-  int running = 0;
-  for (int base = 0; base < nb; base += kCarryLanes) {
-    const int i = base + (int)threadIdx.x;
-    const int x = i < nb ? a[i] : 0;
-    const int incl = wave_inclusive(x);
-    int total;
-    const int ex = running + block_exclusive<kCarryLanes / kWave>(incl - x, __shfl(incl, kWave - 1), wsum, &total);
-    if (i < nb) a[i] = ex;
-    running += total;
-  }
-  if (threadIdx.x == 0) a[nb] = running;
-  __syncthreads();  // the table was written by this workgroup: visible to it behind the barrier
-  for (int n = (int)threadIdx.x; n < N; n += kCarryLanes) counts[2 * n + col] = (int64_t)(a[(n + 1) * bpm] - a[n * bpm]);
 }
 
 // corners of the twelve triangles, two per direction in the mask's bit order
@@ -286,7 +237,7 @@ P3D_API int p3di_cubify_count(const float* voxels, const int64_t voxel_strides[4
                                                               w.masks, w.carry_f);
   vertex_kernel<<<(unsigned)(N * s.bpm_v), kLanes, 0, st>>>(w.masks, (int)D, (int)H, (int)W, (int)s.M, (int)s.L, (int)s.bpm_v, w.local,
                                                             w.carry_v);
-  carry_kernel<<<2, kCarryLanes, 0, st>>>(w.carry_f, (int)(N * s.bpm_f), (int)s.bpm_f, w.carry_v, (int)(N * s.bpm_v), (int)s.bpm_v, (int)N,
+  carry_kernel<kCarryLanes><<<2, kCarryLanes, 0, st>>>(w.carry_f, (int)(N * s.bpm_f), (int)s.bpm_f, w.carry_v, (int)(N * s.bpm_v), (int)s.bpm_v, (int)N,
                                           counts);
   return launch_status();
 }

@@ -178,6 +178,50 @@ int p3di_harmonic_embedding_backward(const float* x, const float* diag_cov, cons
 int p3di_stratified_depths(const float* centers, const int64_t strides[2], int64_t rows, int64_t n, const float* uniforms, float* out,
                            p3d_stream_t stream);
 
+/* Marching cubes (csrc/marching_cubes.hip): scalar fields vol (N, D, H, W), float32 read through vol_strides (in elements: a channel
+ * slice or a permuted view is read in place), to the isosurface meshes of the reference's pytorch3d/ops/marching_cubes.py.  x runs
+ * along W, y along H, z along D; lattice point g = (z H + y) W + x; isolevels: N floats, one per volume.
+ *   inside      a lattice point is inside iff its value < the isolevel, strictly; NaN: outside.
+ *   cubes       the (D-1)(H-1)(W-1) cubes in the order of their low corner g.  Corner i of a cube is its low corner moved by
+ *               (i & 1, i >> 1 & 1, i >> 2 & 1); the configuration byte has bit i set iff corner i is inside.  The triangles of a
+ *               configuration are the rows of csrc/marching_cubes_tables.h: up to 15 entries 8 axis + corner, the edge that runs from
+ *               `corner` one step along axis (0 = x, 1 = y, 2 = z).  The edges a configuration names are the edges whose ends differ.
+ *   vertex      on the edge from p1 (value v1) to p2 (value v2), eps = 1e-5f: p1 if |iso - v1| < eps, else p2 if |iso - v2| < eps, else
+ *               p1 if |v1 - v2| < eps, else with r = (iso - v1) / (v2 - v1) every coordinate p1 (1 - r) + p2 r -- products and sum
+ *               rounded one by one, the two coordinates that do not vary included (csrc/marching_cubes_geom.h).
+ * The DEVICE contract (what the reference returns for GPU tensors after its dedup) -- p3di_marching_cubes_count / _emit:
+ *   a lattice edge carries a vertex iff its ends differ; it belongs to its LOW lattice point.  The vertices of a volume are in the order
+ *   of (g, axis); every table triangle is kept, degenerate ones too; faces hold the per-volume vertex ranks (int64), cubes in g order,
+ *   table order inside a cube; ids[v] = g (W + W H + W H D) + g', g' the edge's high lattice point: strictly ascending per volume.
+ *   count: fills the workspace (a word per lattice point: the rank of its first vertex inside its scan block, its three edge flags and
+ *     its cube's configuration byte; and the exclusive scans of the vertex and triangle totals of every scan block of
+ *     P3D_MARCHING_CUBES_ITEMS lattice points -- a scan block never spans two volumes) and writes counts (N, 2) int64 = (V_n, F_n).
+ *     Two launches: a lane per lattice point in rounds of P3D_MARCHING_CUBES_BLOCK, then two workgroups of
+ *     P3D_MARCHING_CUBES_CARRY_BLOCK lanes over the block totals in rounds.  No workgroup waits for another.
+ *   emit: from that workspace, unchanged, and the same vol and isolevels, on the same stream: verts (total_verts, 3) float32 -- world
+ *     coordinates, or with local != 0 each coordinate c / ((size - 1) / 2) - 1 --, ids (total_verts) int64 and faces (total_faces, 3)
+ *     int64.  total_verts and total_faces must be the sums of the counts.  Two launches, a lane per lattice point each; the table is
+ *     staged in LDS.
+ *   workspace: p3di_marching_cubes_workspace_bytes(N, D, H, W) bytes, about 4 per lattice point; 0 for sizes the entries refuse.
+ *   No atomic; the same bits on every run and stream.  N == 0, or no cube (a dimension of 1): count writes zeros, without a scan.
+ *   A dimension below 1, negative sizes, missing pointers, 15 N D H W beyond INT32_MAX: P3D_ERR_INVALID_ARG.  No host sync.
+ * The CPU contract (what the reference's compiled CPU operator returns) -- p3di_marching_cubes_host, ONE volume (D, H, W) on host
+ * pointers: cubes in the same order; a triangle of which two vertices are closer than 1e-5 in every coordinate is dropped, AND every
+ *   later triangle of the same cube with it; the vertices of the kept triangles in order of first use, one per lattice edge.
+ *   edge_rank: 3 D H W int64 the caller filled with -1 (scratch).  verts (cap_verts, 3) and faces (cap_faces, 3) are written as far as
+ *   the capacities reach (both may be NULL with capacity 0: a counting call); counts[2] = (V, F) always. */
+#define P3D_MARCHING_CUBES_BLOCK 256
+#define P3D_MARCHING_CUBES_ITEMS 2048
+#define P3D_MARCHING_CUBES_CARRY_BLOCK 1024
+size_t p3di_marching_cubes_workspace_bytes(int64_t N, int64_t D, int64_t H, int64_t W);
+int p3di_marching_cubes_count(const float* vol, const int64_t vol_strides[4], int64_t N, int64_t D, int64_t H, int64_t W,
+                              const float* isolevels, void* workspace, size_t workspace_bytes, int64_t* counts, p3d_stream_t stream);
+int p3di_marching_cubes_emit(const float* vol, const int64_t vol_strides[4], int64_t N, int64_t D, int64_t H, int64_t W,
+                             const float* isolevels, int64_t local, int64_t total_verts, int64_t total_faces, const void* workspace,
+                             size_t workspace_bytes, float* verts, int64_t* ids, int64_t* faces, p3d_stream_t stream);
+int p3di_marching_cubes_host(const float* vol, const int64_t vol_strides[3], int64_t D, int64_t H, int64_t W, float isolevel,
+                             int64_t* edge_rank, float* verts, int64_t cap_verts, int64_t* faces, int64_t cap_faces, int64_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

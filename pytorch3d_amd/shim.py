@@ -19,7 +19,9 @@ And `_C.iou_box3d` (csrc/box3d.hip: the kernels for GPU tensors, the library's h
 `pytorch3d.ops.box3d_overlap` runs on both.  And `_C.gather_scatter` (csrc/graph_conv.hip): the unmodified `pytorch3d.ops.GraphConv`
 runs on the GPU, forward and backward, its neighbour sums added in list order instead of by float atomics.  And `_C.sample_pdf`
 (csrc/implicit.hip: the kernel for GPU tensors, the library's host loop for CPU tensors, the same bits from both): the unmodified
-`pytorch3d.renderer.implicit.sample_pdf` runs on both.
+`pytorch3d.renderer.implicit.sample_pdf` runs on both.  And `_C.marching_cubes` (csrc/marching_cubes.hip for a GPU volume: every vertex
+once, with strictly ascending edge ids, so that the wrapper's torch.unique is the identity; the library's host loop for a CPU volume):
+the unmodified `pytorch3d.ops.marching_cubes` runs on both, volume by volume.
 
     shim.install(patch_python=True)
 
@@ -92,6 +94,12 @@ reference classes runs on them end to end:
                                                                  (csrc/vert_align.hip); an ordered grad_feats under
                                                                  torch.use_deterministic_algorithms(True)
 
+    ops.marching_cubes.marching_cubes                         -> pytorch3d_amd.marching_cubes.marching_cubes: the whole batch in four
+                                                                 launches and one host read (the reference: three reads and a
+                                                                 torch.unique per volume), isolevel=None included; CPU volumes go
+                                                                 to the library's host loop, GPU sizes beyond int32 to this
+                                                                 package's torch formulation
+
     renderer.implicit.raymarching.EmissionAbsorptionRaymarcher.forward / AbsorptionOnlyRaymarcher.forward
                                                               -> pytorch3d_amd.implicit: one autograd node over csrc/implicit.hip's
                                                                  forward and backward kernels (scans along the ray, no division, no
@@ -149,6 +157,7 @@ EXPORTS = {
     "iou_box3d": ("iou_box3d", "iou_box3d_op"),  # csrc/box3d.hip; the library's host loop for CPU boxes
     "gather_scatter": ("graph_conv", "gather_scatter_op"),  # csrc/graph_conv.hip; the table of an edge tensor is cached
     "sample_pdf": ("implicit", "sample_pdf_op"),  # csrc/implicit.hip; the library's host loop for CPU tensors; in place
+    "marching_cubes": ("marching_cubes", "marching_cubes_op"),  # csrc/marching_cubes.hip; the library's host loop for CPU volumes
 }
 
 
@@ -763,6 +772,20 @@ def _cubify(ref):
     return {"cubify": cubify}
 
 
+def _marching_cubes(ref):
+    """pytorch3d.ops.marching_cubes (a Python loop over the volumes, each with `_C.marching_cubes`, three host reads and a torch.unique
+    on the GPU) -> pytorch3d_amd.marching_cubes: the batch at once.  The reference's pytorch3d.ops does not copy this name (there
+    `marching_cubes` is the module); _replace_everywhere rebinds it in the module and in every loaded module that did copy it."""
+    ours = _our("marching_cubes")
+
+    def marching_cubes(vol_batch, isolevel=None, return_local_coords=True):
+        out = ours.marching_cubes(vol_batch, isolevel, return_local_coords)
+        _count("marching_cubes", ours.kernel_path(vol_batch))
+        return out
+
+    return {"marching_cubes": marching_cubes}
+
+
 # (reference module, the packages that copied its names, its replacements), in the order they are applied
 _FUNCTION_PATCHES = (
     ("pytorch3d.loss.mesh_edge_loss", ("pytorch3d.loss",), _mesh_loss),
@@ -780,6 +803,7 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.graph_conv", ("pytorch3d.ops",), _graph_conv),
     ("pytorch3d.ops.vert_align", ("pytorch3d.ops",), _vert_align),
     ("pytorch3d.ops.cubify", ("pytorch3d.ops",), _cubify),
+    ("pytorch3d.ops.marching_cubes", ("pytorch3d.ops",), _marching_cubes),
     ("pytorch3d.renderer.implicit.raymarching", (), _raymarchers),
     ("pytorch3d.renderer.implicit.renderer", (), _volume_sampler),
     ("pytorch3d.renderer.implicit.harmonic_embedding", (), _harmonic_embedding),
