@@ -1938,6 +1938,94 @@ def stratified_depths(centers, uniforms):
     return out
 
 
+# ----------------------------------------------------------------------------------------------
+# iterative_closest_point / corresponding_points_alignment (csrc/points_alignment.hip, the contract: csrc/implicit_abi.h), behind
+# pytorch3d_amd.points_alignment.  The reference has no compiled operator of this kind: nothing here is an export of the shim module.
+def points_alignment_fits(N, P1, P2):
+    """Whether the entries take clouds of these sizes (their indices are int32 per cloud, their grid N ceil(P1 / 64) workgroups)."""
+    return 0 < N <= MAX_INT and 0 < P1 <= MAX_INT and 0 <= P2 <= MAX_INT and N * ((P1 + 63) // 64) <= MAX_INT
+
+
+def _align_clouds(who, X, Y, *lengths):
+    dev = _same_device(("X", X), ("Y", Y))
+    if X.dim() != 3 or Y.dim() != 3 or X.shape[2] != 3 or Y.shape[2] != 3 or X.shape[0] != Y.shape[0]:
+        raise RuntimeError(f"{who}: the kernels take X (N, P1, 3) and Y (N, P2, 3), got {tuple(X.shape)} and {tuple(Y.shape)}; "
+                           "pytorch3d_amd.points_alignment has a torch formulation for the rest")
+    if not points_alignment_fits(X.shape[0], X.shape[1], Y.shape[1]):
+        raise RuntimeError(f"{who}: clouds of {tuple(X.shape)} and {tuple(Y.shape)} are empty or beyond the kernels' int32 indices")
+    names = ("lengths1", "lengths2", "mask_len")
+    return (dev, _c(X, torch.float32), _c(Y, torch.float32)) + tuple(_int64_arg(t, X.shape[0], dev, names[k], who) for k, t in enumerate(lengths))
+
+
+def _align_transform(who, R, T, s, N, dev):
+    if R is None and T is None and s is None:
+        return None, None, None
+    if R is None or T is None or s is None or R.shape != (N, 3, 3) or T.shape != (N, 3) or s.shape != (N,):
+        raise RuntimeError(f"{who}: R (N, 3, 3), T (N, 3) and s (N,) come together")
+    _same_device(("R", R), ("T", T), ("s", s))
+    if R.device != dev:
+        raise RuntimeError(f"Expected all tensors to be on the same GPU, but R is on {R.device} and X is on {dev}")
+    return _c(R, torch.float32), _c(T, torch.float32), _c(s, torch.float32)
+
+
+def _align_flags(estimate_scale, allow_reflection):
+    return (_lib.ALIGN_ESTIMATE_SCALE if estimate_scale else 0) | (_lib.ALIGN_ALLOW_REFLECTION if allow_reflection else 0)
+
+
+def icp_workspace(N, P1, device):
+    """(workspace, its bytes) of the three entries for clouds of (N, P1) rows: one allocation serves every iteration of a call."""
+    nbytes = _lib.load().p3di_icp_workspace_bytes(N, P1)
+    return _workspace(nbytes, device), nbytes
+
+
+def icp_match(X, Y, lengths1=None, lengths2=None, R=None, T=None, s=None, split=0):
+    """p3di_icp_match: idx (N, P1) int64, the nearest point of Y[n, :lengths2[n]] to s * (X[n, i] R) + T (to X[n, i] itself without a
+    transform): knn_points_idx(K=1)'s indices on the transformed points.  split: waves per workgroup, 0 (the launch decides), 1, 2, 4, 8."""
+    who = "icp_match"
+    dev, X, Y, lengths1, lengths2 = _align_clouds(who, X, Y, lengths1, lengths2)
+    N, P1, _ = X.shape
+    R, T, s = _align_transform(who, R, T, s, N, dev)
+    idx = torch.empty((N, P1), dtype=torch.int64, device=dev)
+    ws, nbytes = icp_workspace(N, P1, dev)
+    _lib.call("p3di_icp_match", who, dev, X, Y, lengths1, lengths2, R, T, s, N, P1, Y.shape[1], int(split), idx, ws, nbytes)
+    return idx
+
+
+def icp_iteration(workspace, X, Y, lengths1, lengths2, mask_len, transform, rmse_prev, split, estimate_scale, allow_reflection,
+                  relative_rmse_thr, R_out, T_out, s_out, idx, Xt, rmse, status):
+    """p3di_icp_iteration on buffers of the caller (pytorch3d_amd.points_alignment holds them for the whole call): six launches, no
+    host read.  workspace: icp_workspace's pair; transform: (R, T, s) or None (X as given); rmse_prev None: the first iteration."""
+    who = "iterative_closest_point"
+    N, P1, _ = X.shape
+    R, T, s = transform if transform is not None else (None, None, None)
+    _lib.call("p3di_icp_iteration", who, X.device, X, Y, lengths1, lengths2, mask_len, R, T, s, rmse_prev, N, P1, Y.shape[1], int(split),
+              _align_flags(estimate_scale, allow_reflection), float(relative_rmse_thr), R_out, T_out, s_out, idx, Xt, rmse, status,
+              workspace[0], workspace[1])
+
+
+def points_alignment(X, Y, mask_len, weights, estimate_scale, allow_reflection, eps):
+    """p3di_points_alignment: (R (N, 3, 3), T (N, 3), s (N,), status (2,) int32 on the device -- status[1]: some singular value
+    <= 1e-15) of corresponding rows of X and Y (N, P, 3).  mask_len (N,) int64 or None, weights (N, P) float32 or None."""
+    who = "corresponding_points_alignment"
+    dev, X, Y, mask_len = _align_clouds(who, X, Y, mask_len)
+    if X.shape != Y.shape:
+        raise RuntimeError(f"{who}: X and Y must have one shape, got {tuple(X.shape)} and {tuple(Y.shape)}")
+    N, P, _ = X.shape
+    if weights is not None:
+        _same_device(("X", X), ("weights", weights))
+        if weights.shape != (N, P):
+            raise RuntimeError(f"{who}: weights must have shape (N, P)")
+        weights = _c(weights, torch.float32)
+    R = torch.empty((N, 3, 3), dtype=torch.float32, device=dev)
+    T = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    s = torch.empty((N,), dtype=torch.float32, device=dev)
+    status = torch.zeros((2,), dtype=torch.int32, device=dev)
+    ws, nbytes = icp_workspace(N, P, dev)
+    _lib.call("p3di_points_alignment", who, dev, X, Y, mask_len, weights, N, P, _align_flags(estimate_scale, allow_reflection), float(eps),
+              R, T, s, status, ws, nbytes)
+    return R, T, s, status
+
+
 POINT_MESH_EXPORTS = ("point_face_dist_forward", "point_face_dist_backward", "face_point_dist_forward", "face_point_dist_backward",
                       "point_edge_dist_forward", "point_edge_dist_backward", "edge_point_dist_forward", "edge_point_dist_backward")
 # operators both flavours serve through Python wrappers of their own modules (shim.EXPORTS holds the whole table)

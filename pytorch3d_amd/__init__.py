@@ -28,6 +28,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     sample_pdf, ea_raymarch, absorption_only_raymarch  hierarchical ray sampling and emission-absorption raymarching, fused, fwd + bwd
     sample_volumes, volume_sampler_forward  voxel grids sampled along rays (VolumeSampler): one node, both grids in one pass, fwd + bwd
     harmonic_embedding, HarmonicEmbedding  the positional encoding of NeRF-style MLPs: one read of x, one write of the embedding, fwd + bwd
+    iterative_closest_point, corresponding_points_alignment, apply_similarity_transform  rigid / similarity registration of point
+                                     clouds: six launches and one 4-byte host read per ICP iteration, the 3 x 3 SVD in float64 on the device
     stratified_depths                one jiggled depth per bin along every ray, the centres read in place (an expand stays an expand)
 
 Importing the package does not load the HIP library; the first operator call does, and raises
@@ -52,6 +54,9 @@ from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_to
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
 from .point_mesh import (edge_point_distance, face_point_distance, point_edge_distance, point_face_distance,  # noqa: F401
                          point_mesh_edge_distance, point_mesh_face_distance)
+from .points_alignment import (ICPSolution, SimilarityTransform, apply_similarity_transform,  # noqa: F401
+                               corresponding_points_alignment, corresponding_points_alignment_torch, iterative_closest_point,
+                               iterative_closest_point_torch)
 from .points_normals import (estimate_pointcloud_local_coord_frames, estimate_pointcloud_normals,  # noqa: F401
                              point_covariances)
 from .points_to_volumes import add_pointclouds_to_volumes, add_points_features_to_volume_densities_features  # noqa: F401

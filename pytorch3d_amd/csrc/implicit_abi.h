@@ -1,5 +1,6 @@
 /* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching), csrc/cubify.hip,
- * csrc/volume_sample.hip and csrc/harmonic.hip (harmonic embedding, stratified ray depths).
+ * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip and
+ * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -221,6 +222,54 @@ int p3di_marching_cubes_emit(const float* vol, const int64_t vol_strides[4], int
                              size_t workspace_bytes, float* verts, int64_t* ids, int64_t* faces, p3d_stream_t stream);
 int p3di_marching_cubes_host(const float* vol, const int64_t vol_strides[3], int64_t D, int64_t H, int64_t W, float isolevel,
                              int64_t* edge_rank, float* verts, int64_t cap_verts, int64_t* faces, int64_t cap_faces, int64_t* counts);
+
+/* Points alignment (csrc/points_alignment.hip): the reference's pytorch3d/ops/points_alignment.py on padded float32 clouds of dimension
+ * 3.  X (N, P1, 3), Y (N, P2, 3) contiguous; lengths1 / lengths2 (N) int64 or NULL (full; clamped into [0, P]); R (N, 3, 3), T (N, 3),
+ * s (N): the similarity transform  Xt = s * (x R) + T  of a ROW vector, formed as s * ((x0 R[0][k] + x1 R[1][k]) + x2 R[2][k]) + T[k], every
+ * operation a float32 rounding of its own.
+ *   weights   the weight of row i of cloud n is (mask_len == NULL or i < mask_len[n] ? 1 : 0) * (weights == NULL ? 1 : weights[n, i]).
+ *             With neither (`uniform`) the means are plain means over the P1 rows and the total weight is clamp(P1, 1); else the means
+ *             are sum(w x) / clamp(sum w, eps) and the total weight clamp(sum w, eps) -- the reference's two forms.
+ *   moments   Xc = (x - Xmu) w, Yc = (y - Ymu) w (uniform: no w): the weight enters every product squared, as in the reference.
+ *             XYcov = sum Xc^T Yc / total, Xcov = sum Xc . Xc / total, float32.
+ *   solve     float64 on the float32 XYcov: XYcov = U diag(sigma) V^T, sigma descending; R = U diag(1, 1, e) V^T with e = det(U V^T), or
+ *             e = 1 with P3D_ALIGN_ALLOW_REFLECTION; s = (sigma1 + sigma2 + e sigma3) / clamp(Xcov, eps) with P3D_ALIGN_ESTIMATE_SCALE,
+ *             else 1; T = Ymu - s Xmu R.  Each result is rounded to float32 once.  A zero covariance gives R = I.  status[1] is set to 1
+ *             where some sigma <= 1e-15 and is never cleared: the caller zeroes status before its first call.
+ *   sums      every per-cloud sum is csrc/fixed_sum.h's tree over the partials of waves of 64 consecutive rows: no atomic, the same
+ *             bits on every run, stream and process.
+ * p3di_points_alignment: corresponding_points_alignment -- y of row i is row i of Y (P2 = P1 = P).  Four launches.
+ * p3di_icp_match: idx[n, i] (int64) = the nearest point of Y[n, :lengths2[n]] to Xt[n, i] (to x itself where R, T, s are NULL, all three)
+ *   by squared distance ((dx dx + dy dy) + dz dz, unfused) in the order (dist, j): what p3d_knn_points_forward returns for K = 1 and
+ *   norm 2 on the transformed points, bit for bit; 0 in the rows past lengths1[n], where the cloud of Y is empty, and for a row
+ *   no point of Y has a distance below +inf to.  A workgroup is 64 rows and `split` waves, each scanning a slice of ceil(lengths2 /
+ *   split) points of Y in LDS tiles of P3D_KNN_TILE; split in {1, 2, 4, 8}, or 0: doubled while N ceil(P1 / 64) split stays within
+ *   the chip's SIMDs and split within ceil(P2 / P3D_KNN_TILE).  The result does not depend on it.
+ * p3di_icp_iteration: one iteration of iterative_closest_point, six launches:  match with (R_in, T_in, s_in) (NULL: X as given);
+ *   the alignment of X with its neighbours under the weights of mask_len -> (R_out, T_out, s_out);  Xt (N, P1, 3) = X under the new
+ *   transform;  rmse[n] = sqrt(sum w |Xt - y|^2 / clamp(sum w, 1e-9)) with the neighbours of the match;  relative = (rmse_prev[n] -
+ *   rmse[n]) / rmse_prev[n], an IEEE float32 quotient (0 / 0: NaN), or 1 where rmse_prev is NULL -- the FIRST iteration, which also
+ *   computes Xmu into the workspace, where the later iterations of the call find it: the same workspace, untouched in between;
+ *   status[0] = 1 if relative <= relative_rmse_thr in every cloud, else 0.  A row past lengths1[n] that mask_len does not mask keeps
+ *   its weight and is paired with Y[n, 0]: the reference's mask rule.  eps is the reference's 1e-9.
+ * workspace: p3di_icp_workspace_bytes(N, P1) bytes for all three (smaller, or NULL: P3D_ERR_WORKSPACE); 0 for sizes the entries refuse.
+ * N P1 == 0: P3D_OK without a launch for match; P3D_ERR_INVALID_ARG for the other two (there is nothing to align: the caller answers).
+ * Negative sizes, N, P1 or P2 beyond INT32_MAX, a split outside {0, 1, 2, 4, 8}, unknown flags, missing pointers, some but not all
+ * of R, T, s: P3D_ERR_INVALID_ARG.  No host sync. */
+#define P3D_ICP_MAX_SPLIT 8
+#define P3D_ALIGN_ESTIMATE_SCALE 1
+#define P3D_ALIGN_ALLOW_REFLECTION 2
+size_t p3di_icp_workspace_bytes(int64_t N, int64_t P1);
+int p3di_icp_match(const float* X, const float* Y, const int64_t* lengths1, const int64_t* lengths2, const float* R, const float* T,
+                   const float* s, int64_t N, int64_t P1, int64_t P2, int split, int64_t* idx, void* workspace, size_t workspace_bytes,
+                   p3d_stream_t stream);
+int p3di_icp_iteration(const float* X, const float* Y, const int64_t* lengths1, const int64_t* lengths2, const int64_t* mask_len,
+                       const float* R_in, const float* T_in, const float* s_in, const float* rmse_prev, int64_t N, int64_t P1, int64_t P2,
+                       int split, unsigned flags, float relative_rmse_thr, float* R_out, float* T_out, float* s_out, int64_t* idx,
+                       float* Xt, float* rmse, int32_t* status, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+int p3di_points_alignment(const float* X, const float* Y, const int64_t* mask_len, const float* weights, int64_t N, int64_t P,
+                          unsigned flags, float eps, float* R, float* T, float* s, int32_t* status, void* workspace,
+                          size_t workspace_bytes, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

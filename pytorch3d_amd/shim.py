@@ -83,6 +83,10 @@ reference classes runs on them end to end:
                                                                  estimate_normals comes here through `ops`; K > 64, float64, CPU
                                                                  tensors, eigh and inputs that require grad go to this package's
                                                                  torch formulation
+    ops.points_alignment.iterative_closest_point / corresponding_points_alignment -> csrc/points_alignment.hip: per ICP iteration six
+                                                                 launches and one 4-byte host read, the 3 x 3 SVD in float64 on
+                                                                 the device; CPU tensors, float64, d != 3 and inputs that require
+                                                                 grad go to this package's restated chain
     ops.iou_box3d.box3d_overlap                               -> pytorch3d_amd.iou_box3d.box3d_overlap: the same operator (csrc/box3d.hip)
                                                                  behind input checks that cost one host sync instead of four
     ops.graph_conv.GraphConv.forward, ops.graph_conv.gather_scatter
@@ -786,6 +790,31 @@ def _marching_cubes(ref):
     return {"marching_cubes": marching_cubes}
 
 
+def _points_alignment(ref):
+    """pytorch3d.ops.iterative_closest_point / corresponding_points_alignment (per iteration a knn_points call, a chain of several dozen
+    small launches around torch.svd and three host reads) -> pytorch3d_amd.points_alignment: six launches and one 4-byte read per
+    iteration for float32 GPU clouds of dimension 3 without a gradient, the package's restated chain for the rest.  The results are
+    the reference's own ICPSolution / SimilarityTransform classes; a Pointclouds input gets its Xt through update_padded."""
+    ours = _our("points_alignment")
+
+    def iterative_closest_point(X, Y, init_transform=None, max_iterations=100, relative_rmse_thr=1e-6, estimate_scale=False,
+                                allow_reflection=False, verbose=False):
+        fused = ours.kernel_path(X, Y, None, init_transform) and int(max_iterations) > 0
+        out = ours.iterative_closest_point(X, Y, init_transform, max_iterations, relative_rmse_thr, estimate_scale, allow_reflection,
+                                           verbose)
+        _count("iterative_closest_point", fused)
+        return ref.ICPSolution(out.converged, out.rmse, out.Xt, ref.SimilarityTransform(*out.RTs),
+                               [ref.SimilarityTransform(*t) for t in out.t_history])
+
+    def corresponding_points_alignment(X, Y, weights=None, estimate_scale=False, allow_reflection=False, eps=1e-9):
+        fused = ours.kernel_path(X, Y, weights)
+        out = ours.corresponding_points_alignment(X, Y, weights, estimate_scale, allow_reflection, eps)
+        _count("corresponding_points_alignment", fused)
+        return ref.SimilarityTransform(*out)
+
+    return {"iterative_closest_point": iterative_closest_point, "corresponding_points_alignment": corresponding_points_alignment}
+
+
 # (reference module, the packages that copied its names, its replacements), in the order they are applied
 _FUNCTION_PATCHES = (
     ("pytorch3d.loss.mesh_edge_loss", ("pytorch3d.loss",), _mesh_loss),
@@ -799,6 +828,7 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.ball_query", ("pytorch3d.ops",), _ball_query),
     ("pytorch3d.ops.points_to_volumes", ("pytorch3d.ops",), _points_to_volumes),
     ("pytorch3d.ops.points_normals", ("pytorch3d.ops",), _points_normals),
+    ("pytorch3d.ops.points_alignment", ("pytorch3d.ops",), _points_alignment),
     ("pytorch3d.ops.iou_box3d", ("pytorch3d.ops",), _box3d_overlap),
     ("pytorch3d.ops.graph_conv", ("pytorch3d.ops",), _graph_conv),
     ("pytorch3d.ops.vert_align", ("pytorch3d.ops",), _vert_align),
