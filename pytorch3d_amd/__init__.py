@@ -30,6 +30,8 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     harmonic_embedding, HarmonicEmbedding  the positional encoding of NeRF-style MLPs: one read of x, one write of the embedding, fwd + bwd
     iterative_closest_point, corresponding_points_alignment, apply_similarity_transform  rigid / similarity registration of point
                                      clouds: six launches and one 4-byte host read per ICP iteration, the 3 x 3 SVD in float64 on the device
+    cot_laplacian, taubin_smoothing, taubin_smooth_packed  the cotangent Laplacian's entries and Taubin smoothing as gathers over the loss
+                                     tables: no sparse matrix per step, no atomics; mesh_laplacian_smoothing "cot" / "cotcurv" are fused too
     stratified_depths                one jiggled depth per bin along every ray, the centres read in place (an expand stays an expand)
 
 Importing the package does not load the HIP library; the first operator call does, and raises
@@ -49,8 +51,9 @@ from .graph_conv import gather_scatter, graph_conv, graph_topology, topology_of_
 from .iou_box3d import box3d_overlap  # noqa: F401
 from .knn import knn_gather, knn_points  # noqa: F401
 from .marching_cubes import marching_cubes, marching_cubes_packed, marching_cubes_torch  # noqa: F401
-from .mesh_losses import (mesh_edge_loss, mesh_laplacian_smoothing, mesh_loss_topology,  # noqa: F401
-                          mesh_normal_consistency)
+from .mesh_filtering import taubin_smooth_packed, taubin_smooth_torch, taubin_smoothing  # noqa: F401
+from .mesh_losses import (cot_laplacian, cot_laplacian_torch, cot_tables, mesh_edge_loss, mesh_laplacian_smoothing,  # noqa: F401
+                          mesh_loss_topology, mesh_normal_consistency)
 from .mesh_normals import face_areas_normals, vert_incidence, verts_normals  # noqa: F401
 from .point_mesh import (edge_point_distance, face_point_distance, point_edge_distance, point_face_distance,  # noqa: F401
                          point_mesh_edge_distance, point_mesh_face_distance)

@@ -21,8 +21,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # P3D_LIB_PATH selects an ablation build (profiles/ scripts only; see build.py)
 LIB_PATH = os.environ.get("P3D_LIB_PATH") or os.path.join(_HERE, "libp3d_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "p3d_amd.h")
-# the extension ABI of csrc/implicit.hip, cubify.hip, volume_sample.hip, harmonic.hip, marching_cubes.hip and points_alignment.hip:
-# entries p3di_*, declared in a header of their own (see its head)
+# the extension ABI of csrc/implicit.hip, cubify.hip, volume_sample.hip, harmonic.hip, marching_cubes.hip, points_alignment.hip and
+# mesh_laplacian.hip: entries p3di_*, declared in a header of their own (see its head)
 EXTENSION_HEADER_PATH = os.path.join(_HERE, "csrc", "implicit_abi.h")
 EXTENSION_PREFIX = "p3di_"
 

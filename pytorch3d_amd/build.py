@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("P3D_LIB_PATH") or os.path.join(HERE, "libp3d_amd.so")
 ARCH = "gfx950"
 
-SOURCES = ["binning.hip", "raster_mesh.hip", "raster_mesh_bwd.hip", "gather.hip", "transform.hip", "raster_points.hip", "render_points.hip", "composite.hip", "blend.hip", "clip.hip", "interp.hip", "shade.hip", "soft_phong.hip", "splatter.hip", "texture.hip", "texture_multi.hip", "atlas.hip", "ordered_bwd.hip", "normals.hip", "mesh_losses.hip", "knn.hip", "point_mesh.hip", "sample_points.hip", "fps_ball.hip", "points_to_volumes.hip", "point_frames.hip", "box3d.hip", "graph_conv.hip", "vert_align.hip", "implicit.hip", "cubify.hip", "marching_cubes.hip", "volume_sample.hip", "harmonic.hip", "points_alignment.hip", "profile.cpp"]
+SOURCES = ["binning.hip", "raster_mesh.hip", "raster_mesh_bwd.hip", "gather.hip", "transform.hip", "raster_points.hip", "render_points.hip", "composite.hip", "blend.hip", "clip.hip", "interp.hip", "shade.hip", "soft_phong.hip", "splatter.hip", "texture.hip", "texture_multi.hip", "atlas.hip", "ordered_bwd.hip", "normals.hip", "mesh_losses.hip", "mesh_laplacian.hip", "knn.hip", "point_mesh.hip", "sample_points.hip", "fps_ball.hip", "points_to_volumes.hip", "point_frames.hip", "box3d.hip", "graph_conv.hip", "vert_align.hip", "implicit.hip", "cubify.hip", "marching_cubes.hip", "volume_sample.hip", "harmonic.hip", "points_alignment.hip", "profile.cpp"]
 # what a source may include (paths relative to csrc/): every header on disk, so that a new one cannot be left out of needs_build()
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "p3d_amd.h")]
 

@@ -1,6 +1,7 @@
 /* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching), csrc/cubify.hip,
- * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip and
- * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points).
+ * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip,
+ * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points) and csrc/mesh_laplacian.hip (the cotangent
+ * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -270,6 +271,51 @@ int p3di_icp_iteration(const float* X, const float* Y, const int64_t* lengths1, 
 int p3di_points_alignment(const float* X, const float* Y, const int64_t* mask_len, const float* weights, int64_t N, int64_t P,
                           unsigned flags, float eps, float* R, float* T, float* s, int32_t* status, void* workspace,
                           size_t workspace_bytes, p3d_stream_t stream);
+
+/* The cotangent Laplacian (csrc/mesh_laplacian.hip): mesh_laplacian_smoothing "cot" / "cotcurv", the entries of cot_laplacian
+ * (pytorch3d/ops/laplacian_matrices.py:73-141) and taubin_smoothing (pytorch3d/ops/mesh_filtering.py) as gathers over int32 tables
+ * that the faces alone give (pytorch3d_amd/mesh_losses.py: cot_tables) beside the tables of p3d_amd.h's mesh regularisers:
+ *   adj_offsets (V + 1), adj (2 E), vert_mesh (V), num_verts (N): as there;  adj_edge (2 E): the edge id of every slot of adj;
+ *   edge_corner_offsets (E + 1), edge_corners (3 F): the corners 3 f + k sorted stably by the edge opposite them;
+ *   inc_offsets (V + 1), inc_corners (3 F): the corners sorted stably by their vertex.
+ * V, 2 E and 3 F must fit an int32.  faces (F, 3) int64 packed vertex ids, verts (V, 3) float32.
+ * p3di_mesh_cot_weights, two launches: face_cot (F, 3) <- per corner k (b^2 + c^2 - a^2) / area / 4.0 with a the side opposite the
+ *   corner, the sides by norm, s = 0.5 (A + B + C), face_area (F) <- sqrt(max(s (s - A) (s - B) (s - C), eps)): the reference's
+ *   operations in its order, one float32 rounding each;  edge_w (E) <- +0 plus face_cot of the edge's corners in list order:
+ *   L[i, j] of the reference for the edge (i, j).
+ * p3di_mesh_cot_inv_areas: inv_areas (V) <- A_v = +0 plus face_area of the vertex's corners in list order; 1 / A_v where A_v > 0.
+ * p3di_mesh_cot_laplacian_forward: per vertex Lx = sum_j w_e x_j and rowsum = sum_j w_e over its row of adj in list order;
+ *   curvature == 0 ("cot"):  scale = rowsum > 0 ? 1 / rowsum : rowsum,  r = Lx scale - x;
+ *   curvature != 0 ("cotcurv"):  scale = 0.25 inv_area,  r = (Lx - rowsum x) scale;
+ *   term = |r| (1.0f / num_verts[mesh]);  loss: ONE float, (the sum of the terms by the fixed tree of csrc/fixed_sum.h, depth
+ *   D(V) = 8 + ceil(ceil(V / 256) / 256) + 8) / N.  d (V, 3) <- r weight / |r| (0 where the norm is 0), scale (V), rowsum (V): kept for
+ *   the backward.  workspace: one partial sum per 256 vertices.  face_area and the incidence lists are read for curvature != 0 only.
+ * p3di_mesh_cot_laplacian_backward, one launch: with y = scale d, grad_verts_u = (grad_loss / N) (sum_j w_e y_j - d_u) for "cot" and
+ *   (grad_loss / N) (sum_j w_e y_j - rowsum_u y_u) for "cotcurv": L is symmetric and a constant of the step.  Every row is written.
+ * p3di_mesh_taubin_smoothing, 2 num_iter launches: a half-step is out_v = c1 x_v + (c sum_j w x_j) / sum_j w with
+ *   w = 1 / (|x_v - x_j| + eps) over the row of adj; a vertex without a neighbour gives NaN (0 / 0), the reference's answer.  Each
+ *   iteration takes a half-step with (lambd_c1, lambd_c) into scratch (V, 3) and one with (mu_c1, mu_c) into out (V, 3); verts is
+ *   only read and may not overlap either; num_iter == 0 copies verts to out.
+ * No float atomics: the same bits on every run and stream.  A table that breaks its contract gives NaN or wrong numbers, never an
+ * access outside the arrays (ids are range-checked, CSR offsets clamped).  Negative sizes, sizes beyond int32, N <= 0, missing
+ * pointers: P3D_ERR_INVALID_ARG; a short workspace: P3D_ERR_WORKSPACE.  No host sync. */
+size_t p3di_mesh_cot_laplacian_forward_workspace_bytes(int64_t V);
+int p3di_mesh_cot_weights(const float* verts, const int64_t* faces, const int32_t* edge_corner_offsets, const int32_t* edge_corners,
+                          int64_t V, int64_t F, int64_t E, float eps, float* face_cot, float* face_area, float* edge_w,
+                          p3d_stream_t stream);
+int p3di_mesh_cot_inv_areas(const float* face_area, const int32_t* inc_offsets, const int32_t* inc_corners, int64_t V, int64_t F,
+                            float* inv_areas, p3d_stream_t stream);
+int p3di_mesh_cot_laplacian_forward(const float* verts, const float* edge_w, const float* face_area, const int32_t* adj_offsets,
+                                    const int32_t* adj, const int32_t* adj_edge, const int32_t* inc_offsets, const int32_t* inc_corners,
+                                    const int32_t* vert_mesh, const int32_t* num_verts, int64_t V, int64_t E, int64_t F, int N,
+                                    int curvature, float* d, float* scale, float* rowsum, void* workspace, size_t workspace_bytes,
+                                    float* loss, p3d_stream_t stream);
+int p3di_mesh_cot_laplacian_backward(const float* grad_loss, const float* d, const float* scale, const float* rowsum, const float* edge_w,
+                                     const int32_t* adj_offsets, const int32_t* adj, const int32_t* adj_edge, int64_t V, int64_t E, int N,
+                                     int curvature, float* grad_verts, p3d_stream_t stream);
+int p3di_mesh_taubin_smoothing(const float* verts, const int32_t* adj_offsets, const int32_t* adj, int64_t V, int64_t E, float lambd_c1,
+                               float lambd_c, float mu_c1, float mu_c, float eps, int num_iter, float* scratch, float* out,
+                               p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,10 +1,12 @@
-"""The three mesh regularisers of a fitting loop on the HIP kernels of csrc/mesh_losses.hip.
+"""The three mesh regularisers of a fitting loop on the HIP kernels of csrc/mesh_losses.hip and csrc/mesh_laplacian.hip.
 
     mesh_edge_loss(meshes, target_length=0.0)            pytorch3d/loss/mesh_edge_loss.py
     mesh_laplacian_smoothing(meshes, method="uniform")   pytorch3d/loss/mesh_laplacian_smoothing.py
     mesh_normal_consistency(meshes)                      pytorch3d/loss/mesh_normal_consistency.py
     edge_loss / laplacian_smoothing / normal_consistency (verts, topology, ...)   the same on packed vertices
     mesh_loss_topology(faces_packed, num_verts_per_mesh, num_faces_per_mesh)      the tables, once per topology
+    cot_laplacian(verts, faces, eps=1e-12) -> (L, inv_areas)   pytorch3d/ops/laplacian_matrices.py
+    cot_tables(faces_packed, V)                          what "cot" / "cotcurv" and cot_laplacian need beside them, on first use
 
 Same names, defaults and return values as the reference; `meshes` is this package's PackedMeshes or the reference's Meshes (anything
 with verts_packed / faces_packed / num_verts_per_mesh / num_faces_per_mesh).  The reference redoes the topology's work on every call
@@ -14,14 +16,18 @@ backward adds with float atomics.  Here everything that depends on the faces alo
 autograd node, and every sum is a gather or a fixed tree: no float atomic, the same bits on every run, stream and process, with
 torch.use_deterministic_algorithms on or off (include/p3d_amd.h: the tree and its depth).
 
-float32 vertices on the GPU take the kernels.  CPU tensors, float64 and the methods "cot" / "cotcurv" take the torch formulation of
-the same arithmetic below (differentiated by autograd).
+float32 vertices on the GPU take the kernels, "cot" and "cotcurv" included (csrc/mesh_laplacian.hip: the face and edge weights in
+two launches, the vertex pass and its fixed-tree sum in two, the backward in one).  CPU tensors and float64 take the torch formulation
+of the same arithmetic below (differentiated by autograd).  CALLS counts, for the cotangent paths, which of the two ran.
 """
+import weakref
+
 import torch
 
 from . import _C, _lib
 
 _TOPOLOGY_KEY = "_p3d_amd_loss_topology"
+CALLS = {"cot_fused": 0, "cot_torch": 0, "cot_laplacian_fused": 0, "cot_laplacian_torch": 0}
 
 
 # ---- the wing-pair index (also `pytorch3d._C.mesh_normal_consistency_find_verts`: pytorch3d_amd/_aux_ops.py) ---------------------
@@ -48,16 +54,32 @@ class MeshLossTopology:
         adj_offsets (V + 1,), adj (2 E,), vert_mesh (V,), num_verts (N,)   neighbours of a vertex ascending; deg(v) from the offsets
         pairs (P, 4), pair_mesh (P,), num_pairs (N,)            rows (v0, v1, a, b)
         pair_offsets (V + 1,), pair_slots (4 P,)                 per vertex its slots 4 pair + role, sorted stably by vertex
+        cot                                                      None, or the CotTables of "cot" / "cotcurv" (built on their first use)
     and on the host N, V, E, P, `empty` (no mesh, no vertex or no face: the reference's isempty()) and `repeated`: some face names one
     vertex twice.  Such a face has a self edge (lo == hi), which the tables would count as an edge of length 0 and a neighbour of
     itself where the reference does something else: the losses refuse such a topology and the shim hands it to the reference."""
 
     __slots__ = ("N", "V", "E", "P", "empty", "repeated", "device", "edges", "edge_mesh", "num_edges", "adj_offsets", "adj", "vert_mesh", "num_verts",
-                 "pairs", "pair_mesh", "num_pairs", "pair_offsets", "pair_slots")
+                 "pairs", "pair_mesh", "num_pairs", "pair_offsets", "pair_slots", "cot")
 
 
 def _i32(t):
     return t.to(torch.int32).contiguous()
+
+
+def _corner_edges(faces, V):
+    """faces (F, 3) int64.  Corner 3 f + k of a face names the edge OPPOSITE its vertex k: (lo, hi) (F, 3) of every corner, the unique
+    keys lo * V + hi ascending and the edge id of every corner (3 F,)."""
+    opposite = torch.stack([faces[:, [1, 2]], faces[:, [2, 0]], faces[:, [0, 1]]], 1)  # (F, 3, 2)
+    lo, hi = opposite.amin(2), opposite.amax(2)
+    key, corner_edge = torch.unique((lo * max(V, 1) + hi).reshape(-1), return_inverse=True)
+    return lo, hi, key, corner_edge
+
+
+def _adjacency_order(edges, V):
+    """Both directions of every edge sorted by (vertex, neighbour): (src, dst, order) with slot i of the adjacency = dst[order[i]]."""
+    src, dst = torch.cat([edges[:, 0], edges[:, 1]]), torch.cat([edges[:, 1], edges[:, 0]])
+    return src, dst, torch.argsort(src * max(V, 1) + dst)
 
 
 def mesh_loss_topology(faces_packed, num_verts_per_mesh, num_faces_per_mesh):
@@ -75,7 +97,7 @@ def mesh_loss_topology(faces_packed, num_verts_per_mesh, num_faces_per_mesh):
     if nv.numel() != nf.numel():
         raise RuntimeError("mesh_loss_topology: num_verts_per_mesh and num_faces_per_mesh must have one entry per mesh")
     t = MeshLossTopology()
-    t.device = dev
+    t.device, t.cot = dev, None
     t.N, F = int(nv.numel()), int(faces.size(0))
     t.V = int(nv.sum()) if t.N else 0
     if t.N and int(nf.sum()) != F:
@@ -84,16 +106,13 @@ def mesh_loss_topology(faces_packed, num_verts_per_mesh, num_faces_per_mesh):
     t.empty = t.N == 0 or V == 0 or F == 0
     vert_mesh = torch.repeat_interleave(torch.arange(t.N, device=dev), nv)
     # the unique undirected edges, ascending by lo * V + hi; corner 3 f + k of a face names the edge OPPOSITE its vertex k
-    opposite = torch.stack([faces[:, [1, 2]], faces[:, [2, 0]], faces[:, [0, 1]]], 1)  # (F, 3, 2)
-    lo, hi = opposite.amin(2), opposite.amax(2)
-    key, corner_edge = torch.unique((lo * max(V, 1) + hi).reshape(-1), return_inverse=True)
+    lo, hi, key, corner_edge = _corner_edges(faces, V)
     edges = torch.stack([key // max(V, 1), key % max(V, 1)], 1)
     t.E = int(edges.size(0))
     t.repeated = bool((lo == hi).any())
     edge_mesh = vert_mesh[edges[:, 0]] if t.E else edges.new_zeros((0,))
     # the adjacency: both directions of every edge, sorted by (vertex, neighbour)
-    src, dst = torch.cat([edges[:, 0], edges[:, 1]]), torch.cat([edges[:, 1], edges[:, 0]])
-    order = torch.argsort(src * max(V, 1) + dst)
+    src, dst, order = _adjacency_order(edges, V)
     adj_offsets = torch.searchsorted(src[order].contiguous(), torch.arange(V + 1, device=dev))
     # the wing pairs: the corners sorted stably by edge, every pair (i < j) of corners of one edge
     order_c = torch.sort(corner_edge, stable=True).indices
@@ -113,6 +132,88 @@ def mesh_loss_topology(faces_packed, num_verts_per_mesh, num_faces_per_mesh):
     t.pairs, t.pair_mesh, t.num_pairs = _i32(pairs), _i32(pair_mesh), _i32(torch.bincount(pair_mesh, minlength=t.N))
     t.pair_offsets, t.pair_slots = _i32(pair_offsets), _i32(slots)
     return t
+
+
+# ---- the tables of the cotangent Laplacian ---------------------------------------------------------------------------------------------
+class CotTables:
+    """What "cot" / "cotcurv", cot_laplacian and nothing else need, from (faces_packed, V) alone.  int32, contiguous, on the faces' device:
+        adj_offsets (V + 1,), adj (2 E,)              the adjacency of MeshLossTopology (the same arrays where built from one)
+        adj_edge (2 E,)                                the edge id of every slot of adj
+        edge_corner_offsets (E + 1,), edge_corners (3 F,)   the corners 3 f + k sorted stably by the edge opposite them: a boundary edge
+                                                       has one corner, a non-manifold edge three or more
+        inc_offsets (V + 1,), inc_corners (3 F,)      the incidence list of mesh_normals.vert_incidence
+    and faces (F, 3) int64 contiguous, V, E, F, `repeated`, and `coo` (2, 2 E) int64: the (row, column) of every slot, the indices
+    of cot_laplacian's matrix, made on its first call."""
+
+    __slots__ = ("V", "E", "F", "repeated", "device", "faces", "adj_offsets", "adj", "adj_edge", "edge_corner_offsets", "edge_corners",
+                 "inc_offsets", "inc_corners", "coo")
+
+
+def cot_tables(faces_packed, V, topology=None):
+    """The CotTables of faces_packed (F, 3) integer packed vertex ids in [0, V).  Plain torch on the device of the faces; syncs with
+    the host -- built once per topology (cot_tables_of).  topology: the MeshLossTopology of the same faces, whose adjacency is shared."""
+    from .mesh_normals import vert_incidence
+
+    faces = faces_packed
+    if faces.dim() != 2 or faces.size(1) != 3:
+        raise RuntimeError("cot_tables: faces_packed must have shape (F, 3)")
+    if faces.numel() >= 2 ** 31:
+        raise RuntimeError("cot_tables: 3 F must fit an int32")
+    V, dev = int(V), faces.device
+    faces = faces.to(torch.int64).contiguous()
+    c = CotTables()
+    c.V, c.F, c.device, c.faces, c.coo = V, int(faces.size(0)), dev, faces, None
+    lo, hi, key, corner_edge = _corner_edges(faces, V)
+    c.E = int(key.numel())
+    c.repeated = bool((lo == hi).any())
+    edges = torch.stack([key // max(V, 1), key % max(V, 1)], 1)
+    src, dst, order = _adjacency_order(edges, V)
+    if topology is not None and topology.E == c.E and topology.V == V:
+        c.adj_offsets, c.adj = topology.adj_offsets, topology.adj
+    else:
+        c.adj_offsets = _i32(torch.searchsorted(src[order].contiguous(), torch.arange(V + 1, device=dev)))
+        c.adj = _i32(dst[order])
+    edge_id = torch.arange(c.E, device=dev)
+    c.adj_edge = _i32(torch.cat([edge_id, edge_id])[order])
+    by_edge = torch.sort(corner_edge, stable=True)
+    c.edge_corners = _i32(by_edge.indices)
+    c.edge_corner_offsets = _i32(torch.searchsorted(by_edge.values.contiguous(), torch.arange(c.E + 1, device=dev)))
+    c.inc_offsets, c.inc_corners = vert_incidence(faces, V)
+    return c
+
+
+_COT_CACHE_SIZE = 8
+_cot_cache = []  # [weakref of the faces tensor, data_ptr, shape, _version, V, tables], most recent last
+
+
+def cot_tables_of(faces_packed, V, topology=None):
+    """cot_tables(faces_packed, V) kept: in `topology.cot` where a MeshLossTopology is given (a user of "uniform" alone never pays for
+    them), and in a cache of the last few faces tensors (the same tensor object with the same address, shape and _version, and V --
+    the way graph_conv.topology_of_edges keeps its tables per edge tensor).  Meshes.faces_packed() hands back the same tensor on every
+    call: a fitting loop builds once."""
+    V = int(V)
+    if topology is not None and topology.cot is not None:
+        return topology.cot
+    _cot_cache[:] = [c for c in _cot_cache if c[0]() is not None]
+    key = (faces_packed.data_ptr(), tuple(faces_packed.shape), faces_packed._version, V)
+    found = None
+    for i, c in enumerate(_cot_cache):
+        if c[0]() is faces_packed and tuple(c[1:5]) == key:
+            _cot_cache.append(_cot_cache.pop(i))
+            found = c[5]
+            break
+    if found is None:
+        found = cot_tables(faces_packed, V, topology)
+        _cot_cache[:] = [c for c in _cot_cache if c[0]() is not faces_packed]
+        _cot_cache.append([weakref.ref(faces_packed), *key, found])
+        del _cot_cache[:-_COT_CACHE_SIZE]
+    if topology is not None:
+        topology.cot = found
+    return found
+
+
+def clear_cot_tables_cache():
+    del _cot_cache[:]
 
 
 def topology_of(meshes):
@@ -269,6 +370,50 @@ class _Laplacian(torch.autograd.Function):
         return out, None
 
 
+def _cot_weights_hip(v, c, eps=1e-12):
+    """(face_cot (F, 3), face_area (F,), edge_w (E,)) of float32 GPU vertices v (V, 3) contiguous: two launches."""
+    dev = v.device
+    face_cot = torch.empty((c.F, 3), dtype=torch.float32, device=dev)
+    face_area = torch.empty((c.F,), dtype=torch.float32, device=dev)
+    edge_w = torch.empty((c.E,), dtype=torch.float32, device=dev)
+    _lib.call("p3di_mesh_cot_weights", "cot_laplacian weights", dev, v, c.faces, c.edge_corner_offsets, c.edge_corners, c.V, c.F, c.E,
+              float(eps), face_cot, face_area, edge_w)
+    return face_cot, face_area, edge_w
+
+
+class _CotLaplacian(torch.autograd.Function):
+    """mesh_laplacian_smoothing "cot" / "cotcurv": five launches a step (face weights, edge weights, vertex pass, its sum; backward)."""
+
+    @staticmethod
+    def forward(ctx, verts, t, c, curvature):
+        v = _C._c(verts, torch.float32)
+        lib, dev = _lib.load(), v.device
+        _, face_area, edge_w = _cot_weights_hip(v, c)
+        nbytes = lib.p3di_mesh_cot_laplacian_forward_workspace_bytes(t.V)
+        ws = _C._workspace(nbytes, dev)
+        d = torch.empty_like(v)
+        scale = torch.empty((t.V,), dtype=torch.float32, device=dev)
+        rowsum = torch.empty((t.V,), dtype=torch.float32, device=dev)
+        loss = torch.empty((1,), dtype=torch.float32, device=dev)
+        _lib.call("p3di_mesh_cot_laplacian_forward", "mesh_laplacian_smoothing cot forward", dev, v, edge_w, face_area, c.adj_offsets, c.adj,
+                  c.adj_edge, c.inc_offsets, c.inc_corners, t.vert_mesh, t.num_verts, t.V, c.E, c.F, t.N, int(curvature), d, scale, rowsum,
+                  ws, nbytes, loss)
+        ctx.save_for_backward(d, scale, rowsum, edge_w)
+        ctx.tables, ctx.N, ctx.curvature = c, t.N, int(curvature)
+        return loss.reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        (d, scale, rowsum, edge_w), c = ctx.saved_tensors, ctx.tables
+        dev = d.device
+        g = _grad_scalar(grad_loss, dev)
+        out = torch.empty_like(d)
+        _lib.call("p3di_mesh_cot_laplacian_backward", "mesh_laplacian_smoothing cot backward", dev, g, d, scale, rowsum, edge_w, c.adj_offsets,
+                  c.adj, c.adj_edge, c.V, c.E, ctx.N, ctx.curvature, out)
+        return out, None, None, None
+
+
 class _NormalConsistency(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, t):
@@ -311,7 +456,9 @@ def edge_loss(verts, topology, target_length=0.0):
 
 
 def laplacian_smoothing(verts, topology, method="uniform", faces_packed=None):
-    """verts (V, 3), topology: mesh_loss_topology(...).  "cot" / "cotcurv" need faces_packed and take the torch formulation."""
+    """verts (V, 3), topology: mesh_loss_topology(...).  "cot" / "cotcurv" need faces_packed -- the faces the topology was built from;
+    float32 vertices on the GPU take one autograd node over csrc/mesh_laplacian.hip (the tables of cot_tables_of, built on the first
+    call and kept in topology.cot), CPU tensors and float64 the torch formulation."""
     if method not in ("uniform", "cot", "cotcurv"):
         raise ValueError("Method should be one of {uniform, cot, cotcurv}")
     _check(verts, topology, "laplacian_smoothing")
@@ -319,7 +466,74 @@ def laplacian_smoothing(verts, topology, method="uniform", faces_packed=None):
         return _Laplacian.apply(verts, topology)
     if method != "uniform" and faces_packed is None:
         raise ValueError("laplacian_smoothing: the methods cot and cotcurv need faces_packed")
+    if method != "uniform" and _fused(verts):
+        if faces_packed.device != verts.device:
+            raise RuntimeError(f"laplacian_smoothing: verts are on {verts.device}, faces_packed on {faces_packed.device}")
+        c = cot_tables_of(faces_packed, topology.V, topology)
+        if c.E != topology.E or c.F != int(faces_packed.shape[0]):
+            raise RuntimeError("laplacian_smoothing: faces_packed are not the faces of the topology")
+        CALLS["cot_fused"] += 1
+        return _CotLaplacian.apply(verts, topology, c, method == "cotcurv")
+    if method != "uniform":
+        CALLS["cot_torch"] += 1
     return _torch_laplacian(verts, topology, method, None if faces_packed is None else faces_packed.long())
+
+
+def cot_laplacian_torch(verts, faces, eps=1e-12):
+    """The reference's chain restated (laplacian_matrices.py:91-141): an UNCOALESCED sparse (V, V) L and inv_areas (V, 1)."""
+    V, F = verts.shape[0], faces.shape[0]
+    face_verts = verts[faces]
+    v0, v1, v2 = face_verts[:, 0], face_verts[:, 1], face_verts[:, 2]
+    A, B, C = (v1 - v2).norm(dim=1), (v0 - v2).norm(dim=1), (v0 - v1).norm(dim=1)
+    s = 0.5 * (A + B + C)
+    area = (s * (s - A) * (s - B) * (s - C)).clamp(min=eps).sqrt()
+    A2, B2, C2 = A * A, B * B, C * C
+    cot = torch.stack([(B2 + C2 - A2) / area, (A2 + C2 - B2) / area, (A2 + B2 - C2) / area], dim=1) / 4.0
+    idx = torch.stack([faces[:, [1, 2, 0]], faces[:, [2, 0, 1]]], dim=0).view(2, F * 3)
+    L = torch.sparse_coo_tensor(idx, cot.view(-1), (V, V), dtype=torch.float32)
+    L = L + L.t()
+    inv_areas = torch.zeros(V, dtype=torch.float32, device=verts.device)
+    inv_areas.scatter_add_(0, faces.view(-1), torch.stack([area] * 3, dim=1).view(-1))
+    pos = inv_areas > 0
+    inv_areas[pos] = torch.reciprocal(inv_areas[pos])
+    return L, inv_areas.view(-1, 1)
+
+
+def cot_laplacian_kernel_path(verts, faces):
+    """Whether cot_laplacian(verts, faces) runs the kernels, the tables apart (a face that names one vertex twice: the chain)."""
+    return (torch.is_tensor(verts) and torch.is_tensor(faces) and verts.is_cuda and verts.dtype == torch.float32 and verts.dim() == 2
+            and verts.size(1) == 3 and faces.dim() == 2 and faces.size(1) == 3 and faces.device == verts.device
+            and not faces.dtype.is_floating_point and verts.size(0) > 0 and faces.size(0) > 0
+            and not (torch.is_grad_enabled() and verts.requires_grad))
+
+
+def cot_laplacian(verts, faces, eps=1e-12):
+    """pytorch3d.ops.cot_laplacian: (L, inv_areas) -- L a sparse float32 (V, V) with L[i, j] = the sum, over the faces that hold the
+    edge (i, j), of cot(the angle opposite the edge) / 4, and inv_areas (V, 1) the reciprocal of the summed areas of the faces round
+    each vertex (a sum that is not positive stays as it is).
+
+    float32 GPU input whose result needs no gradient -- not (torch.is_grad_enabled() and verts.requires_grad) -- takes the face and
+    edge kernels of csrc/mesh_laplacian.hip and the area gather: three launches and one gather of the 2 E values.  That L is COALESCED,
+    with the 2 E directed entries ascending by (row, column); its indices are built once per faces tensor (cot_tables_of).  The
+    reference's L is uncoalesced, one entry per corner and direction: compare `to_dense()` or `coalesce()`, not the raw values.
+    Everything else (CPU tensors, inputs that want a gradient, a face that names one vertex twice) takes the reference's chain
+    restated, which gives the reference's layout."""
+    fused = cot_laplacian_kernel_path(verts, faces)
+    c = cot_tables_of(faces, verts.shape[0]) if fused else None
+    if c is None or c.repeated:
+        CALLS["cot_laplacian_torch"] += 1
+        return cot_laplacian_torch(verts, faces, eps)
+    CALLS["cot_laplacian_fused"] += 1
+    v = _C._c(verts.detach(), torch.float32)
+    dev = v.device
+    _, face_area, edge_w = _cot_weights_hip(v, c, eps)
+    inv_areas = torch.empty((c.V,), dtype=torch.float32, device=dev)
+    _lib.call("p3di_mesh_cot_inv_areas", "cot_laplacian inv_areas", dev, face_area, c.inc_offsets, c.inc_corners, c.V, c.F, inv_areas)
+    if c.coo is None:
+        off = c.adj_offsets.long()
+        c.coo = torch.stack([torch.repeat_interleave(torch.arange(c.V, device=dev), off[1:] - off[:-1]), c.adj.long()], 0)
+    L = torch.sparse_coo_tensor(c.coo, edge_w[c.adj_edge.long()], (c.V, c.V), dtype=torch.float32, is_coalesced=True)
+    return L, inv_areas.view(-1, 1)
 
 
 def normal_consistency(verts, topology):
@@ -350,8 +564,8 @@ def mesh_edge_loss(meshes, target_length: float = 0.0):
 
 
 def mesh_laplacian_smoothing(meshes, method: str = "uniform"):
-    """Laplacian smoothing objective |L x| averaged per mesh; method uniform (HIP kernels for float32 on the GPU), cot or cotcurv
-    (torch).  Returns tensor([0.]) (requires_grad) for a batch without meshes or of empty meshes only."""
+    """Laplacian smoothing objective |L x| averaged per mesh; method uniform, cot or cotcurv: HIP kernels for float32 on the GPU, the
+    torch formulation for CPU tensors and float64.  Returns tensor([0.]) (requires_grad) for a batch without meshes or of empty meshes only."""
     if len(meshes) == 0:
         return _empty_value(_device_of(meshes))
     t = topology_of(meshes)

@@ -57,6 +57,14 @@ reference classes runs on them end to end:
                                                                  fixed-tree sums (no float atomics, no host round trip);
                                                                  without patch_python the reference's own normal consistency
                                                                  runs too (`_C.mesh_normal_consistency_find_verts` on the host)
+    ops.laplacian_matrices.cot_laplacian / ops.mesh_filtering.taubin_smoothing -> csrc/mesh_laplacian.hip: the cotangent weights per
+                                                                 face and edge and the vertex areas as gathers over tables kept per
+                                                                 faces tensor (a coalesced L); Taubin smoothing as 2 num_iter
+                                                                 launches over the loss tables' adjacency.  The reference's own
+                                                                 mesh_laplacian_smoothing("cot" / "cotcurv") finds cot_laplacian
+                                                                 served by the kernels (the patched loss keeps "uniform" alone);
+                                                                 inputs that want a gradient, CPU tensors and a face that names
+                                                                 one vertex twice go to the reference's functions
     ops.knn.knn_points / loss.chamfer.chamfer_distance        -> csrc/knn.hip: brute-force nearest neighbours, one lane per query;
                                                                  chamfer without normals is one autograd node with no host
                                                                  sync; inputs the kernels do not take go to this package's torch
@@ -487,6 +495,48 @@ def _mesh_loss(ref):
     return {fname: _wrap(fname, getattr(ref, fname), getattr(ours, fname), uniform if fname == "mesh_laplacian_smoothing" else usable)}
 
 
+def _cot_laplacian(ref):
+    """pytorch3d.ops.laplacian_matrices.cot_laplacian (an uncoalesced sparse V x V matrix and a scatter_add on every call) ->
+    pytorch3d_amd.mesh_losses.cot_laplacian: the face and edge kernels of csrc/mesh_laplacian.hip and the area gather over tables
+    kept per faces tensor; a COALESCED L with the same dense values.  float32 on the GPU, a non-empty mesh, no face that names one
+    vertex twice and no gradient wanted (the reference's losses call it under no_grad); anything else goes to the reference's
+    function.  The patched pytorch3d.loss.mesh_laplacian_smoothing keeps its predicate method == "uniform": a "cot" / "cotcurv" call
+    runs the reference's loss, which finds this function under its global name."""
+    ours = _our("mesh_losses")
+
+    def usable(verts, faces, eps=1e-12):
+        if not ours.cot_laplacian_kernel_path(verts, faces):
+            return False
+        return not ours.cot_tables_of(faces, verts.shape[0]).repeated
+
+    return {"cot_laplacian": _wrap("cot_laplacian", ref.cot_laplacian, ours.cot_laplacian, usable)}
+
+
+def _taubin_smoothing(ref):
+    """pytorch3d.ops.mesh_filtering.taubin_smoothing (two sparse V x V matrices, two torch.sparse.sum and two mm per iteration) ->
+    pytorch3d_amd.mesh_filtering.taubin_smoothing: 2 num_iter launches over the adjacency of the loss tables kept with the topology.
+    Exact Meshes, float32 on the GPU, not empty, no face that names one vertex twice, no gradient wanted; anything else goes to the
+    reference's function.  The result is built as the reference builds it: Meshes(verts=list, faces=meshes.faces_list())."""
+    import torch
+
+    ours, losses = _our("mesh_filtering"), _our("mesh_losses")
+    Meshes = importlib.import_module("pytorch3d.structures.meshes").Meshes
+
+    def usable(meshes, lambd=0.53, mu=-0.53, num_iter=10):
+        if type(meshes) is not Meshes or meshes._N == 0 or int(num_iter) < 0:
+            return False
+        verts = meshes.verts_packed()
+        if not _is_hip_f32(verts) or (torch.is_grad_enabled() and verts.requires_grad):
+            return False
+        empty = meshes.__dict__.get("_p3d_amd_isempty")  # a host sync: asked once per topology (see _patch_meshes_offset_verts)
+        if empty is None:
+            empty = bool(meshes.isempty())
+            meshes.__dict__["_p3d_amd_isempty"] = empty
+        return not empty and not losses.topology_of(meshes).repeated
+
+    return {"taubin_smoothing": _wrap("taubin_smoothing", ref.taubin_smoothing, ours.taubin_smoothing, usable)}
+
+
 def _knn_points(ref):
     """csrc/knn.hip for float32 GPU clouds with D in {2, 3} and K <= 32.  The reference's own function ends in `_C.knn_points_idx`,
     which stays a stub that raises."""
@@ -820,6 +870,8 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.loss.mesh_edge_loss", ("pytorch3d.loss",), _mesh_loss),
     ("pytorch3d.loss.mesh_laplacian_smoothing", ("pytorch3d.loss",), _mesh_loss),
     ("pytorch3d.loss.mesh_normal_consistency", ("pytorch3d.loss",), _mesh_loss),
+    ("pytorch3d.ops.laplacian_matrices", ("pytorch3d.ops", "pytorch3d.loss.mesh_laplacian_smoothing", "pytorch3d.loss"), _cot_laplacian),
+    ("pytorch3d.ops.mesh_filtering", ("pytorch3d.ops",), _taubin_smoothing),
     ("pytorch3d.ops.knn", ("pytorch3d.ops", "pytorch3d.loss.chamfer", "pytorch3d.loss"), _knn_points),
     ("pytorch3d.loss.chamfer", ("pytorch3d.loss",), _chamfer_distance),
     ("pytorch3d.loss.point_mesh_distance", ("pytorch3d.loss",), _point_mesh_distance),
