@@ -2042,3 +2042,90 @@ HOT_PATH_EXPORTS = (
     "accum_weightedsumnorm", "accum_weightedsumnorm_backward", "accum_weightedsum", "accum_weightedsum_backward",
     "interp_face_attrs_forward", "interp_face_attrs_backward", "sigmoid_alpha_blend", "sigmoid_alpha_blend_backward",
 )
+
+
+# ----------------------------------------------------------------------------------------------
+# mesh edges and SubdivideMeshes (csrc/mesh_edges.hip, csrc/subdivide.hip, csrc/implicit_abi.h), behind pytorch3d_amd.subdivide_meshes.
+# No `_C` operator of the reference: nothing in shim.EXPORTS.
+def mesh_edges_fits(V, F):
+    """Whether the kernels' int32 indices cover the sizes (else p3di_mesh_edges_build refuses them)."""
+    return V >= 1 and F >= 1 and 6 * F <= 2**31 - 1 and 2 * V + 1 <= 2**31 - 1
+
+
+def mesh_edges_build(faces, vert_first, V):
+    """p3di_mesh_edges_build: faces (F, 3) int64 contiguous packed ids, vert_first (N + 1,) int32 on the same GPU -> (edges (3 F, 2),
+    face_edges (F, 3), edge_mesh (3 F,), edge_first (N + 1,), row_offsets (2 V + 1,), hi_edges (3 F,)) int32 and record (4 + N,)
+    int64, all on the device and not synchronised; the first record[0] rows of edges, edge_mesh and hi_edges are written."""
+    who = "mesh_edges_build"
+    dev = _same_device(("faces", faces), ("vert_first", vert_first))
+    F, N = faces.shape[0], vert_first.numel() - 1
+    if faces.dtype != torch.int64 or faces.dim() != 2 or faces.shape[1] != 3 or not faces.is_contiguous():
+        raise RuntimeError(f"{who}: faces must be contiguous int64 (F, 3), got {faces.dtype} {tuple(faces.shape)}")
+    if not mesh_edges_fits(V, F) or N < 1:
+        raise RuntimeError(f"{who}: V = {V}, F = {F}, N = {N} is empty or beyond the kernels' int32 indices")
+    nbytes = _lib.load().p3di_mesh_edges_workspace_bytes(V, F)
+    with torch.cuda.device(dev):
+        ws = _workspace(nbytes, dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        edges, face_edges, edge_mesh = torch.empty((3 * F, 2), **i32), torch.empty((F, 3), **i32), torch.empty((3 * F,), **i32)
+        edge_first, row_offsets, hi_edges = torch.empty((N + 1,), **i32), torch.empty((2 * V + 1,), **i32), torch.empty((3 * F,), **i32)
+        record = torch.empty((4 + N,), dtype=torch.int64, device=dev)
+    _lib.call("p3di_mesh_edges_build", who, dev, faces, vert_first, V, F, N, ws, nbytes, edges, face_edges, edge_mesh, edge_first,
+              row_offsets, hi_edges, record)
+    return edges, face_edges, edge_mesh, edge_first, row_offsets, hi_edges, record
+
+
+def subdivide_faces(faces, face_edges, vert_first, face_first, edge_first, local=True, packed=True):
+    """p3di_subdivide_faces -> (faces_local, faces_packed), each (4 F, 3) int64 or None where not asked for."""
+    dev = _same_device(("faces", faces), ("face_edges", face_edges), ("vert_first", vert_first), ("face_first", face_first),
+                       ("edge_first", edge_first))
+    F, N = faces.shape[0], vert_first.numel() - 1
+    with torch.cuda.device(dev):
+        out = [torch.empty((4 * F, 3), dtype=torch.int64, device=dev) if wanted else None for wanted in (local, packed)]
+    _lib.call("p3di_subdivide_faces", "subdivide_faces", dev, faces, face_edges, vert_first, face_first, edge_first, F, N, *out)
+    return tuple(out)
+
+
+def _rows3(x):
+    """x (V, D) or (B, V, D) as (the tensor, its (batch, row, element) strides, B)."""
+    return (x, (0,) + tuple(x.stride()), 1) if x.dim() == 2 else (x, tuple(x.stride()), x.shape[0])
+
+
+def subdivide_forward(xs, edges, vert_first, edge_first, V, E):
+    """p3di_subdivide_forward: xs one or two float32 tensors (V, D) or (B, V, D) with any strides (the same B) -> their subdivided
+    (V + E, D) / (B, V + E, D) tensors, one launch."""
+    dev = _same_device(*[("x%d" % i, x) for i, x in enumerate(xs)], ("edges", edges))
+    N = vert_first.numel() - 1
+    args, outs, B = [], [], 1
+    for x in xs:
+        x, strides, B = _rows3(x)
+        with torch.cuda.device(dev):
+            out = torch.empty(tuple(x.shape[:-2]) + (V + E, x.shape[-1]), dtype=torch.float32, device=dev)
+        args += [x, strides, x.shape[-1], out]
+        outs.append(out)
+    if len(xs) == 1:
+        args += [None, (0, 0, 0), 0, None]
+    _lib.call("p3di_subdivide_forward", "subdivide_forward", dev, *args, edges, vert_first, edge_first, V, E, N, B)
+    return outs
+
+
+def subdivide_backward(gs, row_offsets, hi_edges, vert_first, edge_first, V, E):
+    """p3di_subdivide_backward: gs one or two contiguous float32 gradients (V + E, D) / (B, V + E, D), an entry None where no gradient
+    is wanted -> the (V, D) / (B, V, D) input gradients (None likewise), one launch."""
+    dev = row_offsets.device
+    N = vert_first.numel() - 1
+    args, outs, B = [], [], 1
+    for g in gs:
+        if g is None:
+            args += [None, 0, None]
+            outs.append(None)
+            continue
+        B = g.shape[0] if g.dim() == 3 else 1
+        with torch.cuda.device(dev):
+            out = torch.empty(tuple(g.shape[:-2]) + (V, g.shape[-1]), dtype=torch.float32, device=dev)
+        args += [g, g.shape[-1], out]
+        outs.append(out)
+    if len(gs) == 1:
+        args += [None, 0, None]
+    _lib.call("p3di_subdivide_backward", "subdivide_backward", dev, *args, row_offsets, hi_edges, vert_first, edge_first, V, E, N, B)
+    return outs

@@ -30,6 +30,9 @@ AMD MI355X (CDNA4 / gfx950) as hand-written HIP behind a C ABI (include/p3d_amd.
     harmonic_embedding, HarmonicEmbedding  the positional encoding of NeRF-style MLPs: one read of x, one write of the embedding, fwd + bwd
     iterative_closest_point, corresponding_points_alignment, apply_similarity_transform  rigid / similarity registration of point
                                      clouds: six launches and one 4-byte host read per ICP iteration, the 3 x 3 SVD in float64 on the device
+    SubdivideMeshes, subdivide_packed, mesh_edges  every edge split at its midpoint, every face into four (csrc/subdivide.hip: one
+                                     launch forward, one gather backward, no atomics) over the unique edges of the face list built on
+                                     the device without a global sort (csrc/mesh_edges.hip, one host read)
     cot_laplacian, taubin_smoothing, taubin_smooth_packed  the cotangent Laplacian's entries and Taubin smoothing as gathers over the loss
                                      tables: no sparse matrix per step, no atomics; mesh_laplacian_smoothing "cot" / "cotcurv" are fused too
     stratified_depths                one jiggled depth per bin along every ray, the centres read in place (an expand stays an expand)
@@ -51,6 +54,7 @@ from .graph_conv import gather_scatter, graph_conv, graph_topology, topology_of_
 from .iou_box3d import box3d_overlap  # noqa: F401
 from .knn import knn_gather, knn_points  # noqa: F401
 from .marching_cubes import marching_cubes, marching_cubes_packed, marching_cubes_torch  # noqa: F401
+from .subdivide_meshes import MeshEdges, SubdivideMeshes, mesh_edges, subdivide_packed  # noqa: F401
 from .mesh_filtering import taubin_smooth_packed, taubin_smooth_torch, taubin_smoothing  # noqa: F401
 from .mesh_losses import (cot_laplacian, cot_laplacian_torch, cot_tables, mesh_edge_loss, mesh_laplacian_smoothing,  # noqa: F401
                           mesh_loss_topology, mesh_normal_consistency)

@@ -1,7 +1,8 @@
 /* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching), csrc/cubify.hip,
  * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip,
- * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points) and csrc/mesh_laplacian.hip (the cotangent
- * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing).
+ * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points), csrc/mesh_laplacian.hip (the cotangent
+ * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing), csrc/mesh_edges.hip (the unique edges of a face list) and
+ * csrc/subdivide.hip (SubdivideMeshes).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -316,6 +317,64 @@ int p3di_mesh_cot_laplacian_backward(const float* grad_loss, const float* d, con
 int p3di_mesh_taubin_smoothing(const float* verts, const int32_t* adj_offsets, const int32_t* adj, int64_t V, int64_t E, float lambd_c1,
                                float lambd_c, float mu_c1, float mu_c, float eps, int num_iter, float* scratch, float* out,
                                p3d_stream_t stream);
+
+/* Mesh edges (csrc/mesh_edges.hip): the unique edges of a packed face list and every face's three edge ids, the reference's
+ * Meshes._compute_edges_packed (structures/meshes.py:1036-1135) without a global sort.  faces (F, 3) int64 packed vertex ids,
+ * vert_first (N + 1) int32: the exclusive scan of the vertices per mesh, vert_first[N] == V.
+ *   corner 3 f + k names the edge OPPOSITE vertex k of face f: (v1, v2), (v2, v0), (v0, v1), as (lo, hi); a face that names a vertex
+ *   twice has a self edge (v, v), which is kept.  A corner one of whose ids is outside [0, V) is flagged and skipped by every kernel.
+ *   edges (3 F, 2) int32, the first E rows written: the unique (lo, hi) ascending by lo V + hi;  face_edges (F, 3) int32: the edge id
+ *   of every corner;  edge_mesh (3 F) int32: the mesh of lo;  edge_first (N + 1) int32 = row_offsets[vert_first[n]], edge_first[N] = E.
+ *   row_offsets (2 V + 1) int32: for v < V the edges with lo == v are the ids [row_offsets[v], row_offsets[v + 1]); the edges with
+ *   hi == v are hi_edges[row_offsets[V + v] - E .. row_offsets[V + v + 1] - E), ascending.  hi_edges (3 F) int32, E written.
+ *   record (4 + N) int64: E, 1 if an id was outside [0, V) else 0, the rows longer than P3D_MESH_EDGES_ROW_REGISTERS, the rows longer
+ *   than P3D_MESH_EDGES_ROW_LDS, then the edges of every mesh: what the caller reads, once.
+ * Rows: row v < V holds (hi, corner) of the corners with lo == v, row V + v holds (lo, corner) of the corners with hi == v; count
+ * (integer atomics) -> exclusive scan in scan blocks of P3D_MESH_EDGES_ITEMS rows -> fill (integer atomic tickets) -> every row sorted
+ * by its 64-bit keys, which removes the ticket order: a lane per row in registers up to P3D_MESH_EDGES_ROW_REGISTERS entries, a
+ * workgroup per row through LDS up to P3D_MESH_EDGES_ROW_LDS, a workgroup's rank sort over the row's own slots beyond; the long rows
+ * are listed by the scan and taken by P3D_MESH_EDGES_LONG_GROUPS workgroups in turns -> the runs of equal first halves are counted,
+ * scanned and emitted.  13 launches, no float anywhere, no host sync; the same result on every run.
+ * workspace: p3di_mesh_edges_workspace_bytes(V, F) bytes (smaller: P3D_ERR_WORKSPACE), 0 for sizes the entry refuses.
+ * V, F or N below 1, 6 F or 2 V + 1 beyond INT32_MAX, missing pointers: P3D_ERR_INVALID_ARG. */
+#define P3D_MESH_EDGES_BLOCK 256
+#define P3D_MESH_EDGES_ITEMS 1024
+#define P3D_MESH_EDGES_CARRY_BLOCK 1024
+#define P3D_MESH_EDGES_ROW_REGISTERS 16
+#define P3D_MESH_EDGES_ROW_LDS 2048
+#define P3D_MESH_EDGES_LONG_GROUPS 256
+size_t p3di_mesh_edges_workspace_bytes(int64_t V, int64_t F);
+int p3di_mesh_edges_build(const int64_t* faces, const int32_t* vert_first, int64_t V, int64_t F, int64_t N, void* workspace,
+                          size_t workspace_bytes, int32_t* edges, int32_t* face_edges, int32_t* edge_mesh, int32_t* edge_first,
+                          int32_t* row_offsets, int32_t* hi_edges, int64_t* record, p3d_stream_t stream);
+
+/* SubdivideMeshes (csrc/subdivide.hip): pytorch3d/ops/subdivide_meshes.py over the tables of p3di_mesh_edges_build and
+ * vert_first / face_first / edge_first (N + 1) int32.  Mesh n of the result has V_n + E_n vertices -- its old ones, then the midpoints
+ * of its edges in edge order -- and 4 F_n faces.
+ * p3di_subdivide_faces, one launch: rows [4 face_first[n] + k F_n, + F_n) hold block k of mesh n, face f of it as
+ *   k = 0: (v0, e2, e1), 1: (v1, e0, e2), 2: (v2, e1, e0), 3: (e0, e1, e2); a vertex v is written as v - vert_first[n], edge e as
+ *   V_n + e - edge_first[n] in faces_local, both plus vert_first[n] + edge_first[n] in faces_packed; (4 F, 3) int64, either may be
+ *   NULL.  With N == 1 this is the reference's subdivide_faces.
+ * p3di_subdivide_forward, one launch for up to two tensors (x1 NULL: one): x (B, V, D) float32 read through strides (batch, row,
+ *   element), out (B, V + E, D) contiguous; row vert_first[n] + edge_first[n] + r of out is row vert_first[n] + r of x for r < V_n and
+ *   (x[lo] + x[hi]) * 0.5f of edge edge_first[n] + r - V_n otherwise: one rounding, the bits of the reference's mean.  A lane per
+ *   element in output order, or per 16 bytes where D % 4 == 0 and base and strides allow it.  B > 1: the same tables for every b.
+ * p3di_subdivide_backward, one launch for both: g (B, V + E, D) and grad_x (B, V, D) contiguous,
+ *   grad_x[v] = g[row(v)] + 0.5f * (((+0 + g[row(e_0)]) + g[row(e_1)]) + ...), e_i the edges of v ascending -- its hi_edges list, then
+ *   its lo run; a self edge is in both.  A gather: no atomic, the same bits on every run and stream.
+ * Tables that break their contract give wrong numbers, never an access outside the arrays (ids and offsets are clamped).  Nothing
+ * to do (no row or D == 0): P3D_OK without a launch.  Negative sizes, (V + E) beyond INT32_MAX, B beyond 65535, missing pointers:
+ * P3D_ERR_INVALID_ARG.  No host sync. */
+#define P3D_SUBDIVIDE_MAX_GROUPS 8192
+int p3di_subdivide_faces(const int64_t* faces, const int32_t* face_edges, const int32_t* vert_first, const int32_t* face_first,
+                         const int32_t* edge_first, int64_t F, int64_t N, int64_t* faces_local, int64_t* faces_packed,
+                         p3d_stream_t stream);
+int p3di_subdivide_forward(const float* x0, const int64_t strides0[3], int64_t D0, float* out0, const float* x1,
+                           const int64_t strides1[3], int64_t D1, float* out1, const int32_t* edges, const int32_t* vert_first,
+                           const int32_t* edge_first, int64_t V, int64_t E, int64_t N, int64_t B, p3d_stream_t stream);
+int p3di_subdivide_backward(const float* g0, int64_t D0, float* grad_x0, const float* g1, int64_t D1, float* grad_x1,
+                            const int32_t* row_offsets, const int32_t* hi_edges, const int32_t* vert_first, const int32_t* edge_first,
+                            int64_t V, int64_t E, int64_t N, int64_t B, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -826,6 +826,37 @@ def _cubify(ref):
     return {"cubify": cubify}
 
 
+def _subdivide_meshes(ref):
+    """SubdivideMeshes.forward and SubdivideMeshes.subdivide_faces (ops/subdivide_meshes.py: two global sorts and a unique for the
+    edges, two argsorts, a scatter_add, bincounts, four gathers and host reads per call; no `_C` operator stands under it) ->
+    pytorch3d_amd.subdivide_meshes: csrc/mesh_edges.hip and csrc/subdivide.hip for float32 GPU meshes, the package's torch formulation
+    for the rest.  The methods are patched directly, as GraphConv.forward is, so `ico_sphere` subdivides through them unchanged.
+    PATCH_CALLS counts kernel calls as fused and the formulation as fallbacks."""
+    ours = _our("subdivide_meshes")
+    cls = ref.SubdivideMeshes
+
+    def forward(self, meshes, feats=None):
+        self._N = len(meshes)
+        if self.precomputed:
+            out = ours.subdivide_homogeneous(self, meshes, feats)
+        else:
+            out = ours.subdivide_heterogeneous(meshes, feats)
+        _count("SubdivideMeshes.forward", ours.kernel_path(meshes.verts_packed(), feats))
+        return out
+
+    def subdivide_faces(self, meshes):
+        out = ours.subdivide_faces(meshes)
+        _count("SubdivideMeshes.subdivide_faces", ours.edges_kernel_path(meshes.faces_packed(), meshes.verts_packed().shape[0]))
+        return out
+
+    for name, new in (("forward", forward), ("subdivide_faces", subdivide_faces)):
+        orig = getattr(cls, name)
+        new.__name__, new.__doc__, new.__wrapped__, new.__p3d_amd__ = name, orig.__doc__, orig, True
+        setattr(cls, name, new)
+        _PATCHED.append((cls, name, orig, new))
+    return {}
+
+
 def _marching_cubes(ref):
     """pytorch3d.ops.marching_cubes (a Python loop over the volumes, each with `_C.marching_cubes`, three host reads and a torch.unique
     on the GPU) -> pytorch3d_amd.marching_cubes: the batch at once.  The reference's pytorch3d.ops does not copy this name (there
@@ -886,6 +917,7 @@ _FUNCTION_PATCHES = (
     ("pytorch3d.ops.vert_align", ("pytorch3d.ops",), _vert_align),
     ("pytorch3d.ops.cubify", ("pytorch3d.ops",), _cubify),
     ("pytorch3d.ops.marching_cubes", ("pytorch3d.ops",), _marching_cubes),
+    ("pytorch3d.ops.subdivide_meshes", ("pytorch3d.ops",), _subdivide_meshes),
     ("pytorch3d.renderer.implicit.raymarching", (), _raymarchers),
     ("pytorch3d.renderer.implicit.renderer", (), _volume_sampler),
     ("pytorch3d.renderer.implicit.harmonic_embedding", (), _harmonic_embedding),

@@ -87,6 +87,24 @@ class PackedMeshes:
     def verts_packed_to_mesh_idx(self):
         return torch.repeat_interleave(torch.arange(self._N, device=self.device), self._num_verts)
 
+    def _edges(self):
+        """The MeshEdges of the batch (pytorch3d_amd.subdivide_meshes.mesh_edges: kept with the faces tensor)."""
+        from .subdivide_meshes import mesh_edges
+
+        return mesh_edges(self._faces_packed, self._nv_host, [int(f.shape[0]) for f in self._faces_list])
+
+    def edges_packed(self):
+        return self._edges().edges_packed()
+
+    def faces_packed_to_edges_packed(self):
+        return self._edges().faces_packed_to_edges_packed()
+
+    def num_edges_per_mesh(self):
+        return self._edges().num_edges_per_mesh()
+
+    def edges_packed_to_mesh_idx(self):
+        return self._edges().edges_packed_to_mesh_idx()
+
     def update_verts_packed(self, new_verts_packed):
         """Same topology, new vertex positions (like Meshes.update_padded, for camera transforms).  What is kept with the topology
         (the tables of pytorch3d_amd.mesh_losses) is handed on: the copy shares the __dict__ entries."""
