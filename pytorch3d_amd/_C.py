@@ -1048,6 +1048,74 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _nee
     return grad_p1, grad_p2
 
 
+def _knn_features_check(p1, p2, lengths1, lengths2, K, who):
+    """_knn_check for the entries of csrc/knn_features.hip: KNN_FEATURES_MIN_D <= D <= KNN_FEATURES_MAX_D."""
+    dev = _same_device(("p1", p1), ("p2", p2))
+    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != p2.shape[0] or p1.shape[2] != p2.shape[2]:
+        raise RuntimeError(f"{who}: p1 (N, P1, D) and p2 (N, P2, D) must share N and D")
+    if not _lib.KNN_FEATURES_MIN_D <= p1.shape[2] <= _lib.KNN_FEATURES_MAX_D or not 1 <= K <= _lib.KNN_MAX_K:
+        raise RuntimeError(f"{who}: the kernels take {_lib.KNN_FEATURES_MIN_D} <= D <= {_lib.KNN_FEATURES_MAX_D} and 1 <= K <= "
+                           f"{_lib.KNN_MAX_K}; pytorch3d_amd.knn.knn_points routes the rest")
+    out = []
+    for name, t in (("lengths1", lengths1), ("lengths2", lengths2)):
+        if t is not None:
+            _same_device(("p1", p1), (name, t))
+            if t.shape != (p1.shape[0],):
+                raise RuntimeError(f"{who}: {name} must have shape (N,)")
+            t = _c(t, torch.int64)
+        out.append(t)
+    return dev, out[0], out[1]
+
+
+def knn_features_idx(p1, p2, lengths1, lengths2, K, _out=None):
+    """knn_points_idx with norm 2 for feature clouds (csrc/knn_features.hip): (idx (N, P1, K) int64, dists (N, P1, K)), sorted
+    ascending by (dist, j), the bits of knn.torch_knn_forward.  _out: (idx, dists) buffers to write into -- the kernel writes every
+    entry."""
+    K = int(K)
+    dev, lengths1, lengths2 = _knn_features_check(p1, p2, lengths1, lengths2, K, "knn_features_idx")
+    p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
+    N, P1, D = p1.shape
+    P2 = p2.shape[1]
+    if _out is None:
+        idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+        dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    else:
+        idx, dists = _out
+        if (idx.shape != (N, P1, K) or dists.shape != (N, P1, K) or idx.dtype != torch.int64 or dists.dtype != torch.float32
+                or not idx.is_contiguous() or not dists.is_contiguous() or idx.device != dev or dists.device != dev):
+            raise RuntimeError("knn_features_idx: _out must be contiguous (N, P1, K) int64 and float32 tensors on the inputs' GPU")
+    nbytes = _lib.load().p3di_knn_features_forward_workspace_bytes(N, P2, D)
+    ws = _workspace(nbytes, dev)
+    _lib.call("p3di_knn_features_forward", "knn_features_idx", dev, p1, p2, lengths1, lengths2, N, P1, P2, D, K, idx, dists, ws, nbytes)
+    return idx, dists
+
+
+def knn_features_backward(p1, p2, lengths1, lengths2, idxs, grad_dists, _needs=(True, True), _out=None, accumulate_p2=False):
+    """knn_points_backward with norm 2 for feature clouds: (grad_p1 (N, P1, D), grad_p2 (N, P2, D)).  grad_p1 is a gather, the bits
+    of knn.torch_knn_backward; grad_p2 a scatter with float atomics.  _needs: which of the two to compute (the other is None); _out:
+    (grad_p1, grad_p2) buffers to write into; accumulate_p2 (with _out): the hits are added to what grad_p2 holds."""
+    _same_device(("p1", p1), ("idxs", idxs), ("grad_dists", grad_dists))
+    if idxs.dim() != 3 or idxs.shape[:2] != p1.shape[:2] or grad_dists.shape != idxs.shape:
+        raise RuntimeError("knn_features_backward: idxs and grad_dists must have shape (N, P1, K)")
+    K = int(idxs.shape[2])
+    dev, lengths1, lengths2 = _knn_features_check(p1, p2, lengths1, lengths2, K, "knn_features_backward")
+    p1, p2, idxs = _c(p1, torch.float32), _c(p2, torch.float32), _c(idxs, torch.int64)
+    g = grad_dists.to(torch.float32).contiguous()
+    if _out is None:
+        grad_p1 = torch.empty_like(p1) if _needs[0] else None
+        grad_p2 = torch.empty_like(p2) if _needs[1] else None
+    else:
+        grad_p1, grad_p2 = _out
+        for t, like in ((grad_p1, p1), (grad_p2, p2)):
+            if t is not None and (t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
+                raise RuntimeError("knn_features_backward: _out must be contiguous float32 tensors shaped like p1 and p2 on their GPU")
+    N, P1, D = p1.shape
+    flags = _lib.KNN_ACCUMULATE_P2 if accumulate_p2 else 0
+    _lib.call("p3di_knn_features_backward", "knn_features_backward", dev, p1, p2, lengths1, lengths2, idxs, g, N, P1, p2.shape[1], D, K,
+              flags, grad_p1, grad_p2)
+    return grad_p1, grad_p2
+
+
 # ----------------------------------------------------------------------------------------------
 # farthest point sampling and ball query (csrc/fps_ball.hip), behind the wrappers of pytorch3d_amd.sample_farthest_points /
 # pytorch3d_amd.ball_query (shim.EXPORTS), which come here for float32 GPU tensors with D in (2, 3).

@@ -1,8 +1,8 @@
 /* implicit_abi.h -- the C ABI of csrc/implicit.hip (sample_pdf and emission-absorption raymarching), csrc/cubify.hip,
  * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip,
  * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points), csrc/mesh_laplacian.hip (the cotangent
- * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing), csrc/mesh_edges.hip (the unique edges of a face list) and
- * csrc/subdivide.hip (SubdivideMeshes).
+ * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing), csrc/mesh_edges.hip (the unique edges of a face list),
+ * csrc/subdivide.hip (SubdivideMeshes) and csrc/knn_features.hip (nearest neighbours between clouds of feature points).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -375,6 +375,36 @@ int p3di_subdivide_forward(const float* x0, const int64_t strides0[3], int64_t D
 int p3di_subdivide_backward(const float* g0, int64_t D0, float* grad_x0, const float* g1, int64_t D1, float* grad_x1,
                             const int32_t* row_offsets, const int32_t* hi_edges, const int32_t* vert_first, const int32_t* edge_first,
                             int64_t V, int64_t E, int64_t N, int64_t B, p3d_stream_t stream);
+
+/* ---- nearest neighbours between clouds of feature points (csrc/knn_features.hip): p3d_knn_points_forward / _backward of
+ * include/p3d_amd.h at P3D_KNN_FEATURES_MIN_D <= D <= P3D_KNN_FEATURES_MAX_D, squared L2 (norm 2) only.
+ *
+ * p1 (N,P1,D), p2 (N,P2,D) contiguous f32; lengths1 / lengths2 (N) i64 or NULL (every cloud full; a length is clamped to [0, P]);
+ * 1 <= K <= P3D_KNN_MAX_K.  D or K outside that: P3D_ERR_UNSUPPORTED (the caller owns a formulation for the rest:
+ * pytorch3d_amd/knn.py); negative or overlong sizes, missing pointers: P3D_ERR_INVALID_ARG.  No host sync.
+ * Forward: for n and i < lengths1[n] the min(K, lengths2[n]) smallest dist(p1[n,i], p2[n,j]), j < lengths2[n], ascending by
+ * (dist, j) -- a tie goes to the smaller index.  dist is the contract's of p3d_knn_points_forward: per coordinate the difference,
+ * squared, accumulated in coordinate order, one float32 operation each, NOT fused -- the bits of pytorch3d_amd.knn.torch_knn_forward.
+ * idx (N,P1,K) i64, dists (N,P1,K) f32: every entry is written, 0 in both for rows i >= lengths1[n] and slots k >= lengths2[n]; no
+ * memset in front.  A NaN distance is never selected (a slot that finds nothing holds idx 0, dist +inf).
+ * How: a wave per 32 queries, tiles of 32 targets in LDS; |q|^2 + |y|^2 - 2 q.y with the cross term on v_mfma_f32_32x32x2_f32
+ * screens the pairs -- a pair is dropped only where that value minus a proven bound of its error (csrc/knn_features.hip has the
+ * derivation) still exceeds the query's current worst neighbour, a non-finite value never drops one -- and every other pair is
+ * evaluated by the arithmetic above from the staged rows.  The result does not depend on the screen, the tile or the launch shape.
+ * workspace: p3di_knn_features_forward_workspace_bytes(N, P2, D) bytes (|y|^2 of every p2 row, written by the same call); smaller
+ * or NULL with P2 > 0: P3D_ERR_WORKSPACE.
+ * Backward, the formulas of p3d_knn_points_backward with norm 2 and cloud_scale NULL: grad_p1 (N,P1,D), NULL to skip: a gather, one
+ * lane per (row, coordinate), k ascending, every entry written (the bits of torch_knn_backward).  grad_p2 (N,P2,D), NULL to skip:
+ * float atomics, lane = hit * D + coordinate; zero-filled first (by a kernel) unless flags has P3D_KNN_ACCUMULATE_P2. */
+#define P3D_KNN_FEATURES_MIN_D 4
+#define P3D_KNN_FEATURES_MAX_D 256
+size_t p3di_knn_features_forward_workspace_bytes(int64_t N, int64_t P2, int D);
+int p3di_knn_features_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
+                              int64_t P2, int D, int K, int64_t* idx, float* dists, void* workspace, size_t workspace_bytes,
+                              p3d_stream_t stream);
+int p3di_knn_features_backward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, const int64_t* idx,
+                               const float* grad_dists, int64_t N, int64_t P1, int64_t P2, int D, int K, unsigned flags,
+                               float* grad_p1, float* grad_p2, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

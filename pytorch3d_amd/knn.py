@@ -8,10 +8,13 @@ or L1 --, idx (N, P1, K) int64 and knn (N, P1, K, D) or None.  For each query th
 ascending by (dist, j): a tie goes to the smaller index.  Rows past lengths1[n] and slots past lengths2[n] hold 0 in both.  `version`
 is accepted and ignored; the result is always sorted.  One autograd node; `lengths=None` never waits for the device.
 
-float32 GPU tensors with D in {2, 3} and K <= 32 take the kernels (include/p3d_amd.h).  Everything else -- CPU tensors, float64,
-other D, larger K -- takes the torch formulation below: the same contract, the (P1, P2) distances computed in bounded chunks,
-differentiated by an explicit backward with the kernels' formulas.  The backward's scatter into grad_p2 uses float atomics, or,
-under torch.use_deterministic_algorithms(True), the ordered sum of csrc/ordered_sum.h (the same bits on every run and stream).
+float32 GPU tensors with D in {2, 3} and K <= 32 take the kernels of csrc/knn.hip (include/p3d_amd.h).  Feature clouds -- float32
+GPU tensors with 4 <= D <= 256, K <= 32 and norm 2 -- take csrc/knn_features.hip: a screen of the pairs on the matrix instruction
+and the contract's arithmetic for those that pass, the bits of the torch formulation.  Everything else -- CPU tensors, float64, D = 1
+or D > 256, L1 at D > 3, larger K -- takes the torch formulation below: the same contract, the (P1, P2) distances computed in
+bounded chunks, differentiated by an explicit backward with the kernels' formulas.  The backward's scatter into grad_p2 uses float
+atomics, or, under torch.use_deterministic_algorithms(True), the ordered sum of csrc/ordered_sum.h at D in {2, 3} and the torch
+formulation's backward for feature clouds (the same bits on every run and stream).
 """
 from collections import namedtuple
 
@@ -29,6 +32,13 @@ def kernel_path(p1, p2, K):
     return (torch.is_tensor(p1) and torch.is_tensor(p2) and p1.is_cuda and p2.is_cuda and p1.device == p2.device
             and p1.dtype == torch.float32 and p2.dtype == torch.float32 and p1.dim() == 3 and p2.dim() == 3
             and p1.shape[2] in (2, 3) and 1 <= K <= _lib.KNN_MAX_K)
+
+
+def feature_kernel_path(p1, p2, K, norm=2):
+    """Whether knn_points(p1, p2, K=K, norm=norm) runs csrc/knn_features.hip."""
+    return (torch.is_tensor(p1) and torch.is_tensor(p2) and p1.is_cuda and p2.is_cuda and p1.device == p2.device
+            and p1.dtype == torch.float32 and p2.dtype == torch.float32 and p1.dim() == 3 and p2.dim() == 3
+            and _lib.KNN_FEATURES_MIN_D <= p1.shape[2] <= _lib.KNN_FEATURES_MAX_D and 1 <= K <= _lib.KNN_MAX_K and norm == 2)
 
 
 def _lengths_arg(lengths, N, device, name):
@@ -137,8 +147,11 @@ def backward_kernels(p1, p2, lengths1, lengths2, idx, K, norm, grad_dists, cloud
 class _KnnPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p1, p2, lengths1, lengths2, K, norm, fused):
-        if fused:
+        """fused: "points" (csrc/knn.hip), "features" (csrc/knn_features.hip) or None (the torch formulation)."""
+        if fused == "points":
             idx, dists = _C.knn_points_idx(p1, p2, lengths1, lengths2, norm, K, -1)
+        elif fused == "features":
+            idx, dists = _C.knn_features_idx(p1, p2, lengths1, lengths2, K)
         else:
             idx, dists = torch_knn_forward(p1, p2, lengths1, lengths2, norm, K)
         ctx.save_for_backward(p1, p2, idx)
@@ -152,9 +165,11 @@ class _KnnPoints(torch.autograd.Function):
     def backward(ctx, grad_dists, _grad_idx):
         p1, p2, idx = ctx.saved_tensors
         lengths1, lengths2 = ctx.lengths
-        if ctx.fused:
+        if ctx.fused == "points":
             grad_p1, grad_p2 = _C.knn_points_backward(p1, p2, lengths1, lengths2, idx, ctx.norm, grad_dists,
                                                       _needs=ctx.needs_input_grad[:2])
+        elif ctx.fused == "features" and not _C._ordered():
+            grad_p1, grad_p2 = _C.knn_features_backward(p1, p2, lengths1, lengths2, idx, grad_dists, _needs=ctx.needs_input_grad[:2])
         else:
             grad_p1, grad_p2 = torch_knn_backward(p1, p2, lengths1, lengths2, idx, ctx.norm, grad_dists)
         return grad_p1, grad_p2, None, None, None, None, None
@@ -176,7 +191,7 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     N = p1.shape[0]
     lengths1 = _lengths_arg(lengths1, N, p1.device, "lengths1")
     lengths2 = _lengths_arg(lengths2, N, p1.device, "lengths2")
-    fused = kernel_path(p1, p2, K)
+    fused = "points" if kernel_path(p1, p2, K) else ("features" if feature_kernel_path(p1, p2, K, norm) else None)
     if not fused and p1.dtype != p2.dtype:
         p2 = p2.to(p1.dtype)
     dists, idx = _KnnPoints.apply(p1, p2, lengths1, lengths2, K, int(norm), fused)

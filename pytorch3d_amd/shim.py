@@ -67,8 +67,11 @@ reference classes runs on them end to end:
                                                                  one vertex twice go to the reference's functions
     ops.knn.knn_points / loss.chamfer.chamfer_distance        -> csrc/knn.hip: brute-force nearest neighbours, one lane per query;
                                                                  chamfer without normals is one autograd node with no host
-                                                                 sync; inputs the kernels do not take go to this package's torch
-                                                                 formulation (`_C.knn_points_idx` itself stays a stub that raises)
+                                                                 sync; feature clouds (4 <= D <= 256, norm 2: EdgeConv graphs,
+                                                                 descriptor matching) -> csrc/knn_features.hip, a matrix-instruction
+                                                                 screen with an exact rescore; inputs the kernels do not take go to
+                                                                 this package's torch formulation (`_C.knn_points_idx` itself stays
+                                                                 a stub that raises)
     loss.point_mesh_distance.point_mesh_face_distance / point_mesh_edge_distance -> csrc/point_mesh.hip: one autograd node each (face /
                                                                  edge gather, two fused brute-force forwards with fixed-tree sums,
                                                                  two backward kernels, the vertex scatter) and no host sync; other
@@ -538,8 +541,9 @@ def _taubin_smoothing(ref):
 
 
 def _knn_points(ref):
-    """csrc/knn.hip for float32 GPU clouds with D in {2, 3} and K <= 32.  The reference's own function ends in `_C.knn_points_idx`,
-    which stays a stub that raises."""
+    """csrc/knn.hip for float32 GPU clouds with D in {2, 3} and K <= 32, csrc/knn_features.hip for 4 <= D <= 256 with norm 2 (counted
+    with the formulation: the count says kernel_path).  The reference's own function ends in `_C.knn_points_idx`, which stays a stub
+    that raises."""
     ours_knn = _our("knn")
 
     def knn_points(p1, p2, lengths1=None, lengths2=None, norm=2, K=1, version=-1, return_nn=False, return_sorted=True):
