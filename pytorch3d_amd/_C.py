@@ -1025,6 +1025,25 @@ def knn_points_idx(p1, p2, lengths1, lengths2, norm, K, version=-1, _out=None):
     return idx, dists
 
 
+def knn_grid_idx(p1, p2, lengths1, lengths2, K, occupancy=0):
+    """knn_points_idx with norm 2 at D = 3 through a uniform grid per cloud (csrc/knn_grid.hip): the same (idx, dists), bit for bit,
+    without the scan of all pairs.  occupancy: the target number of points per grid cell, 0 for the library's default; it changes
+    the time, never the result.  No host sync."""
+    K, occupancy = int(K), int(occupancy)
+    dev, lengths1, lengths2 = _knn_check(p1, p2, lengths1, lengths2, K, "knn_grid_idx")
+    if p1.shape[2] != 3 or occupancy < 0:
+        raise RuntimeError("knn_grid_idx: the grid search takes D = 3 and occupancy >= 0; knn_points_idx takes D = 2")
+    p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
+    N, P1, D = p1.shape
+    P2 = p2.shape[1]
+    idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    nbytes = _lib.load().p3di_knn_grid_forward_workspace_bytes(N, P1, P2)
+    ws = _workspace(nbytes, dev)
+    _lib.call("p3di_knn_grid_forward", "knn_grid_idx", dev, p1, p2, lengths1, lengths2, N, P1, P2, D, K, occupancy, idx, dists, ws, nbytes)
+    return idx, dists
+
+
 def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _needs=(True, True)):
     """KNearestNeighborBackward (knn.h): (grad_p1 (N, P1, D), grad_p2 (N, P2, D)).  grad_p1 is a gather; grad_p2 a scatter with
     float atomics or, under torch.use_deterministic_algorithms(True), the ordered sum.  _needs (not part of the reference's

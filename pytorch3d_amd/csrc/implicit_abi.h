@@ -2,7 +2,8 @@
  * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip,
  * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points), csrc/mesh_laplacian.hip (the cotangent
  * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing), csrc/mesh_edges.hip (the unique edges of a face list),
- * csrc/subdivide.hip (SubdivideMeshes) and csrc/knn_features.hip (nearest neighbours between clouds of feature points).
+ * csrc/subdivide.hip (SubdivideMeshes), csrc/knn_features.hip (nearest neighbours between clouds of feature points) and
+ * csrc/knn_grid.hip (nearest neighbours between large 3D clouds through a uniform grid).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -405,6 +406,25 @@ int p3di_knn_features_forward(const float* p1, const float* p2, const int64_t* l
 int p3di_knn_features_backward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, const int64_t* idx,
                                const float* grad_dists, int64_t N, int64_t P1, int64_t P2, int D, int K, unsigned flags,
                                float* grad_p1, float* grad_p2, p3d_stream_t stream);
+
+/* ---- nearest neighbours between large 3D clouds through a uniform grid (csrc/knn_grid.hip): p3d_knn_points_forward of
+ * include/p3d_amd.h at D = 3, norm 2, and the SAME idx and dists, bit for bit -- the same distance arithmetic, the (dist, j) order,
+ * the same zeros in padding rows and slots -- where the scan of all pairs is quadratic.  The grid only decides which pairs are never
+ * looked at: a query stops when its K-th distance is strictly below a proven lower bound of the distance to every cell it has not
+ * seen (the proof is at stop_bound in the source); a query that cannot stop early (NaN, lengths2[n] < K, a cloud that an outlier
+ * squeezes into one cell) scans its whole cloud.  The grid of cloud n is chosen on the device from the bounding box of p2[n],
+ * lengths2[n] and `occupancy`, the target number of points per cell (0: P3D_KNN_GRID_OCCUPANCY), with at most
+ * min(max(P2, 1), P3D_KNN_GRID_MAX_CELLS) cells; no host sync.  The order of the points inside a cell is decided by integer atomics
+ * and differs from run to run; the result does not.  D != 3 or K > P3D_KNN_MAX_K: P3D_ERR_UNSUPPORTED.
+ * workspace: p3di_knn_grid_forward_workspace_bytes(N, P1, P2) bytes, every byte read was written by the same call; smaller:
+ * P3D_ERR_WORKSPACE. */
+#define P3D_KNN_GRID_OCCUPANCY 8
+#define P3D_KNN_GRID_TILE 512
+#define P3D_KNN_GRID_MAX_CELLS 4194304
+size_t p3di_knn_grid_forward_workspace_bytes(int64_t N, int64_t P1, int64_t P2);
+int p3di_knn_grid_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
+                          int64_t P2, int D, int K, int occupancy, int64_t* idx, float* dists, void* workspace,
+                          size_t workspace_bytes, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

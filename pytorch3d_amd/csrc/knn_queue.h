@@ -42,4 +42,34 @@ struct Queue<1> {
   __device__ __forceinline__ void init() { d[0] = pos_inf(), j[0] = -1; }
 };
 
+// The queue for candidates that arrive in NO PARTICULAR j ORDER (knn_grid.hip): the KQ smallest pairs in the lexicographic order
+// (distance, index), whatever the order of the offers -- provided no pair is offered twice.  `after(s, dn, jn)`: slot s sorts behind
+// the candidate.  The shift is Queue's with `after` in place of `>`.  An empty slot is (+inf, -1): it sorts behind every finite
+// distance, and a candidate of +inf or NaN is behind nothing, so it is never taken (as in Queue).  KQ = 1 is the plain compare.
+template <int KQ>
+struct LexQueue {
+  float d[KQ];
+  int j[KQ];
+  __device__ __forceinline__ void init() {
+#pragma unroll
+    for (int s = 0; s < KQ; ++s) d[s] = pos_inf(), j[s] = -1;
+  }
+  __device__ __forceinline__ bool after(int s, float dn, int jn) const { return d[s] > dn || (d[s] == dn && j[s] > jn); }
+  __device__ __forceinline__ bool wants(float dn, int jn) const { return after(KQ - 1, dn, jn); }
+  // a lane that does not want the candidate has no slot behind it (the slots ascend): nothing changes there
+  __device__ __forceinline__ void insert(float dn, int jn) {
+    bool behind = after(KQ - 1, dn, jn);  // of slot s; slot s - 1 is still untouched when slot s is written
+#pragma unroll
+    for (int s = KQ - 1; s >= 0; --s) {
+      const bool shift = s > 0 && after(s > 0 ? s - 1 : 0, dn, jn);
+      const bool here = !shift && behind;
+      behind = shift;
+      const float dl = d[s > 0 ? s - 1 : 0];
+      const int jl = j[s > 0 ? s - 1 : 0];
+      d[s] = shift ? dl : (here ? dn : d[s]);
+      j[s] = shift ? jl : (here ? jn : j[s]);
+    }
+  }
+};
+
 }  // namespace p3d

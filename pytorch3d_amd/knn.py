@@ -8,7 +8,10 @@ or L1 --, idx (N, P1, K) int64 and knn (N, P1, K, D) or None.  For each query th
 ascending by (dist, j): a tie goes to the smaller index.  Rows past lengths1[n] and slots past lengths2[n] hold 0 in both.  `version`
 is accepted and ignored; the result is always sorted.  One autograd node; `lengths=None` never waits for the device.
 
-float32 GPU tensors with D in {2, 3} and K <= 32 take the kernels of csrc/knn.hip (include/p3d_amd.h).  Feature clouds -- float32
+float32 GPU tensors with D in {2, 3} and K <= 32 take the kernels of csrc/knn.hip (include/p3d_amd.h): every pair is looked at.
+Where GRID_MIN_P2 is a number, 3D clouds with norm 2 and p2.shape[1] >= GRID_MIN_P2 take csrc/knn_grid.hip instead: a uniform grid
+per cloud, built on the device, and a search that grows a box of cells around 64 neighbouring queries until a proven bound says that
+nothing outside can enter a queue -- the same idx and dists, bit for bit, and the backward of csrc/knn.hip.  Feature clouds -- float32
 GPU tensors with 4 <= D <= 256, K <= 32 and norm 2 -- take csrc/knn_features.hip: a screen of the pairs on the matrix instruction
 and the contract's arithmetic for those that pass, the bits of the torch formulation.  Everything else -- CPU tensors, float64, D = 1
 or D > 256, L1 at D > 3, larger K -- takes the torch formulation below: the same contract, the (P1, P2) distances computed in
@@ -25,6 +28,11 @@ from . import _C, _lib
 _KNN = namedtuple("KNN", "dists idx knn")
 
 CHUNK_ELEMENTS = 1 << 22  # the torch formulation keeps at most this many distances (N x rows x P2) alive at a time
+# The padded P2 from which knn_points takes the grid search; None: never (the entry stays reachable as _C.knn_grid_idx).
+# The rule: the smallest swept P from which the grid beats the scan of all pairs on all three distributions and K.  There is none
+# (profiles/knn_grid_mi355x.txt): uniform and surface clouds win from 262 144 points on, 9 - 56 x at 10^6, but a cloud with far
+# outliers loses at every size.  Callers who know their clouds set a number here, e.g. 262144.
+GRID_MIN_P2 = None
 
 
 def kernel_path(p1, p2, K):
@@ -32,6 +40,11 @@ def kernel_path(p1, p2, K):
     return (torch.is_tensor(p1) and torch.is_tensor(p2) and p1.is_cuda and p2.is_cuda and p1.device == p2.device
             and p1.dtype == torch.float32 and p2.dtype == torch.float32 and p1.dim() == 3 and p2.dim() == 3
             and p1.shape[2] in (2, 3) and 1 <= K <= _lib.KNN_MAX_K)
+
+
+def grid_kernel_path(p1, p2, K, norm=2):
+    """Whether knn_points(p1, p2, K=K, norm=norm) runs csrc/knn_grid.hip (its backward: csrc/knn.hip's)."""
+    return (GRID_MIN_P2 is not None and kernel_path(p1, p2, K) and p1.shape[2] == 3 and norm == 2 and p2.shape[1] >= GRID_MIN_P2)
 
 
 def feature_kernel_path(p1, p2, K, norm=2):
@@ -147,8 +160,11 @@ def backward_kernels(p1, p2, lengths1, lengths2, idx, K, norm, grad_dists, cloud
 class _KnnPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p1, p2, lengths1, lengths2, K, norm, fused):
-        """fused: "points" (csrc/knn.hip), "features" (csrc/knn_features.hip) or None (the torch formulation)."""
-        if fused == "points":
+        """fused: "points" (csrc/knn.hip), "grid" (csrc/knn_grid.hip; the backward of "points"), "features" (csrc/knn_features.hip)
+        or None (the torch formulation)."""
+        if fused == "grid":
+            idx, dists = _C.knn_grid_idx(p1, p2, lengths1, lengths2, K)
+        elif fused == "points":
             idx, dists = _C.knn_points_idx(p1, p2, lengths1, lengths2, norm, K, -1)
         elif fused == "features":
             idx, dists = _C.knn_features_idx(p1, p2, lengths1, lengths2, K)
@@ -165,7 +181,7 @@ class _KnnPoints(torch.autograd.Function):
     def backward(ctx, grad_dists, _grad_idx):
         p1, p2, idx = ctx.saved_tensors
         lengths1, lengths2 = ctx.lengths
-        if ctx.fused == "points":
+        if ctx.fused in ("points", "grid"):
             grad_p1, grad_p2 = _C.knn_points_backward(p1, p2, lengths1, lengths2, idx, ctx.norm, grad_dists,
                                                       _needs=ctx.needs_input_grad[:2])
         elif ctx.fused == "features" and not _C._ordered():
@@ -191,7 +207,14 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     N = p1.shape[0]
     lengths1 = _lengths_arg(lengths1, N, p1.device, "lengths1")
     lengths2 = _lengths_arg(lengths2, N, p1.device, "lengths2")
-    fused = "points" if kernel_path(p1, p2, K) else ("features" if feature_kernel_path(p1, p2, K, norm) else None)
+    if grid_kernel_path(p1, p2, K, norm):
+        fused = "grid"
+    elif kernel_path(p1, p2, K):
+        fused = "points"
+    elif feature_kernel_path(p1, p2, K, norm):
+        fused = "features"
+    else:
+        fused = None
     if not fused and p1.dtype != p2.dtype:
         p2 = p2.to(p1.dtype)
     dists, idx = _KnnPoints.apply(p1, p2, lengths1, lengths2, K, int(norm), fused)

@@ -69,7 +69,9 @@ reference classes runs on them end to end:
                                                                  chamfer without normals is one autograd node with no host
                                                                  sync; feature clouds (4 <= D <= 256, norm 2: EdgeConv graphs,
                                                                  descriptor matching) -> csrc/knn_features.hip, a matrix-instruction
-                                                                 screen with an exact rescore; inputs the kernels do not take go to
+                                                                 screen with an exact rescore; 3D clouds of knn.GRID_MIN_P2 points
+                                                                 or more (None: never, the setting as measured) -> csrc/knn_grid.hip,
+                                                                 the same bits through a uniform grid; inputs the kernels do not take go to
                                                                  this package's torch formulation (`_C.knn_points_idx` itself stays
                                                                  a stub that raises)
     loss.point_mesh_distance.point_mesh_face_distance / point_mesh_edge_distance -> csrc/point_mesh.hip: one autograd node each (face /
