@@ -1067,6 +1067,81 @@ def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _nee
     return grad_p1, grad_p2
 
 
+# ----------------------------------------------------------------------------------------------
+# chamfer_distance with normals (csrc/chamfer_normals.hip, the contract: csrc/implicit_abi.h), behind pytorch3d_amd.chamfer.
+POINT_REDUCTIONS = {None: 0, "sum": 1, "mean": 2}
+
+
+def _chamfer_normals_check(who, x, y, x_normals, y_normals, x_lengths, y_lengths):
+    dev = _same_device(("x", x), ("y", y), ("x_normals", x_normals), ("y_normals", y_normals))
+    if (x.dim() != 3 or y.dim() != 3 or x.shape[2] != 3 or y.shape[2] != 3 or x.shape[0] != y.shape[0]
+            or x_normals.shape != x.shape or y_normals.shape != y.shape):
+        raise RuntimeError(f"{who}: the kernels take x (N, P1, 3), y (N, P2, 3) and normals of those shapes, got {tuple(x.shape)}, "
+                           f"{tuple(y.shape)}, {tuple(x_normals.shape)} and {tuple(y_normals.shape)}")
+    lengths = tuple(_int64_arg(t, x.shape[0], dev, name, who) for name, t in (("x_lengths", x_lengths), ("y_lengths", y_lengths)))
+    return (dev,) + tuple(_c(t, torch.float32) for t in (x, y, x_normals, y_normals)) + lengths
+
+
+def chamfer_normals_forward(x, y, x_normals, y_normals, x_lengths=None, y_lengths=None, weights=None, norm=2, abs_cosine=True,
+                            single_directional=False, point_reduction="mean", split=0):
+    """p3di_chamfer_normals_forward: (idx_x (N, P1), idx_y (N, P2) or None for single_directional, out).  out for point_reduction
+    None: the per-point terms (dist_x, normal_x, dist_y, normal_y), the last two None for single_directional; for "sum" / "mean":
+    sums (N, 2), per cloud the distance loss and the normal loss.  split: waves per workgroup, 0 (the launch decides), 1, 2, 4, 8.
+    One launch plus one for the sums; no host sync."""
+    who = "chamfer_normals_forward"
+    dev, x, y, x_normals, y_normals, x_lengths, y_lengths = _chamfer_normals_check(who, x, y, x_normals, y_normals, x_lengths, y_lengths)
+    N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
+    if weights is not None:
+        _same_device(("x", x), ("weights", weights))
+        if weights.shape != (N,):
+            raise RuntimeError(f"{who}: weights must have shape (N,)")
+        weights = _c(weights, torch.float32)
+    both = not single_directional
+
+    def new(P, dtype, wanted=True):
+        return torch.empty((N, P), dtype=dtype, device=dev) if wanted else None
+
+    idx_x, idx_y = new(P1, torch.int64), new(P2, torch.int64, both)
+    per_point = point_reduction is None
+    terms = (new(P1, torch.float32, per_point), new(P1, torch.float32, per_point), new(P2, torch.float32, per_point and both),
+             new(P2, torch.float32, per_point and both))
+    sums = None if per_point else torch.empty((N, 2), dtype=torch.float32, device=dev)
+    nbytes = 0 if per_point else _lib.load().p3di_chamfer_normals_forward_workspace_bytes(N, P1, P2)
+    ws = None if per_point else _workspace(nbytes, dev)
+    _lib.call("p3di_chamfer_normals_forward", who, dev, x, y, x_normals, y_normals, x_lengths, y_lengths, weights, N, P1, P2, int(norm),
+              1 if abs_cosine else 0, 0 if both else 1, POINT_REDUCTIONS[point_reduction], int(split), idx_x, idx_y, *terms, sums, ws, nbytes)
+    return idx_x, idx_y, (terms if per_point else sums)
+
+
+def chamfer_normals_backward(x, y, x_normals, y_normals, x_lengths, y_lengths, idx_x, idx_y, weights, cloud_grad, grad_terms, norm=2,
+                             abs_cosine=True, single_directional=False, point_mean=False, needs=(True, True, True, True)):
+    """p3di_chamfer_normals_backward: (grad_x, grad_y, grad_x_normals, grad_y_normals), None where `needs` says so.  cloud_grad
+    (2, N) float32 or None: the gradients of the forward's sums (N, 2), transposed; grad_terms: the four per-point upstream
+    gradients in the order of the forward's terms, each (N, P) float32 or None (1); weights and point_mean as in the forward.
+    Two launches; the far side's sums use float atomics."""
+    who = "chamfer_normals_backward"
+    dev, x, y, x_normals, y_normals, x_lengths, y_lengths = _chamfer_normals_check(who, x, y, x_normals, y_normals, x_lengths, y_lengths)
+    N, P1, P2 = x.shape[0], x.shape[1], y.shape[1]
+    if idx_x.shape != (N, P1) or (not single_directional and (idx_y is None or idx_y.shape != (N, P2))):
+        raise RuntimeError(f"{who}: idx_x (N, P1) and idx_y (N, P2) are the forward's")
+    for name, t, shape in (("weights", weights, (N,)), ("cloud_grad", cloud_grad, (2, N))):
+        if t is not None and (t.shape != shape or t.device != dev):
+            raise RuntimeError(f"{who}: {name} must have shape {shape} on the clouds' GPU")
+    weights = None if weights is None else _c(weights, torch.float32)
+    cloud_grad = None if cloud_grad is None else _c(cloud_grad, torch.float32)
+    shapes = ((N, P1), (N, P1), (N, P2), (N, P2))
+    if any(g is not None and g.shape != s for g, s in zip(grad_terms, shapes)):
+        raise RuntimeError(f"{who}: a per-point gradient has the shape of its term, (N, P)")
+    grad_terms = [None if g is None else _c(g, torch.float32) for g in grad_terms]
+    grads = [torch.empty_like(t) if need else None for t, need in zip((x, y, x_normals, y_normals), needs)]
+    if N * (P1 + P2) and (P1 == 0 or P2 == 0):
+        return tuple(None if g is None else g.zero_() for g in grads)
+    _lib.call("p3di_chamfer_normals_backward", who, dev, x, y, x_normals, y_normals, x_lengths, y_lengths, _c(idx_x, torch.int64),
+              None if idx_y is None else _c(idx_y, torch.int64), weights, cloud_grad, *grad_terms, N, P1, P2, int(norm), 1 if abs_cosine else 0,
+              1 if single_directional else 0, 1 if point_mean else 0, *grads)
+    return tuple(grads)
+
+
 def _knn_features_check(p1, p2, lengths1, lengths2, K, who):
     """_knn_check for the entries of csrc/knn_features.hip: KNN_FEATURES_MIN_D <= D <= KNN_FEATURES_MAX_D."""
     dev = _same_device(("p1", p1), ("p2", p2))

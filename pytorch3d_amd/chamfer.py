@@ -14,9 +14,17 @@ launches and three host syncs; here nothing waits for the device, except the ref
 are given.  (A length above P is clamped by the kernels; the "A length value was too long" check runs for CPU tensors only, where it
 costs nothing.)
 
-With normals, or point_reduction "max" / None, and for every input the kernels do not take (CPU, float64, other D), the indices and
-distances come from pytorch3d_amd.knn.knn_points -- kernels where they apply, its torch formulation otherwise -- and the rest is
-torch arithmetic differentiated by autograd.
+With BOTH normals and point_reduction "sum", "mean" or None, float32 GPU clouds with D = 3 are one autograd node for (loss,
+loss_normals) on csrc/chamfer_normals.hip: one launch scans both directions (a workgroup of 64 queries and 1, 2, 4 or 8 waves that
+split the far cloud, chosen from the number of workgroups), gathers the far normal at the winner and forms both terms with mask and
+weight; one launch adds the clouds' sums in the fixed order; the backward is a launch that writes every entry of the four
+gradients with the rows' own terms and one that adds the far sides' with float atomics.  The cosine and its gradient are
+F.cosine_similarity's (eps 1e-6), operation for operation.  Under torch.use_deterministic_algorithms(True), or when `weights` asks
+for a gradient, the call takes the general form below.
+
+With one normal, point_reduction "max", or None without normals, and for every input the kernels do not take (CPU, float64, other
+D), the indices and distances come from pytorch3d_amd.knn.knn_points -- kernels where they apply, its torch formulation otherwise --
+and the rest is torch arithmetic differentiated by autograd.
 """
 import torch
 import torch.nn.functional as F
@@ -143,6 +151,66 @@ class _ChamferFused(torch.autograd.Function):
         return gx, gy, None, None, None, None, None, None, None
 
 
+# ---- the node with normals -------------------------------------------------------------------------------------------------------
+def fused_normals_path(x, y, x_normals, y_normals, point_reduction):
+    """Whether chamfer_distance on these (tensor) inputs is the single autograd node of csrc/chamfer_normals.hip: both normals,
+    float32 on the clouds' GPU, D = 3, no empty dimension, point_reduction "mean" / "sum" / None, and not under the strict
+    deterministic flag (its far-side sums are float atomics)."""
+    if x_normals is None or y_normals is None or point_reduction == "max" or not _knn.kernel_path(x, y, 1) or _C._ordered():
+        return False
+    ok = all(torch.is_tensor(t) and t.dtype == torch.float32 and t.device == x.device for t in (x_normals, y_normals))
+    return (ok and x.shape[2] == 3 and x_normals.shape == x.shape and y_normals.shape == y.shape and x.shape[0] == y.shape[0]
+            and min(x.shape[0], x.shape[1], y.shape[1]) > 0)
+
+
+class _ChamferNormalsFused(torch.autograd.Function):
+    """x, y and their normals float32 (N, P, 3) on one GPU; lengths int64 on that GPU or None; weights float32 (N,) or None.
+    Returns (loss, loss_normals) -- per cloud (N,) for batch_reduction None, else 0-dim -- or, for point_reduction None, the
+    per-point terms (dist_x, normal_x) for single_directional and (dist_x, dist_y, normal_x, normal_y) otherwise."""
+
+    @staticmethod
+    def forward(ctx, x, y, x_normals, y_normals, x_lengths, y_lengths, weights, norm, point_reduction, single_directional,
+                batch_reduction, abs_cosine):
+        idx_x, idx_y, out = _C.chamfer_normals_forward(x, y, x_normals, y_normals, x_lengths, y_lengths, weights, norm, abs_cosine,
+                                                       single_directional, point_reduction)
+        ctx.save_for_backward(x, y, x_normals, y_normals, idx_x, idx_y)
+        div = None
+        if point_reduction is None:
+            result = (out[0], out[1]) if single_directional else (out[0], out[2], out[1], out[3])
+        elif batch_reduction is None:
+            result = (out[:, 0], out[:, 1])
+        else:
+            total = out.sum(0)
+            if batch_reduction == "mean":
+                # a tensor: a quotient by a Python number is a product with its rounded reciprocal on the GPU
+                div = weights.sum() if weights is not None else torch.full((), float(max(x.shape[0], 1)), device=x.device)
+                total = total / div
+            result = (total[0], total[1])
+        ctx.aux = (x_lengths, y_lengths, weights, div)
+        ctx.args = (norm, point_reduction, single_directional, batch_reduction is not None, abs_cosine)
+        return result
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        x, y, x_normals, y_normals, idx_x, idx_y = ctx.saved_tensors
+        x_lengths, y_lengths, weights, div = ctx.aux
+        norm, point_reduction, single, reduced, abs_cosine = ctx.args
+        N, dev = x.shape[0], x.device
+        with torch.cuda.device(dev):
+            if point_reduction is None:  # the order of the forward's terms: dist_x, normal_x, dist_y, normal_y
+                cloud_grad = None
+                terms = (grads[0], grads[1], None, None) if single else (grads[0], grads[2], grads[1], grads[3])
+            else:
+                cloud_grad = torch.stack([g.to(device=dev, dtype=torch.float32) for g in grads])  # (2,) or (2, N)
+                if reduced:
+                    cloud_grad = (cloud_grad if div is None else cloud_grad / div)[:, None].expand(2, N)
+                terms = (None, None, None, None)
+            out = _C.chamfer_normals_backward(x, y, x_normals, y_normals, x_lengths, y_lengths, idx_x, idx_y, weights, cloud_grad, terms,
+                                              norm, abs_cosine, single, point_reduction == "mean", ctx.needs_input_grad[:4])
+        return out + (None,) * 8
+
+
 # ---- the general form ------------------------------------------------------------------------------------------------------------
 def _rows_outside(lengths, N, P, device):
     return None if lengths is None else torch.arange(P, device=device)[None, :] >= lengths.to(device)[:, None]
@@ -234,6 +302,18 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
         w = None if weights is None else weights.to(device=dev, dtype=torch.float32).contiguous()
         loss = _ChamferFused.apply(x, y, xl, yl, w, int(norm), point_reduction == "mean", bool(single_directional), batch_reduction)
         return loss, None
+
+    if (not zero_weights and fused_normals_path(x, y, x_normals, y_normals, point_reduction)
+            and not (weights is not None and weights.requires_grad)):  # a gradient for the weights is the general form's
+        dev = x.device
+        xl = None if x_lengths is None else x_lengths.to(device=dev, dtype=torch.int64).contiguous()
+        yl = None if y_lengths is None else y_lengths.to(device=dev, dtype=torch.int64).contiguous()
+        w = None if weights is None else weights.to(device=dev, dtype=torch.float32).contiguous()
+        out = _ChamferNormalsFused.apply(x, y, x_normals, y_normals, xl, yl, w, int(norm), point_reduction, bool(single_directional),
+                                         batch_reduction, bool(abs_cosine))
+        if point_reduction is None and not single_directional:
+            return (out[0], out[1]), (out[2], out[3])
+        return out[0], out[1]
 
     cham_x, normals_x = _one_direction(x, y, x_lengths, y_lengths, x_normals, y_normals, weights, zero_weights, point_reduction, norm, abs_cosine)
     if single_directional:

@@ -2,8 +2,9 @@
  * csrc/volume_sample.hip, csrc/harmonic.hip (harmonic embedding, stratified ray depths), csrc/marching_cubes.hip,
  * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points), csrc/mesh_laplacian.hip (the cotangent
  * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing), csrc/mesh_edges.hip (the unique edges of a face list),
- * csrc/subdivide.hip (SubdivideMeshes), csrc/knn_features.hip (nearest neighbours between clouds of feature points) and
- * csrc/knn_grid.hip (nearest neighbours between large 3D clouds through a uniform grid).
+ * csrc/subdivide.hip (SubdivideMeshes), csrc/knn_features.hip (nearest neighbours between clouds of feature points),
+ * csrc/knn_grid.hip (nearest neighbours between large 3D clouds through a uniform grid) and csrc/chamfer_normals.hip
+ * (chamfer_distance with normals).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -425,6 +426,54 @@ size_t p3di_knn_grid_forward_workspace_bytes(int64_t N, int64_t P1, int64_t P2);
 int p3di_knn_grid_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
                           int64_t P2, int D, int K, int occupancy, int64_t* idx, float* dists, void* workspace,
                           size_t workspace_bytes, p3d_stream_t stream);
+
+/* ---- chamfer_distance with normals (csrc/chamfer_normals.hip): both directions of pytorch3d/loss/chamfer.py at D = 3 with
+ * x_normals and y_normals given.  x (N,P1,3), y (N,P2,3), x_normals (N,P1,3), y_normals (N,P2,3) contiguous f32; x_lengths /
+ * y_lengths (N) i64 or NULL (full; clamped into [0, P]); weights (N) f32 or NULL (1); norm 1 or 2.  Direction x -> y pairs row i of
+ * x with its nearest point of y[n, :y_lengths[n]], direction y -> x the other way round (absent with single_directional != 0).
+ *   idx      idx_x (N,P1), idx_y (N,P2) i64: what p3d_knn_points_forward returns for K = 1 with that norm, bit for bit -- the same
+ *            distance arithmetic (per coordinate the difference, squared or absolute, added in coordinate order, unfused), the
+ *            order (dist, smaller j), 0 in padding rows and where the far cloud is empty.  Every entry is written.
+ *   cosine   a = u / max(|u|, 1e-6), b = v / max(|v|, 1e-6), c = (a0 b0 + a1 b1) + a2 b2, |u| = sqrt((u0 u0 + u1 u1) + u2 u2), one
+ *            float32 rounding per operation: F.cosine_similarity(u, v, dim=2, eps=1e-6).  v is the far normal at idx, or zeros
+ *            where the far cloud is empty (then c = 0).
+ *   terms    for a row i < lengths[n]: dist * w and (1 - |c|) * w, or (1 - c) * w with abs_cosine == 0; 0 in both for padding rows.
+ *   point_reduction 0 (None): dist_x, normal_x (N,P1) and dist_y, normal_y (N,P2) hold the terms, every entry written; sums unused.
+ *   point_reduction 1 (sum), 2 (mean): sums (N, 2) = per cloud the two losses: each direction's terms added by the tree of
+ *            csrc/fixed_sum.h over waves of 64 consecutive rows (depth 6 + ceil(ceil(P / 64) / 256) + 8), divided by
+ *            max(lengths[n], 1) for mean, then x -> y plus y -> x.  No float atomic: the same bits on every run and stream.  The
+ *            four per-point pointers are unused.  workspace: p3di_chamfer_normals_forward_workspace_bytes(N, P1, P2) bytes, the
+ *            wave partials (smaller or NULL: P3D_ERR_WORKSPACE); not needed for point_reduction 0.
+ *   split    a workgroup is 64 rows and `split` waves, each scanning a slice of ceil(lengths / split) points of the far cloud in
+ *            LDS tiles of P3D_KNN_TILE; split in {1, 2, 4, 8}, or 0: the largest of them within ceil(P / P3D_KNN_TILE) of the
+ *            longer far cloud, but 4 where 8 waves a workgroup would be more than two waves on every SIMD.  No result depends on it.
+ * Two launches (one for point_reduction 0).  N == 0: P3D_OK without a launch.
+ * p3di_chamfer_normals_backward: idx_x / idx_y of the forward (range-checked: an index outside the far cloud is no hit).  The
+ *   upstream gradient of a row's distance term is (grad_dist == NULL ? 1 : grad_dist[n, i]) * (cloud_grad == NULL ? 1 :
+ *   cloud_grad[n]), divided by max(lengths[n], 1) of the row's own cloud where point_mean != 0, times weights[n] (NULL: 1) -- the
+ *   forward's steps backwards, a float32 operation each; of its normal term the same with grad_normal and cloud_grad[N + n].
+ *   cloud_grad (2, N): the gradients of the forward's sums.
+ *   Point gradients: p3d_knn_points_backward's terms.  Normal gradients: autograd's of the cosine above -- through the quotient
+ *   and, wherever |u| > 0, through the norm as if it were not clamped (torch clamps it outside the graph); |c| has slope 0 at c == 0.  grad_x, grad_y, grad_x_normals, grad_y_normals as
+ *   their inputs, each NULL to skip: first a lane per (direction, n, i) writes every entry with the row's own terms (zeros where
+ *   there are none; no memset in front), then the far side's terms are added with float atomics, lane = hit * 6 + value after
+ *   consecutive hits of one target were summed inside the wave.  Two launches; nothing to do (N (P1 + P2) == 0): P3D_OK.
+ * Negative sizes, sizes beyond INT32_MAX, N (ceil(P1 / 64) + ceil(P2 / 64)) beyond 2^27, a norm outside {1, 2}, a split outside
+ * {0, 1, 2, 4, 8}, a point_reduction outside {0, 1, 2}, missing pointers, a backward with P1 or P2 of 0: P3D_ERR_INVALID_ARG.
+ * No host sync. */
+#define P3D_CHAMFER_NORMALS_MAX_SPLIT 8
+size_t p3di_chamfer_normals_forward_workspace_bytes(int64_t N, int64_t P1, int64_t P2);
+int p3di_chamfer_normals_forward(const float* x, const float* y, const float* x_normals, const float* y_normals,
+                                 const int64_t* x_lengths, const int64_t* y_lengths, const float* weights, int64_t N, int64_t P1,
+                                 int64_t P2, int norm, int abs_cosine, int single_directional, int point_reduction, int split,
+                                 int64_t* idx_x, int64_t* idx_y, float* dist_x, float* normal_x, float* dist_y, float* normal_y,
+                                 float* sums, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+int p3di_chamfer_normals_backward(const float* x, const float* y, const float* x_normals, const float* y_normals,
+                                  const int64_t* x_lengths, const int64_t* y_lengths, const int64_t* idx_x, const int64_t* idx_y,
+                                  const float* weights, const float* cloud_grad, const float* grad_dist_x, const float* grad_normal_x,
+                                  const float* grad_dist_y, const float* grad_normal_y, int64_t N, int64_t P1, int64_t P2, int norm,
+                                  int abs_cosine, int single_directional, int point_mean, float* grad_x, float* grad_y, float* grad_x_normals,
+                                  float* grad_y_normals, p3d_stream_t stream);
 
 #ifdef __cplusplus
 }

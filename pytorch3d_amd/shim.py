@@ -67,7 +67,9 @@ reference classes runs on them end to end:
                                                                  one vertex twice go to the reference's functions
     ops.knn.knn_points / loss.chamfer.chamfer_distance        -> csrc/knn.hip: brute-force nearest neighbours, one lane per query;
                                                                  chamfer without normals is one autograd node with no host
-                                                                 sync; feature clouds (4 <= D <= 256, norm 2: EdgeConv graphs,
+                                                                 sync; chamfer with both normals (D = 3, point_reduction mean /
+                                                                 sum / None) -> csrc/chamfer_normals.hip, one node for (loss,
+                                                                 loss_normals); feature clouds (4 <= D <= 256, norm 2: EdgeConv graphs,
                                                                  descriptor matching) -> csrc/knn_features.hip, a matrix-instruction
                                                                  screen with an exact rescore; 3D clouds of knn.GRID_MIN_P2 points
                                                                  or more (None: never, the setting as measured) -> csrc/knn_grid.hip,
