@@ -1696,7 +1696,31 @@ def point_mesh_forward(direction, points, points_first_idx, prims, prims_first_i
     """One direction ("point_face", "face_point", "point_edge", "edge_point") of include/p3d_amd.h: p3d_point_mesh_forward ->
     (dists, idxs) over the QUERY objects -- points for point_*, tris / segms for face_point / edge_point --, idxs packed target
     indices; with_sums: also sums (N,), the element sums of dists * weights[n]."""
-    who = direction + "_dist_forward"
+    from . import point_mesh  # the one routing decision of the forward: every public way in comes through here
+
+    if point_mesh.grid_kernel_path(direction, points, prims):
+        return point_mesh_grid_forward(direction, points, points_first_idx, prims, prims_first_idx, max_queries, min_triangle_area,
+                                       weights=weights, with_sums=with_sums)
+    return _pm_forward("p3d_point_mesh_forward", direction, points, points_first_idx, prims, prims_first_idx, max_queries,
+                       min_triangle_area, int(split), weights, with_sums)
+
+
+def point_mesh_grid_forward(direction, points, points_first_idx, prims, prims_first_idx, max_queries, min_triangle_area=5e-3,
+                            occupancy=0, weights=None, with_sums=False):
+    """point_mesh_forward for "point_face" / "point_edge" through a uniform grid per batch element (csrc/point_mesh_grid.hip): the
+    same (dists, idxs[, sums]), bit for bit, without the scan of all pairs.  occupancy: the wanted number of targets per grid cell,
+    0 for the library's default; it changes the time, never the result.  No host sync."""
+    if int(occupancy) < 0:
+        raise RuntimeError("point_mesh_grid_forward: occupancy must be >= 0")
+    return _pm_forward("p3di_point_mesh_grid_forward", direction, points, points_first_idx, prims, prims_first_idx, max_queries,
+                       min_triangle_area, int(occupancy), weights, with_sums)
+
+
+def _pm_forward(entry, direction, points, points_first_idx, prims, prims_first_idx, max_queries, min_triangle_area, knob, weights,
+                with_sums):
+    """The all-pairs entry (knob: split) or the grid entry (knob: occupancy): the same arguments otherwise."""
+    grid = entry == "p3di_point_mesh_grid_forward"
+    who = direction + ("_grid_forward" if grid else "_dist_forward")
     dev, points, prims = _pm_check(direction, points, prims, who, points_first_idx=points_first_idx, prims_first_idx=prims_first_idx)
     pfirst, sfirst = _pm_first(points_first_idx, prims_first_idx, who)
     qk, tk = _PM_KINDS[direction]
@@ -1715,10 +1739,14 @@ def point_mesh_forward(direction, points, points_first_idx, prims, prims_first_i
     sums, ws, nbytes = None, None, 0
     if with_sums:
         sums = torch.empty((N,), dtype=torch.float32, device=dev)
+    if grid:
+        nbytes = lib.p3di_point_mesh_grid_forward_workspace_bytes(N, Q, T)
+    elif with_sums:
         nbytes = lib.p3d_point_mesh_forward_workspace_bytes(N, max_queries)
+    if grid or with_sums:
         ws = _workspace(nbytes, dev)
-    _lib.call("p3d_point_mesh_forward", who, dev, qk, tk, q, t, qf, tf, N, Q, T, max_queries, float(min_triangle_area), int(split), weights,
-              dists, idxs, sums, ws, nbytes)
+    _lib.call(entry, who, dev, qk, tk, q, t, qf, tf, N, Q, T, max_queries, float(min_triangle_area), knob, weights, dists, idxs, sums, ws,
+              nbytes)
     return (dists, idxs, sums) if with_sums else (dists, idxs)
 
 

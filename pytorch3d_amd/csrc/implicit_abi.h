@@ -427,6 +427,38 @@ int p3di_knn_grid_forward(const float* p1, const float* p2, const int64_t* lengt
                           int64_t P2, int D, int K, int occupancy, int64_t* idx, float* dists, void* workspace,
                           size_t workspace_bytes, p3d_stream_t stream);
 
+/* ---- point -> nearest face / edge through a uniform grid (csrc/point_mesh_grid.hip): the two point-query directions of
+ * p3d_point_mesh_forward of include/p3d_amd.h -- query_kind P3D_POINT_MESH_POINT, target_kind P3D_POINT_MESH_TRIANGLE or
+ * P3D_POINT_MESH_SEGMENT -- and the SAME dists, idxs and sums, bit for bit: the pair functions of csrc/point_mesh_geom.h (float32,
+ * unfused, min_triangle_area compared in double), among equal distances the largest packed target index, a NaN distance never
+ * selected, FLT_MAX / 0 for an element without targets, every entry of dists and idxs written (no memset), sums (N, or NULL) the
+ * element sums of dists[q] * weights[n] (weights NULL: 1) by the tree of csrc/fixed_sum.h over waves of 64 CONSECUTIVE queries.  The
+ * arguments are p3d_point_mesh_forward's with `occupancy` in the place of `split`.
+ * The grid only decides which pairs are never evaluated.  Per batch element it is chosen on the device (no host sync) from the
+ * bounding box of the finite target vertices, the element's target count and `occupancy`, the wanted number of targets per cell
+ * (0: P3D_POINT_MESH_GRID_OCCUPANCY), with at most min(max(targets of the element, 1), P3D_POINT_MESH_GRID_MAX_CELLS) cells.  A
+ * target is registered in every cell its box overlaps; one that overlaps more than P3D_POINT_MESH_GRID_MAX_REFS cells (or more than
+ * three along an axis), has a coordinate that is not finite, or is a triangle with a possible inside branch and
+ * |cross| < max(longest edge^2 / 4, 2^-7) goes to the element's large list, which every query of the element scans.  A query stops
+ * when its best distance is strictly below a proven lower bound of the computed distance to every target it has not seen (the
+ * proof is at stop_bound in the source); one that cannot stop (NaN, far outside the box, a cloud far from the origin, cells
+ * smaller than the bound's slack) scans its element's whole target list, after at most as many references again.  The order
+ * of the integer atomics that fill the cells differs from run to run; the result does not.
+ * workspace: p3di_point_mesh_grid_forward_workspace_bytes(N, Q, T) bytes (0 for N <= 0), a function of the sizes alone, needed with
+ * and without sums; every byte read was written by the same call; smaller or NULL with N > 0: P3D_ERR_WORKSPACE.
+ * Kinds that are no direction of p3d_point_mesh_forward, negative sizes, N or Q beyond INT32_MAX, T beyond
+ * INT32_MAX / (2 P3D_POINT_MESH_GRID_MAX_REFS), occupancy < 0, missing pointers, Q > 0 with N == 0 or max_queries == 0:
+ * P3D_ERR_INVALID_ARG.  A query kind other than P3D_POINT_MESH_POINT (face_point, edge_point): P3D_ERR_UNSUPPORTED.  All of that
+ * before any launch. */
+#define P3D_POINT_MESH_GRID_OCCUPANCY 4
+#define P3D_POINT_MESH_GRID_MAX_REFS 12
+#define P3D_POINT_MESH_GRID_MAX_CELLS 4194304
+size_t p3di_point_mesh_grid_forward_workspace_bytes(int64_t N, int64_t Q, int64_t T);
+int p3di_point_mesh_grid_forward(int query_kind, int target_kind, const float* queries, const float* targets,
+                                 const int64_t* query_first_idx, const int64_t* target_first_idx, int64_t N, int64_t Q, int64_t T,
+                                 int64_t max_queries, double min_triangle_area, int occupancy, const float* weights, float* dists,
+                                 int64_t* idxs, float* sums, void* workspace, size_t workspace_bytes, p3d_stream_t stream);
+
 /* ---- chamfer_distance with normals (csrc/chamfer_normals.hip): both directions of pytorch3d/loss/chamfer.py at D = 3 with
  * x_normals and y_normals given.  x (N,P1,3), y (N,P2,3), x_normals (N,P1,3), y_normals (N,P2,3) contiguous f32; x_lengths /
  * y_lengths (N) i64 or NULL (full; clamped into [0, P]); weights (N) f32 or NULL (1); norm 1 or 2.  Direction x -> y pairs row i of

@@ -18,6 +18,11 @@ maximum counts are the host integers the structures already hold (pcls._P, meshe
 by 3 _F).  The backward's target side uses float atomics or, under torch.use_deterministic_algorithms(True), the ordered sum of
 csrc/ordered_sum.h.
 
+Where GRID_MIN_TARGETS is a number, the two point-query forwards (point_face, point_edge) of batches with that many packed targets
+take csrc/point_mesh_grid.hip instead: a uniform grid per element, the same dists, idxs and loss bits without the scan of all
+pairs; the decision is made once, in _C.point_mesh_forward, for the operators, the distances and the fused losses alike.  The two
+target-query directions stay on the scan of all pairs (the next step).
+
 CPU tensors, float64 and everything else the kernels do not take go to the torch formulation below: the same contract and tie rule,
 the (rows, targets) distances in bounded chunks, an explicit backward with the kernels' formulas.
 """
@@ -32,12 +37,23 @@ CHUNK_ELEMENTS = 1 << 20  # the torch formulation keeps at most this many (row, 
 SPLIT = 0  # waves per workgroup in the fused losses' forwards: 0 = the library chooses (profiles/point_mesh_bench.py forces 1 for one leg)
 
 _DIRECTIONS = ("point_face", "face_point", "point_edge", "edge_point")
+# The packed number of targets (faces / edges of the whole batch) from which the two point-query forwards take the grid search of
+# csrc/point_mesh_grid.hip; None: never (the entry stays reachable as _C.point_mesh_grid_forward).  A number only where the grid wins
+# on every measured distribution at and above it (the rule of knn.GRID_MIN_P2): see DESIGN 8.32 for what was measured.
+GRID_MIN_TARGETS = None
 
 
 def kernel_path(points, prims):
     """Whether these tensors run csrc/point_mesh.hip (else: the torch formulation)."""
     return (torch.is_tensor(points) and torch.is_tensor(prims) and points.is_cuda and prims.is_cuda and points.device == prims.device
             and points.dtype == torch.float32 and prims.dtype == torch.float32)
+
+
+def grid_kernel_path(direction, points, prims):
+    """Whether the forward of `direction` on these tensors runs csrc/point_mesh_grid.hip (its backward: csrc/point_mesh.hip's, from
+    idxs).  Decided from the packed total alone: nothing is read from the device.  The target-query directions never do."""
+    return (GRID_MIN_TARGETS is not None and direction in ("point_face", "point_edge") and kernel_path(points, prims)
+            and prims.shape[0] >= GRID_MIN_TARGETS)
 
 
 # ---- the torch formulation -------------------------------------------------------------------------------------------------------

@@ -78,8 +78,11 @@ reference classes runs on them end to end:
                                                                  a stub that raises)
     loss.point_mesh_distance.point_mesh_face_distance / point_mesh_edge_distance -> csrc/point_mesh.hip: one autograd node each (face /
                                                                  edge gather, two fused brute-force forwards with fixed-tree sums,
-                                                                 two backward kernels, the vertex scatter) and no host sync; other
-                                                                 inputs go to this package's torch formulation
+                                                                 two backward kernels, the vertex scatter) and no host sync; with
+                                                                 point_mesh.GRID_MIN_TARGETS packed targets or more (None: never, the
+                                                                 setting as measured) the point-query forward is csrc/point_mesh_grid.hip,
+                                                                 the same bits through a uniform grid; other inputs go to this
+                                                                 package's torch formulation
     ops.sample_points_from_meshes.sample_points_from_meshes   -> csrc/sample_points.hip: one autograd node, a deterministic function of
                                                                  ONE torch.rand((N, S, 3)) (torch's multinomial stream is not
                                                                  reproduced: same distribution, other draws); other inputs go to
