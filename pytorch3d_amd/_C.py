@@ -1044,6 +1044,24 @@ def knn_grid_idx(p1, p2, lengths1, lengths2, K, occupancy=0):
     return idx, dists
 
 
+def knn_tree_idx(p1, p2, lengths1, lengths2, K):
+    """knn_points_idx with norm 2 at D = 3 through a tree of boxes per cloud (csrc/knn_tree.hip): the same (idx, dists), bit for bit,
+    without the scan of all pairs, whatever the distribution of the points.  No host sync."""
+    K = int(K)
+    dev, lengths1, lengths2 = _knn_check(p1, p2, lengths1, lengths2, K, "knn_tree_idx")
+    if p1.shape[2] != 3:
+        raise RuntimeError("knn_tree_idx: the tree search takes D = 3; knn_points_idx takes D = 2")
+    p1, p2 = _c(p1, torch.float32), _c(p2, torch.float32)
+    N, P1, D = p1.shape
+    P2 = p2.shape[1]
+    idx = torch.empty((N, P1, K), dtype=torch.int64, device=dev)
+    dists = torch.empty((N, P1, K), dtype=torch.float32, device=dev)
+    nbytes = _lib.load().p3di_knn_tree_forward_workspace_bytes(N, P1, P2)
+    ws = _workspace(nbytes, dev)
+    _lib.call("p3di_knn_tree_forward", "knn_tree_idx", dev, p1, p2, lengths1, lengths2, N, P1, P2, D, K, idx, dists, ws, nbytes)
+    return idx, dists
+
+
 def knn_points_backward(p1, p2, lengths1, lengths2, idxs, norm, grad_dists, _needs=(True, True)):
     """KNearestNeighborBackward (knn.h): (grad_p1 (N, P1, D), grad_p2 (N, P2, D)).  grad_p1 is a gather; grad_p2 a scatter with
     float atomics or, under torch.use_deterministic_algorithms(True), the ordered sum.  _needs (not part of the reference's

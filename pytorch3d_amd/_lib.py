@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("P3D_LIB_PATH") or os.path.join(_HERE, "libp3d_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "p3d_amd.h")
 # the extension ABI of csrc/implicit.hip, cubify.hip, volume_sample.hip, harmonic.hip, marching_cubes.hip, points_alignment.hip,
-# mesh_laplacian.hip, mesh_edges.hip, subdivide.hip, knn_features.hip, knn_grid.hip, chamfer_normals.hip and point_mesh_grid.hip: entries
+# mesh_laplacian.hip, mesh_edges.hip, subdivide.hip, knn_features.hip, knn_grid.hip, knn_tree.hip, chamfer_normals.hip and point_mesh_grid.hip: entries
 # p3di_*, declared in a header of their own (see its head)
 EXTENSION_HEADER_PATH = os.path.join(_HERE, "csrc", "implicit_abi.h")
 EXTENSION_PREFIX = "p3di_"

@@ -20,7 +20,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.environ.get("P3D_LIB_PATH") or os.path.join(HERE, "libp3d_amd.so")
 ARCH = "gfx950"
 
-SOURCES = ["binning.hip", "raster_mesh.hip", "raster_mesh_bwd.hip", "gather.hip", "transform.hip", "raster_points.hip", "render_points.hip", "composite.hip", "blend.hip", "clip.hip", "interp.hip", "shade.hip", "soft_phong.hip", "splatter.hip", "texture.hip", "texture_multi.hip", "atlas.hip", "ordered_bwd.hip", "normals.hip", "mesh_losses.hip", "mesh_laplacian.hip", "mesh_edges.hip", "subdivide.hip", "knn.hip", "knn_features.hip", "knn_grid.hip", "chamfer_normals.hip", "point_mesh.hip", "point_mesh_grid.hip", "sample_points.hip", "fps_ball.hip", "points_to_volumes.hip", "point_frames.hip", "box3d.hip", "graph_conv.hip", "vert_align.hip", "implicit.hip", "cubify.hip", "marching_cubes.hip", "volume_sample.hip", "harmonic.hip", "points_alignment.hip", "profile.cpp"]
+SOURCES = ["binning.hip", "raster_mesh.hip", "raster_mesh_bwd.hip", "gather.hip", "transform.hip", "raster_points.hip", "render_points.hip", "composite.hip", "blend.hip", "clip.hip", "interp.hip", "shade.hip", "soft_phong.hip", "splatter.hip", "texture.hip", "texture_multi.hip", "atlas.hip", "ordered_bwd.hip", "normals.hip", "mesh_losses.hip", "mesh_laplacian.hip", "mesh_edges.hip", "subdivide.hip", "knn.hip", "knn_features.hip", "knn_grid.hip", "knn_tree.hip", "chamfer_normals.hip", "point_mesh.hip", "point_mesh_grid.hip", "sample_points.hip", "fps_ball.hip", "points_to_volumes.hip", "point_frames.hip", "box3d.hip", "graph_conv.hip", "vert_align.hip", "implicit.hip", "cubify.hip", "marching_cubes.hip", "volume_sample.hip", "harmonic.hip", "points_alignment.hip", "profile.cpp"]
 # what a source may include (paths relative to csrc/): every header on disk, so that a new one cannot be left out of needs_build()
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "p3d_amd.h")]
 
@@ -33,8 +33,8 @@ FLAGS = [
 ]
 
 # per source, behind FLAGS: the float4 arithmetic of subdivide.hip stays out of v_pk_*_f32 as the scalar code does without the SLP
-# vectorizer (the two files are integer and copy code otherwise); the distances of knn_features.hip and knn_grid.hip are contract arithmetic, scalar by definition
-SOURCE_FLAGS = {s: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] for s in ("mesh_edges.hip", "subdivide.hip", "knn_features.hip", "knn_grid.hip")}
+# vectorizer (the two files are integer and copy code otherwise); the distances of knn_features.hip, knn_grid.hip and knn_tree.hip are contract arithmetic, scalar by definition
+SOURCE_FLAGS = {s: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"] for s in ("mesh_edges.hip", "subdivide.hip", "knn_features.hip", "knn_grid.hip", "knn_tree.hip")}
 
 
 # Kernels that keep registers in AGPRs (more than 256 live VGPRs at one wave per SIMD).  Round 4 saw kernels of raster_mesh.hip

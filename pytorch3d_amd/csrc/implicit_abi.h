@@ -3,8 +3,8 @@
  * csrc/points_alignment.hip (iterative closest point, alignment of corresponding points), csrc/mesh_laplacian.hip (the cotangent
  * Laplacian's smoothing loss, cot_laplacian and taubin_smoothing), csrc/mesh_edges.hip (the unique edges of a face list),
  * csrc/subdivide.hip (SubdivideMeshes), csrc/knn_features.hip (nearest neighbours between clouds of feature points),
- * csrc/knn_grid.hip (nearest neighbours between large 3D clouds through a uniform grid) and csrc/chamfer_normals.hip
- * (chamfer_distance with normals).
+ * csrc/knn_grid.hip and csrc/knn_tree.hip (nearest neighbours between large 3D clouds through a uniform grid and through a tree of
+ * boxes) and csrc/chamfer_normals.hip (chamfer_distance with normals).
  *
  * An extension of include/p3d_amd.h with a header and a prefix of its own: the entries of that header (p3d_*) are a closed set that
  * the ABI tests count and compare with the library's exports, so these entries are named p3di_* and declared here.  Same
@@ -426,6 +426,28 @@ size_t p3di_knn_grid_forward_workspace_bytes(int64_t N, int64_t P1, int64_t P2);
 int p3di_knn_grid_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
                           int64_t P2, int D, int K, int occupancy, int64_t* idx, float* dists, void* workspace,
                           size_t workspace_bytes, p3d_stream_t stream);
+
+/* ---- nearest neighbours between large 3D clouds through a tree of boxes (csrc/knn_tree.hip): p3d_knn_points_forward of
+ * include/p3d_amd.h at D = 3, norm 2, and the SAME idx and dists, bit for bit -- the same distance arithmetic, the (dist, j) order,
+ * the same zeros in padding rows and slots -- at a cost that follows the density of the data where one far point would squeeze a
+ * uniform grid into a few cells.  The arguments are p3di_knn_grid_forward's without `occupancy`.
+ * Per cloud, on the device, no host sync and no atomic: the box of the finite points of p2[n]; a 63-bit Morton key per point and per
+ * query, 21 bits an axis; both in key order by a bitonic network of the library's own; the points as records (x, y, z, j); a leaf per
+ * P3D_KNN_TREE_LEAF consecutive records with the exact minimum and maximum of its points as its box; an inner node per
+ * P3D_KNN_TREE_FANOUT consecutive nodes of the level below with the union of theirs.  A wave searches for 64 consecutive queries of
+ * the key order with one stack: a node is skipped only where, in every lane, the contract's own distance from the query to the
+ * nearest point of the node's box is STRICTLY above the lane's min(K, lengths2[n])-th distance so far (the proof that this is a
+ * lower bound as floats is at box_bound in the source).  A query that cannot skip (NaN, lengths2[n] < K, all points identical)
+ * visits every leaf once.  The order of the keys decides the time alone, never the result.
+ * D != 3 or K > P3D_KNN_MAX_K: P3D_ERR_UNSUPPORTED; negative sizes, P1 or P2 above 2^30, missing pointers: P3D_ERR_INVALID_ARG.
+ * workspace: p3di_knn_tree_forward_workspace_bytes(N, P1, P2) bytes (0 for N <= 0 or P1 <= 0), a function of the sizes alone, every
+ * byte read was written by the same call; smaller or NULL: P3D_ERR_WORKSPACE.  All of that before any launch. */
+#define P3D_KNN_TREE_LEAF 64
+#define P3D_KNN_TREE_FANOUT 8
+size_t p3di_knn_tree_forward_workspace_bytes(int64_t N, int64_t P1, int64_t P2);
+int p3di_knn_tree_forward(const float* p1, const float* p2, const int64_t* lengths1, const int64_t* lengths2, int64_t N, int64_t P1,
+                          int64_t P2, int D, int K, int64_t* idx, float* dists, void* workspace, size_t workspace_bytes,
+                          p3d_stream_t stream);
 
 /* ---- point -> nearest face / edge through a uniform grid (csrc/point_mesh_grid.hip): the two point-query directions of
  * p3d_point_mesh_forward of include/p3d_amd.h -- query_kind P3D_POINT_MESH_POINT, target_kind P3D_POINT_MESH_TRIANGLE or

@@ -11,7 +11,10 @@ is accepted and ignored; the result is always sorted.  One autograd node; `lengt
 float32 GPU tensors with D in {2, 3} and K <= 32 take the kernels of csrc/knn.hip (include/p3d_amd.h): every pair is looked at.
 Where GRID_MIN_P2 is a number, 3D clouds with norm 2 and p2.shape[1] >= GRID_MIN_P2 take csrc/knn_grid.hip instead: a uniform grid
 per cloud, built on the device, and a search that grows a box of cells around 64 neighbouring queries until a proven bound says that
-nothing outside can enter a queue -- the same idx and dists, bit for bit, and the backward of csrc/knn.hip.  Feature clouds -- float32
+nothing outside can enter a queue -- the same idx and dists, bit for bit, and the backward of csrc/knn.hip.  Where TREE_MIN_P2 is a
+number, the same clouds with p1.shape[1] and p2.shape[1] >= TREE_MIN_P2 take csrc/knn_tree.hip first: the points in Morton order under a tree of
+exact boxes, built on the device, and a walk that skips a box only where the contract's own distance to it is strictly above every
+query's K-th distance -- again the same bits and the same backward, at a cost that follows the density of the data.  Feature clouds -- float32
 GPU tensors with 4 <= D <= 256, K <= 32 and norm 2 -- take csrc/knn_features.hip: a screen of the pairs on the matrix instruction
 and the contract's arithmetic for those that pass, the bits of the torch formulation.  Everything else -- CPU tensors, float64, D = 1
 or D > 256, L1 at D > 3, larger K -- takes the torch formulation below: the same contract, the (P1, P2) distances computed in
@@ -33,6 +36,13 @@ CHUNK_ELEMENTS = 1 << 22  # the torch formulation keeps at most this many distan
 # (profiles/knn_grid_mi355x.txt): uniform and surface clouds win from 262 144 points on, 9 - 56 x at 10^6, but a cloud with far
 # outliers loses at every size.  Callers who know their clouds set a number here, e.g. 262144.
 GRID_MIN_P2 = None
+# The padded size of BOTH clouds from which knn_points takes the tree search, ahead of the grid; None: never (the entry stays
+# reachable as _C.knn_tree_idx).  The rule is GRID_MIN_P2's: the smallest swept P from which the tree beats the scan of all pairs on all three
+# distributions and K by more than the spread of the legs.  profiles/knn_tree_mi355x.txt: from 262 144 on for one cloud (1.8 - 33 x
+# there, 15 - 168 x at 10^6; the spread is below 5 %), from 32 768 on for eight; at 32 768 one cloud of clusters loses at K = 32
+# (2.95 against 2.57 ms), at 4096 nearly everything does.
+TREE_MIN_P2 = 262144
+TREE_MAX_P = 1 << 30  # p3di_knn_tree_forward answers P3D_ERR_INVALID_ARG above it: its padded key tables are indexed by int
 
 
 def kernel_path(p1, p2, K):
@@ -45,6 +55,14 @@ def kernel_path(p1, p2, K):
 def grid_kernel_path(p1, p2, K, norm=2):
     """Whether knn_points(p1, p2, K=K, norm=norm) runs csrc/knn_grid.hip (its backward: csrc/knn.hip's)."""
     return (GRID_MIN_P2 is not None and kernel_path(p1, p2, K) and p1.shape[2] == 3 and norm == 2 and p2.shape[1] >= GRID_MIN_P2)
+
+
+def tree_kernel_path(p1, p2, K, norm=2):
+    """Whether knn_points(p1, p2, K=K, norm=norm) runs csrc/knn_tree.hip (its backward: csrc/knn.hip's).  BOTH clouds must reach
+    TREE_MIN_P2: the sweep behind it had P1 == P2, and a few queries against a large p2 would pay the whole build of keys, order and
+    boxes per call, which nobody has measured.  Clouds above TREE_MAX_P, which the entry refuses, keep the scan of all pairs."""
+    return (TREE_MIN_P2 is not None and kernel_path(p1, p2, K) and p1.shape[2] == 3 and norm == 2
+            and TREE_MIN_P2 <= min(p1.shape[1], p2.shape[1]) and max(p1.shape[1], p2.shape[1]) <= TREE_MAX_P)
 
 
 def feature_kernel_path(p1, p2, K, norm=2):
@@ -160,9 +178,11 @@ def backward_kernels(p1, p2, lengths1, lengths2, idx, K, norm, grad_dists, cloud
 class _KnnPoints(torch.autograd.Function):
     @staticmethod
     def forward(ctx, p1, p2, lengths1, lengths2, K, norm, fused):
-        """fused: "points" (csrc/knn.hip), "grid" (csrc/knn_grid.hip; the backward of "points"), "features" (csrc/knn_features.hip)
-        or None (the torch formulation)."""
-        if fused == "grid":
+        """fused: "points" (csrc/knn.hip), "tree" (csrc/knn_tree.hip) and "grid" (csrc/knn_grid.hip), both with the backward of
+        "points", "features" (csrc/knn_features.hip) or None (the torch formulation)."""
+        if fused == "tree":
+            idx, dists = _C.knn_tree_idx(p1, p2, lengths1, lengths2, K)
+        elif fused == "grid":
             idx, dists = _C.knn_grid_idx(p1, p2, lengths1, lengths2, K)
         elif fused == "points":
             idx, dists = _C.knn_points_idx(p1, p2, lengths1, lengths2, norm, K, -1)
@@ -181,7 +201,7 @@ class _KnnPoints(torch.autograd.Function):
     def backward(ctx, grad_dists, _grad_idx):
         p1, p2, idx = ctx.saved_tensors
         lengths1, lengths2 = ctx.lengths
-        if ctx.fused in ("points", "grid"):
+        if ctx.fused in ("points", "tree", "grid"):
             grad_p1, grad_p2 = _C.knn_points_backward(p1, p2, lengths1, lengths2, idx, ctx.norm, grad_dists,
                                                       _needs=ctx.needs_input_grad[:2])
         elif ctx.fused == "features" and not _C._ordered():
@@ -207,7 +227,9 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, 
     N = p1.shape[0]
     lengths1 = _lengths_arg(lengths1, N, p1.device, "lengths1")
     lengths2 = _lengths_arg(lengths2, N, p1.device, "lengths2")
-    if grid_kernel_path(p1, p2, K, norm):
+    if tree_kernel_path(p1, p2, K, norm):
+        fused = "tree"
+    elif grid_kernel_path(p1, p2, K, norm):
         fused = "grid"
     elif kernel_path(p1, p2, K):
         fused = "points"
